@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the batched MyoSuite env.step() hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Workload (BASELINE.json metric): myoHandPoseRandom-v0, 4096 envs per GPU (weak scaling), one "step" = one
@@ -74,6 +74,37 @@ def cpu_baseline(seconds_target=12.0):
             "sample": f"{B} envs x {done_steps} env-steps (10 substeps each) of {ENV_ID}, f64 C oracle, {cores} threads, {el:.1f}s"}
 
 
+# what a caller of env.step() receives after a step (observation, reward, done / solved, episode step counter) and the state it leaves
+DUMP_FIELDS = (("obs", "F_OBS"), ("reward", "F_REWARD"), ("done", "F_DONE"), ("solved", "F_SOLVED"), ("elapsed", "F_ELAPSED"),
+               ("qpos", "F_QPOS"), ("qvel", "F_QVEL"), ("act", "F_ACT"), ("time", "F_TIME"))
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(capi, batch, out_dir, seed=0):
+    """Writes the fields of DUMP_FIELDS as out_dir/<name>.npy (float32; integer fields as float64).  If they exceed DUMP_MAX_BYTES together,
+    the same fixed, seeded sample of env rows is kept in every array and its indices are written as env_index.npy."""
+    import numpy as np
+    arrs = {}
+    for name, f in DUMP_FIELDS:
+        a = batch.read(getattr(capi, f))
+        if a.shape[1] == 0:
+            continue
+        arrs[name] = a.astype(np.float64) if a.dtype.kind == "i" else a.astype(np.float32)
+    per_env = sum(a.itemsize * a.shape[1] for a in arrs.values())
+    n = len(next(iter(arrs.values())))
+    keep = n
+    if n * per_env > DUMP_MAX_BYTES:
+        keep = (DUMP_MAX_BYTES - (64 << 10)) // (per_env + 8)          # room for env_index and the .npy headers
+    if keep < n:
+        idx = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+        arrs = {k: v[idx] for k, v in arrs.items()}
+        arrs["env_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrs.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(v))
+    return sorted(arrs)
+
+
 def rollout_multi(torch, env, nsteps, mode, stream, obs, staging, gather_async):
     """The N > 1 loop: nothing waits on the host.  The observation all-gather of step t (RCCL over xGMI, on the process group's own
     stream) overlaps the step kernel of step t+1: the observations are first copied into `staging`, and the compute stream only waits
@@ -105,6 +136,8 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--repeats", type=int, default=1, help="repeat the timed region R times and report the median run (SURVEY 8d config 2: 5); default 1 = the plain contract")
     ap.add_argument("--env", default=ENV_ID, help="env id (default: the BASELINE.json headline workload); other ids are extra measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0's envs) as DIR/<name>.npy")
     args = ap.parse_args()
     env_id = "MyoHandAirplaneRandom-v0" if args.env == TRACK_ALIAS else args.env
 
@@ -173,6 +206,7 @@ def main():
             el = float(t.item())
         runs.append((el, ev_ms, kernel_ms_total))
     el, ev_ms, kernel_ms_total = sorted(runs)[len(runs) // 2]            # median run (the only run when --repeats 1)
+    dumped = dump_outputs(capi, env.batch, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     # N > 1: the observation all-gather on its own ("gather time separately"), outside the timed region: in the
     # rollout it overlaps the next step kernel, here 20 back-to-back gathers are timed with nothing else running
     gather_ms = None
@@ -259,6 +293,7 @@ def main():
             **({"allgather_ms_rank0": gather_ms, "allgather_bytes_out": int(gathered.numel() * 4)} if gather_ms is not None else {}),
             **({"rehearsal": "all ranks on one GPU over gloo: control-flow check only"} if os.environ.get("MYO_BENCH_REHEARSAL") == "1" else {}),
             "flagged_envs": int((flags != 0).sum()),
+            **({"dumped_outputs": {"dir": args.dump_outputs, "arrays": dumped}} if dumped is not None else {}),
         }
         if not args.no_cpu_baseline and world == 1 and env_id == ENV_ID:
             out["cpu_baseline"] = cpu_baseline()

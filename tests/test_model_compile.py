@@ -75,7 +75,6 @@ def test_finger_asset_matches_fresh_compile(finger):
         assert np.allclose(np.asarray(v, float), np.asarray(finger.arrays[k], float), rtol=0, atol=1e-12), k
 
 
-@needs_reference
 def test_unsupported_feature_raises(tmp_path):
     from myosuite_mjx_amd.mjcf import compile_mjcf
     p = tmp_path / "m.xml"

@@ -4,6 +4,7 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "myosuite_mjx_amd", "libmyo_hip.so")
@@ -11,15 +12,12 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 
 
 def resources(lib=LIB):
-    tmp = "/tmp/_myo_co"
-    os.makedirs(tmp, exist_ok=True)
-    subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                           f"--input={lib}", f"--output={tmp}/k.co"], stderr=subprocess.DEVNULL) if False else None
-    # the fat binary sits in .hip_fatbin; extract it, then unbundle
-    subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", lib, f"{tmp}/fat.bin"])
-    subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                           f"--input={tmp}/fat.bin", f"--output={tmp}/k.co"])
-    txt = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", f"{tmp}/k.co"], text=True)
+    with tempfile.TemporaryDirectory(prefix="myo_co_") as tmp:
+        # the fat binary sits in .hip_fatbin; extract it, then unbundle
+        subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", lib, f"{tmp}/fat.bin"])
+        subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                               f"--input={tmp}/fat.bin", f"--output={tmp}/k.co"])
+        txt = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", f"{tmp}/k.co"], text=True)
     out = []
     for blk in txt.split("- .agpr_count:")[1:]:
         g = lambda k: re.search(r"\.%s:\s+(\S+)" % k, blk)

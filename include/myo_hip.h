@@ -71,6 +71,23 @@ typedef enum myo_field {
                         computed it, i.e. at the state before that substep's integration: what an MJX pipeline_state holds in xpos / xmat
                         after mjx.step (forward, then integrate; mjx/myodm_v0.py:201-232 reads it).  Models of the TrackEnv class only */
   MYO_F_METRICS,     /* [B][4] reward terms of the track task: pose, object, bonus, penalty (mjx/myodm_v0.py:243-262 `rwd_dict`) */
+  MYO_F_BODYMASS,    /* [B][nbody] mass of every body in every env (mjModel.body_mass, compiled-model body numbering): the per-env
+                        `model.body_mass[bid] = ...` of PoseEnvV0.reset (envs/myo/myobase/pose_v0.py:163-176, weight_bodyname / weight_range).
+                        The per-env body-mass override starts the first time this field or MYO_F_BODYMASS_RANGE is written (myo_batch_write)
+                        or its device pointer is handed out (myo_batch_field): both buffers are allocated, the masses filled with the model's
+                        body_mass, the ranges with zeros.  Before that, myo_batch_read returns the model's masses and starts nothing.
+                        The step uses the masses as they are at the launch (a device-side write takes effect at the next myo_step); the
+                        link mass / COM / inertia of every link are recomposed from them once per launch.  As with mjModel.body_mass edited
+                        at run time without mj_setConst, nothing else changes: body_inertia, acc0, the invweights (constraint impedance)
+                        and muscle lengthrange keep their compiled values.  Bodies welded to the world have no dynamic effect: their entries
+                        are accepted and ignored.  A host write with a negative mass returns MYO_E_ARG; device-side writes are the caller's
+                        responsibility.  Refused (MYO_E_UNSUPPORTED) for RK4 models, TrackEnv-class models, height-field models, the lanes
+                        kernel (myo_set_lanes != 64) and batches configured for MYO_TASK_WALK / STAND / TRACK (their observations and
+                        rewards use model-wide mass totals).  Hand / leg models that start it step on the run-time-sizes kernel of their class */
+  MYO_F_BODYMASS_RANGE, /* [B][2*nbody] per-env mass range: a `lo` block (nbody) then a `hi` block (nbody).  At every reset of an env
+                        (myo_reset, myo_autoreset) each body with hi > lo gets mass = lo + (hi - lo) u, u ~ U(0,1) from the counter RNG
+                        keyed by (episode seed, global env id, body); bodies with lo == hi keep their mass.  Starts the override like
+                        MYO_F_BODYMASS; a host write with lo < 0 or hi < lo returns MYO_E_ARG */
   MYO_F_COUNT
 } myo_field;
 

@@ -14,7 +14,8 @@ SRC_PATH = os.path.join(_HERE, "csrc", "myo_hip.hip")
 
 # field ids (myo_field)
 (F_QPOS, F_QVEL, F_ACT, F_CTRL, F_WARMSTART, F_TIME, F_TARGET, F_OBS, F_REWARD, F_DONE, F_SOLVED, F_FLAGS, F_DIAG,
- F_QACC, F_TENLEN, F_ACTFORCE, F_SITEXPOS, F_ELAPSED, F_ACTION, F_FATIGUE, F_HFIELD, F_GEOMSIZE, F_LINKX, F_METRICS) = range(24)
+ F_QACC, F_TENLEN, F_ACTFORCE, F_SITEXPOS, F_ELAPSED, F_ACTION, F_FATIGUE, F_HFIELD, F_GEOMSIZE, F_LINKX, F_METRICS,
+ F_BODYMASS, F_BODYMASS_RANGE) = range(26)
 INT_FIELDS = (F_FLAGS, F_DIAG, F_ELAPSED)
 BENCH_OBS, BENCH_FRESH_ACTIONS, BENCH_AUTORESET = 1, 2, 4
 ACTMAP_NONE, ACTMAP_MUSCLE_SIGMOID, ACTMAP_SIGMOID_FATIGUE, ACTMAP_SIGMOID_REAFFERENTATION, ACTMAP_CTRLRANGE = 0, 1, 2, 3, 4
@@ -342,19 +343,35 @@ class HipBatch:
     def obs_reset_only(self, stream=None):
         _chk(lib().myo_obs_reset_only(self.h, stream))
 
+    def set_body_mass_range(self, lo, hi):
+        """Per-env body-mass ranges ([B, nbody] or [nbody] each): every reset of an env draws mass ~ U(lo, hi) for the bodies with
+        hi > lo (MYO_F_BODYMASS_RANGE); starts the per-env body-mass override."""
+        nb = self.model.dims.nbody
+        lo = np.broadcast_to(np.asarray(lo, np.float32), (self.B, nb))
+        hi = np.broadcast_to(np.asarray(hi, np.float32), (self.B, nb))
+        self.write(F_BODYMASS_RANGE, np.concatenate([lo, hi], axis=1))
+
     def field_ptr(self, field):
         p, pitch, width = C.c_void_p(), C.c_size_t(), C.c_size_t()
         _chk(lib().myo_batch_field(self.h, field, C.byref(p), C.byref(pitch), C.byref(width)))
         return p.value, pitch.value, width.value
 
+    def _width(self, field):
+        # the body-mass fields have a known width; asking for their device pointer would start the override
+        if field == F_BODYMASS:
+            return self.model.dims.nbody
+        if field == F_BODYMASS_RANGE:
+            return 2 * self.model.dims.nbody
+        return self.field_ptr(field)[2]
+
     def read(self, field) -> np.ndarray:
-        _, _, width = self.field_ptr(field)
+        width = self._width(field)
         out = np.empty((self.B, width), np.int32 if field in INT_FIELDS else np.float32)
         _chk(lib().myo_batch_read(self.h, field, out.ctypes.data, out.nbytes))
         return out
 
     def write(self, field, arr):
-        _, _, width = self.field_ptr(field)
+        width = self._width(field)
         a = np.ascontiguousarray(arr, np.int32 if field in INT_FIELDS else np.float32).reshape(self.B, width)
         _chk(lib().myo_batch_write(self.h, field, a.ctypes.data, a.nbytes))
 

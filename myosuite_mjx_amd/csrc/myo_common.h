@@ -129,6 +129,11 @@ struct DevBatch {
   float* hfield;           // [B][nrow * ncol] height-field elevation per env (terrain models; NULL otherwise)
   float* gsize;            // [B][4] per-env size (3) + bounding radius of ONE collision geom (ObjHoldRandomEnvV0 re-draws the object's size); NULL: none
   int gsize_cg;            // its collision-geom index
+  // per-env body masses (MYO_F_BODYMASS), run-time-sizes hand / 36-dof instantiations only; NULL: off (the model's link tables are used)
+  float* bmass;            // [B][nbody] mass per body
+  float* bmass_range;      // [B][2 * nbody] lo | hi: a fresh mass ~ U(lo, hi) at every reset of an env for the bodies with hi > lo
+  float* linkc;            // [B][nl][10] link mass, COM (3, link frame), inertia about the COM (xx yy zz xy xz yz), recomposed per launch
+  int nbody;
   // overflow of the LDS contact table (wave kernel): contacts NC .. NC + NCX - 1 of an env keep their point / normal / jacobian rows in
   // HBM (L2-resident in practice; touched by ~0.4 % of myoHandPoseRandom reset poses), candidates beyond NCAND their pair ids
   float* ovf;              // [B][NCX][ovf_row] floats: dist, pos[3], normal[3], pair id, cJ[3 * KC], dof ids (byte-packed)

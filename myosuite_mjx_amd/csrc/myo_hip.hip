@@ -59,6 +59,11 @@ struct myo_model {
   std::vector<float> body_lpos, body_lquat, mass;   // mass = [total, static bodies' mass-weighted COM xyz]
   float* d_qpos0 = nullptr;
   int env_lds_bytes = 0;
+  // per-env body masses (MYO_F_BODYMASS): the compiled body_mass and, per link, its member bodies (CSR) with their COM (3), inertia
+  // about the COM (6) in the link frame and compiled mass -- the per-body constants of lowering.py's link recomposition (link_compose_kernel)
+  std::vector<float> body_mass0;
+  const int *d_lm_adr = nullptr, *d_lm_body = nullptr;
+  const double* d_lm_tab = nullptr;
 };
 
 struct myo_batch {
@@ -82,6 +87,7 @@ struct myo_batch {
   int* d_sched = nullptr;       // substep scheduler: 8 queues x (4 control words + ring)
   int sched_stride = 0;
   int balance = 1;
+  bool bm_on = false;            // per-env body-mass override started (DevBatch.bmass / bmass_range / linkc allocated)
   std::vector<hipEvent_t> kev;   // per-launch event pairs around the step kernel (bench only)
   int kev_pending = 0;           // pairs recorded by asynchronous bench calls and not collected yet
   float last_kernel_ms = 0.f;
@@ -455,6 +461,43 @@ int myo_model_load(const void* blobv, size_t nbytes, int device, myo_model** out
     if (!m->wave_ok) { myo_model_free(m); return fail(MYO_E_UNSUPPORTED, "model working set exceeds 160 KB of LDS per workgroup"); }
     m->generic_ok = false;
   }
+  if (m->wave_ok && !m->body_link.empty()) {   // member tables of the per-env body-mass override (lowering.py's link recomposition, per body)
+    auto f64 = [&](const char* n) { std::vector<double> v; const BlobRec* r = blob_find(blob, n); if (r && r->dtype == 0) { v.resize(r->nbytes / 8); memcpy(v.data(), blob + r->offset, r->nbytes); } return v; };
+    const std::vector<double> bmass = f64("body_mass"), ipos = f64("body_ipos"), iquat = f64("body_iquat"), inert = f64("body_inertia"),
+                              lpos = f64("hip_body_lpos"), lquat = f64("hip_body_lquat");
+    const int nb = (int)m->body_link.size();
+    if ((int)bmass.size() == nb && (int)ipos.size() == 3 * nb && (int)iquat.size() == 4 * nb && (int)inert.size() == 3 * nb &&
+        (int)lpos.size() == 3 * nb && (int)lquat.size() == 4 * nb) {
+      auto qmat = [](const double* q, double* R) {
+        const double w = q[0], x = q[1], y = q[2], z = q[3];
+        R[0] = w * w + x * x - y * y - z * z; R[1] = 2 * (x * y - w * z); R[2] = 2 * (x * z + w * y);
+        R[3] = 2 * (x * y + w * z); R[4] = w * w - x * x + y * y - z * z; R[5] = 2 * (y * z - w * x);
+        R[6] = 2 * (x * z - w * y); R[7] = 2 * (y * z + w * x); R[8] = w * w - x * x - y * y + z * z;
+      };
+      std::vector<int> adr(d.nl + 1, 0), body;
+      std::vector<double> tab;
+      for (int l = 0; l < d.nl; l++) {
+        adr[l] = (int)body.size();
+        for (int b = 1; b < nb; b++) {
+          if (m->body_link[b] != l) continue;
+          double Rl[9], Rq[9], Ri[9], c[3], I[9];
+          qmat(&lquat[4 * b], Rl); qmat(&iquat[4 * b], Rq);
+          for (int i = 0; i < 3; i++) {
+            c[i] = lpos[3 * b + i];
+            for (int j = 0; j < 3; j++) { c[i] += Rl[3 * i + j] * ipos[3 * b + j]; Ri[3 * i + j] = Rl[3 * i] * Rq[j] + Rl[3 * i + 1] * Rq[3 + j] + Rl[3 * i + 2] * Rq[6 + j]; }
+          }
+          for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) I[3 * i + j] = Ri[3 * i] * inert[3 * b] * Ri[3 * j] + Ri[3 * i + 1] * inert[3 * b + 1] * Ri[3 * j + 1] + Ri[3 * i + 2] * inert[3 * b + 2] * Ri[3 * j + 2];
+          body.push_back(b);
+          for (double v : {c[0], c[1], c[2], I[0], I[4], I[8], I[1], I[2], I[5], bmass[b]}) tab.push_back(v);
+        }
+      }
+      adr[d.nl] = (int)body.size();
+      int rc2;
+      if ((rc2 = upload<int>(m, adr, &m->d_lm_adr)) || (rc2 = upload<int>(m, body, &m->d_lm_body)) || (rc2 = upload<double>(m, tab, &m->d_lm_tab))) { myo_model_free(m); return rc2; }
+      m->body_mass0.assign(bmass.begin(), bmass.end());
+    }
+  }
   *out = m;
   return MYO_OK;
 }
@@ -557,6 +600,7 @@ int myo_batch_size(const myo_batch* b) { return b ? b->db.B : 0; }
 
 int myo_batch_configure(myo_batch* b, const myo_task_config* c) {
   if (!b || !c) return fail(MYO_E_ARG, "myo_batch_configure: null");
+  if (b->bm_on && c->task == MYO_TASK_STAND) return fail(MYO_E_UNSUPPORTED, "per-env body masses: the stand task uses model-wide mass totals");
   const DevModel& dm = b->model->dm;
   TaskDev& T = b->task;
   int nv = dm.nv, nu = dm.nu;
@@ -624,6 +668,7 @@ int myo_batch_set_geom_override(myo_batch* b, int geom_id, const float* lo, cons
 
 int myo_batch_configure_walk(myo_batch* b, const myo_walk_config* c) {
   if (!b || !c) return fail(MYO_E_ARG, "myo_batch_configure_walk: null");
+  if (b->bm_on) return fail(MYO_E_UNSUPPORTED, "per-env body masses: the walk task uses model-wide mass totals");
   const myo_model* m = b->model;
   const DevModel& dm = m->dm;
   const int nq = m->nq, nv = dm.nv, nu = dm.nu, nb = (int)m->body_link.size();
@@ -732,6 +777,39 @@ int myo_batch_configure_track(myo_batch* b, const myo_track_config* c) {
   return MYO_OK;
 }
 
+// per-env body-mass override (MYO_F_BODYMASS / MYO_F_BODYMASS_RANGE): the refusals, shared by its start and the launches after it
+static int bm_check(const myo_batch* b) {
+  const myo_model* m = b->model;
+  if (m->rk4) return fail(MYO_E_UNSUPPORTED, "per-env body masses: RK4 models are not supported");
+  if (m->trk) return fail(MYO_E_UNSUPPORTED, "per-env body masses: models of the TrackEnv class are not supported");
+  if (m->dw.hf.on) return fail(MYO_E_UNSUPPORTED, "per-env body masses: height-field models are not supported");
+  if (!m->wave_ok || g_lanes != 64) return fail(MYO_E_UNSUPPORTED, "per-env body masses: wave-per-env kernel only (lanes = 64)");
+  const int t = b->task.task;
+  if (t == MYO_TASK_WALK || t == MYO_TASK_STAND || t == MYO_TASK_TRACK)
+    return fail(MYO_E_UNSUPPORTED, "per-env body masses: the walk / stand / track tasks use model-wide mass totals");
+  if (m->body_mass0.empty() || !m->d_lm_adr) return fail(MYO_E_UNSUPPORTED, "per-env body masses: the model blob lacks the body tables");
+  return MYO_OK;
+}
+
+static int bm_start(myo_batch* b) {
+  if (b->bm_on) return MYO_OK;
+  int rc = bm_check(b);
+  if (rc) return rc;
+  const myo_model* m = b->model;
+  DevBatch& d = b->db;
+  const int nb = (int)m->body_mass0.size();
+  float *bm = nullptr, *br = nullptr, *lc = nullptr;
+  if ((rc = balloc(b, (void**)&bm, (size_t)d.B * nb * 4)) || (rc = balloc(b, (void**)&br, (size_t)d.B * 2 * nb * 4)) ||
+      (rc = balloc(b, (void**)&lc, (size_t)d.B * m->dm.nl * 10 * 4))) return rc;
+  std::vector<float> v((size_t)d.B * nb);
+  for (int e = 0; e < d.B; e++) memcpy(&v[(size_t)e * nb], m->body_mass0.data(), nb * 4);
+  HIPCHK(hipSetDevice(m->device));
+  HIPCHK(hipMemcpy(bm, v.data(), v.size() * 4, hipMemcpyHostToDevice));
+  d.bmass = bm; d.bmass_range = br; d.linkc = lc; d.nbody = nb;
+  b->bm_on = true;
+  return MYO_OK;
+}
+
 static int field_info(myo_batch* b, int f, void** p, size_t* pitch, size_t* width) {
   const DevModel& dm = b->model->dm;
   DevBatch& d = b->db;
@@ -769,6 +847,13 @@ static int field_info(myo_batch* b, int f, void** p, size_t* pitch, size_t* widt
       if (!b->d_metrics) return fail(MYO_E_ARG, "MYO_F_METRICS: the track task is not configured (myo_batch_configure_track)");
       *p = b->d_metrics; *pitch = *width = 4; break;
     case MYO_F_SITEXPOS: *p = d.sitexpos; *pitch = *width = b->task.ntip > 0 ? 3 * b->task.ntip : 1; break;
+    case MYO_F_BODYMASS:
+    case MYO_F_BODYMASS_RANGE: {   // (callers start the override first; before that the pointer is NULL)
+      const size_t nb = b->model->body_mass0.size();
+      *p = f == MYO_F_BODYMASS ? (void*)d.bmass : (void*)d.bmass_range;
+      *pitch = *width = f == MYO_F_BODYMASS ? nb : 2 * nb;
+      break;
+    }
     default: return fail(MYO_E_ARG, "unknown field");
   }
   return MYO_OK;
@@ -776,6 +861,7 @@ static int field_info(myo_batch* b, int f, void** p, size_t* pitch, size_t* widt
 
 int myo_batch_field(myo_batch* b, int field, void** dev_ptr, size_t* pitch, size_t* width) {
   if (!b || !dev_ptr || !pitch || !width) return fail(MYO_E_ARG, "myo_batch_field: null");
+  if (field == MYO_F_BODYMASS || field == MYO_F_BODYMASS_RANGE) { int rc = bm_start(b); if (rc) return rc; }
   return field_info(b, field, dev_ptr, pitch, width);
 }
 
@@ -785,6 +871,16 @@ int myo_batch_read(myo_batch* b, int field, void* host, size_t nbytes) {
   int rc = field_info(b, field, &p, &pitch, &width);
   if (rc) return rc;
   if (nbytes != (size_t)b->db.B * width * 4) return fail(MYO_E_ARG, "myo_batch_read: size mismatch");
+  if ((field == MYO_F_BODYMASS || field == MYO_F_BODYMASS_RANGE) && !b->bm_on) {   // not started: the model's masses, empty ranges
+    const std::vector<float>& m0 = b->model->body_mass0;
+    if (m0.empty()) return fail(MYO_E_UNSUPPORTED, "per-env body masses: the model blob lacks the body tables");
+    float* h = (float*)host;
+    for (int e = 0; e < b->db.B; e++) {
+      if (field == MYO_F_BODYMASS) memcpy(h + (size_t)e * width, m0.data(), width * 4);
+      else memset(h + (size_t)e * width, 0, width * 4);
+    }
+    return MYO_OK;
+  }
   HIPCHK(hipSetDevice(b->model->device));
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(host, p, nbytes, hipMemcpyDeviceToHost));
@@ -797,6 +893,21 @@ int myo_batch_write(myo_batch* b, int field, const void* host, size_t nbytes) {
   int rc = field_info(b, field, &p, &pitch, &width);
   if (rc) return rc;
   if (nbytes != (size_t)b->db.B * width * 4) return fail(MYO_E_ARG, "myo_batch_write: size mismatch");
+  if (field == MYO_F_BODYMASS || field == MYO_F_BODYMASS_RANGE) {
+    if (b->model->body_mass0.empty()) return fail(MYO_E_UNSUPPORTED, "per-env body masses: the model blob lacks the body tables");
+    const float* h = (const float*)host;
+    const size_t nb = b->model->body_mass0.size();
+    for (int e = 0; e < b->db.B; e++)
+      for (size_t i = 0; i < nb; i++) {
+        if (field == MYO_F_BODYMASS) { if (!(h[e * nb + i] >= 0.f)) return fail(MYO_E_ARG, "MYO_F_BODYMASS: masses must be >= 0"); }
+        else {
+          const float lo = h[2 * e * nb + i], hi = h[2 * e * nb + nb + i];
+          if (!(lo >= 0.f) || !(hi >= lo)) return fail(MYO_E_ARG, "MYO_F_BODYMASS_RANGE: need 0 <= lo <= hi");
+        }
+      }
+    if ((rc = bm_start(b))) return rc;
+    if ((rc = field_info(b, field, &p, &pitch, &width))) return rc;
+  }
   HIPCHK(hipSetDevice(b->model->device));
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(p, host, nbytes, hipMemcpyHostToDevice));
@@ -876,6 +987,16 @@ static int launch_step(myo_batch* b, const float* action, int actmap, int nsub, 
 #endif
   if (!(G == 64 && m->wave_ok) && !m->generic_ok)
     return fail(MYO_E_UNSUPPORTED, "this model (tendon limits / free joint / equalities / plane contacts) needs the wave-per-env kernel (lanes = 64)");
+  // per-env body masses: link tables of every env recomposed once per launch; the step runs on the run-time-sizes instantiation of the
+  // model's class (the only ones that read them)
+  const bool bm = b->bm_on;
+  if (bm) {
+    int rc = bm_check(b);
+    if (rc) return rc;
+    const int n = b->db.B * m->dm.nl;
+    hipLaunchKernelGGL(link_compose_kernel, dim3((n + 255) / 256), dim3(256), 0, s, b->db, m->dm.nl, m->d_lm_adr, m->d_lm_body, m->d_lm_tab);
+  }
+  const bool hand_sizes = m->hand_sizes && !bm, leg_sizes = m->leg_sizes && !bm;
   if (G == 64 && m->wave_ok) {
     // kernel attributes are per device: one flag per device ordinal (a process that opens models on two GPUs)
     static std::mutex attr_mu;
@@ -906,7 +1027,7 @@ static int launch_step(myo_batch* b, const float* action, int actmap, int nsub, 
     const int n_cu = m->n_cu > 0 ? m->n_cu : 256;                                                        // per model = per device
     const int resident = n_cu * (m->wave_cfg == 0 ? 16 : (m->wave_cfg == 1 ? 8 : std::max(1, (160 * 1024) / std::max(1, m->env_lds_bytes_w))));
     const bool sched_ok = !kflags && Bn >= 64 && Bn <= SCHED_ENV_MASK && nsub + (wk ? 1 : 0) <= 15 && nsub > 0;
-    const bool sched = sched_ok && m->wave_cfg == 1 && !m->rk4 && !(m->dw.hf.on && !m->terrain_sizes) && (sched_mode == 1 || (sched_mode == -1 && m->wave_cfg == 1 && Bn >= 2 * resident));
+    const bool sched = sched_ok && !bm && m->wave_cfg == 1 && !m->rk4 && !(m->dw.hf.on && !m->terrain_sizes) && (sched_mode == 1 || (sched_mode == -1 && m->wave_cfg == 1 && Bn >= 2 * resident));
     if (b->balance && Bn >= 1024 && Bn % 4 == 0 && !kflags && !sched) {
       static const int prio_mode = [] { const char* e = getenv("MYO_PRIO"); return e ? atoi(e) : 2; }();
       hipLaunchKernelGGL(balance_kernel, dim3(1), dim3(1024), 0, s, (const int*)b->db.diag, Bn, b->d_order, Bn / 4, prio_mode);
@@ -919,9 +1040,9 @@ static int launch_step(myo_batch* b, const float* action, int actmap, int nsub, 
     if (!kflags)   // instantiation chosen below, as rocprofv3 prints it (bench.py reports it next to the kernel time)
       b->last_kernel = m->rk4 ? (m->wave_cfg == 0 ? "step_kernel_w<24,8,32,1,3,false,0,false,false,true>" : "step_kernel_w<36,20,32,2,2,false,0,false,false,true>") :
                        m->wave_cfg == 2 ? "step_kernel_w<36,20,32,2,2,false,0,false,true>" :
-                       sched ? (m->dw.hf.on ? "step_kernel_w<36,20,32,2,2,true,3,true>" : (m->leg_sizes ? "step_kernel_w<36,20,32,2,2,true,2,false>" : "step_kernel_w<36,20,32,2,2,true,0,false>"))
-                             : (m->wave_cfg == 0 ? (m->hand_sizes ? "step_kernel_w<24,8,32,1,4,false,1,false>" : "step_kernel_w<24,8,32,1,3,false,0,false>")
-                                                 : (m->dw.hf.on ? (m->terrain_sizes ? "step_kernel_w<36,20,32,2,2,false,3,true>" : "step_kernel_w<36,20,32,2,2,false,0,true>") : (m->leg_sizes ? "step_kernel_w<36,20,32,2,2,false,2,false>" : "step_kernel_w<36,20,32,2,2,false,0,false>")));
+                       sched ? (m->dw.hf.on ? "step_kernel_w<36,20,32,2,2,true,3,true>" : (leg_sizes ? "step_kernel_w<36,20,32,2,2,true,2,false>" : "step_kernel_w<36,20,32,2,2,true,0,false>"))
+                             : (m->wave_cfg == 0 ? (hand_sizes ? "step_kernel_w<24,8,32,1,4,false,1,false>" : "step_kernel_w<24,8,32,1,3,false,0,false>")
+                                                 : (m->dw.hf.on ? (m->terrain_sizes ? "step_kernel_w<36,20,32,2,2,false,3,true>" : "step_kernel_w<36,20,32,2,2,false,0,true>") : (leg_sizes ? "step_kernel_w<36,20,32,2,2,false,2,false>" : "step_kernel_w<36,20,32,2,2,false,0,false>")));
     if (sched) {
       hipLaunchKernelGGL(sched_init_kernel, dim3(1), dim3(1024), 0, s, (const int*)b->db.diag, Bn, S);
       int grid = Bn < resident ? Bn : resident;    // persistent waves: no more workgroups than the chip holds at once
@@ -930,7 +1051,7 @@ static int launch_step(myo_batch* b, const float* action, int actmap, int nsub, 
       if (m->dw.hf.on)
         hipLaunchKernelGGL((step_kernel_w<36, 20, 32, 2, 2, true, 3, true>), dim3(grid), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm,
                            (const DevModelW*)m->d_dw, b->db, action, actmap, nsub, st, (const int*)nullptr, wk, 0, S);
-      else if (m->leg_sizes)
+      else if (leg_sizes)
         hipLaunchKernelGGL((step_kernel_w<36, 20, 32, 2, 2, true, 2>), dim3(grid), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm,
                            (const DevModelW*)m->d_dw, b->db, action, actmap, nsub, st, (const int*)nullptr, wk, 0, S);
       else
@@ -945,7 +1066,7 @@ static int launch_step(myo_batch* b, const float* action, int actmap, int nsub, 
     else if (m->wave_cfg == 2)   // TrackEnv model class
       hipLaunchKernelGGL((step_kernel_w<36, 20, 32, 2, 2, false, 0, false, true>), dim3(Bn), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm,
                          (const DevModelW*)m->d_dw, b->db, action, actmap, nsub, st, order, wk, kflags, S);
-    else if (m->wave_cfg == 0 && m->hand_sizes)
+    else if (m->wave_cfg == 0 && hand_sizes)
       hipLaunchKernelGGL((step_kernel_w<24, 8, 32, 1, 4, false, 1>), dim3(Bn), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm,
                          (const DevModelW*)m->d_dw, b->db, action, actmap, nsub, st, order, (const DevWalk*)nullptr, 0, S);
     else if (m->wave_cfg == 0)
@@ -957,7 +1078,7 @@ static int launch_step(myo_batch* b, const float* action, int actmap, int nsub, 
     else if (m->dw.hf.on)
       hipLaunchKernelGGL((step_kernel_w<36, 20, 32, 2, 2, false, 0, true>), dim3(Bn), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm,
                          (const DevModelW*)m->d_dw, b->db, action, actmap, nsub, st, order, wk, kflags, S);
-    else if (m->leg_sizes)
+    else if (leg_sizes)
       hipLaunchKernelGGL((step_kernel_w<36, 20, 32, 2, 2, false, 2>), dim3(Bn), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm,
                          (const DevModelW*)m->d_dw, b->db, action, actmap, nsub, st, order, wk, kflags, S);
     else

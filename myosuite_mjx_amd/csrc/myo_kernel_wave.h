@@ -856,18 +856,29 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
     for (int u = 0; u < BKG; u++) { const int l = (u * 64 + lane) >> 4; desc_m[u] = l < nl_ ? ld_mask(W.link_desc, l) : 0ull; }
     const int my_link = M.dof_link[lane < nv ? lane : 0];
     const float my_arm = M.dof_armature[lane < nv ? lane : 0], my_damp = M.dof_damping[lane < nv ? lane : 0];
+    // per-env body masses (DevBatch.linkc, MYO_F_BODYMASS): the run-time-sizes hand / 36-dof instantiations read the link mass, COM and
+    // inertia that link_compose_kernel recomposed for this env at the start of the launch; every other instantiation keeps the model's
+    constexpr bool BMO = !SCHED && SPEC == 0 && !HF && !TRK && !RK4;
     if (lane < nl_) {
       int l = lane;
       const float* R = E + Y.lmat + 9 * l;
       const float* I = M.link_inertia + 6 * l;
+      const float* lcom = M.link_com + 3 * l;
+      const float* lmass = M.link_mass + l;
+      if constexpr (BMO) {
+        if (Bt.linkc) {   // [nl][10] of this env: mass, COM (3), inertia (xx yy zz xy xz yz) in the link frame
+          const float* L = Bt.linkc + ((size_t)env * nl_ + l) * 10;
+          lmass = L; lcom = L + 1; I = L + 4;
+        }
+      }
       float Il[9] = {I[0], I[3], I[4], I[3], I[1], I[5], I[4], I[5], I[2]}, T[9], Iw[9], com[3];
       matmul3(T, R, Il);
 #pragma unroll
       for (int i = 0; i < 3; i++)
 #pragma unroll
         for (int j = 0; j < 3; j++) Iw[3 * i + j] = T[3 * i] * R[3 * j] + T[3 * i + 1] * R[3 * j + 1] + T[3 * i + 2] * R[3 * j + 2];
-      matvec(com, R, M.link_com + 3 * l);
-      float mass = M.link_mass[l];
+      matvec(com, R, lcom);
+      float mass = *lmass;
       float dif[3] = {E[Y.lpos + 3 * l] + com[0] - c0[0], E[Y.lpos + 3 * l + 1] + com[1] - c0[1], E[Y.lpos + 3 * l + 2] + com[2] - c0[2]};
       float ci[10];
       ci[0] = Iw[0] + mass * (dif[1] * dif[1] + dif[2] * dif[2]);

@@ -165,6 +165,14 @@ __device__ __forceinline__ bool reset_body(const DevBatch& Bt, const TaskDev& T,
     float* G = Bt.gsize + 4 * (size_t)e;
     G[0] = sz[0]; G[1] = sz[1]; G[2] = sz[2]; G[3] = rb;
   }
+  if (Bt.bmass_range) {
+    // PoseEnvV0.reset (pose_v0.py:163-176, weight_bodyname / weight_range): a fresh mass per episode for every body whose range is not empty
+    const float* lo = Bt.bmass_range + (size_t)e * 2 * Bt.nbody;
+    for (int i = lane; i < Bt.nbody; i += 64) {
+      const float l = lo[i], h = lo[Bt.nbody + i];
+      if (h > l) Bt.bmass[(size_t)e * Bt.nbody + i] = l + (h - l) * u01(seed ^ 0x3C6EF372FE94F82Bull, ge * 4096 + i, 9);
+    }
+  }
   if (T.terrain && Bt.hfield) {
     // TerrainEnvV0.reset (walk_v0.py:563-622): a fresh 100 x 100 elevation grid per episode (in units of the height field's z scale).
     // Distribution parity only for the random draws, as for every reset.
@@ -200,6 +208,45 @@ __global__ void __launch_bounds__(64) reset_kernel(DevBatch Bt, TaskDev T, int n
                                                   int env_offset, int auto_max) {
   if ((int)blockIdx.x >= Bt.B) return;
   reset_body(Bt, T, nq, nv, nu, qpos0, mask, seed, env_offset, auto_max, blockIdx.x, threadIdx.x);
+}
+
+// per-env body masses (MYO_F_BODYMASS): link mass, COM and inertia about the COM of every link of every env from its bodies' masses, the
+// recomposition lowering.py does at compile time (parallel-axis theorem over the bodies welded into the link).  Member m of link l (CSR
+// adr[l] .. adr[l+1]) is body body[m] with its COM (3), its inertia (6, xx yy zz xy xz yz, about its COM) in the link frame and its compiled
+// float64 mass, tab[10 m ..].  A body whose float32 entry still equals its compiled mass rounded to float32 counts with the float64 mass, so
+// that unchanged bodies contribute exactly what lowering summed (an unchanged link gets the model's link tables to the last bit).
+// One thread per (env, link), float64 arithmetic; run once per step launch, before the step kernel
+__global__ void __launch_bounds__(256) link_compose_kernel(DevBatch Bt, int nl, const int* __restrict__ adr, const int* __restrict__ body,
+                                                          const double* __restrict__ tab) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= Bt.B * nl) return;
+  const int e = t / nl, l = t - e * nl;
+  const float* bm = Bt.bmass + (size_t)e * Bt.nbody;
+  double mass = 0, mc[3] = {0, 0, 0};
+  auto mass_of = [&](int k) { const float f = bm[body[k]]; const double m0 = tab[10 * k + 9]; return f == (float)m0 ? m0 : (double)f; };
+  for (int k = adr[l]; k < adr[l + 1]; k++) {
+    const double mb = mass_of(k);
+    mass += mb;
+    for (int j = 0; j < 3; j++) mc[j] += mb * tab[10 * k + j];
+  }
+  const double inv = mass > 0 ? 1.0 / mass : 0.0;
+  const double com[3] = {mc[0] * inv, mc[1] * inv, mc[2] * inv};
+  double I[6] = {0, 0, 0, 0, 0, 0};
+  for (int k = adr[l]; k < adr[l + 1]; k++) {
+    const double mb = mass_of(k);
+    const double* c = tab + 10 * k;
+    const double d[3] = {c[0] - com[0], c[1] - com[1], c[2] - com[2]}, dd = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+    I[0] += c[3] + mb * (dd - d[0] * d[0]);
+    I[1] += c[4] + mb * (dd - d[1] * d[1]);
+    I[2] += c[5] + mb * (dd - d[2] * d[2]);
+    I[3] += c[6] - mb * d[0] * d[1];
+    I[4] += c[7] - mb * d[0] * d[2];
+    I[5] += c[8] - mb * d[1] * d[2];
+  }
+  float* o = Bt.linkc + (size_t)t * 10;
+  o[0] = (float)mass;
+  for (int j = 0; j < 3; j++) o[1 + j] = (float)com[j];
+  for (int j = 0; j < 6; j++) o[4 + j] = (float)I[j];
 }
 
 // observation + reward (pose_v0.py:98-138, obs_vec_dict.py:86-98); one 64-lane workgroup per env, rows written coalesced

@@ -96,7 +96,8 @@ REGISTRY["motorFingerPoseFixed-v0"] = dict(_pose_spec([0, 0, 0.75, 0.75], [0, 0,
 REGISTRY["motorFingerPoseRandom-v0"] = dict(_pose_spec([-0.2, -0.4, 0.1, 0.1], [0.2, 1.0, 1.0, 1.0], "init", "generate", 0.35, "motorfinger_v0"),
                                             max_episode_steps=200, frame_skip=5)
 # myoElbowPose1D6MExoFixed-v0 (envs/myo/myobase/__init__.py:140-160): the elbow with an exoskeleton motor on the joint (actuator 0) and
-# act_reg weight 5.  (ExoRandom additionally re-draws a body mass per episode -- a per-env model edit, not offered.)
+# act_reg weight 5.  (ExoRandom = this id with the reference's kwargs weight_bodyname="carry_weight", weight_range=(0.1, 2.0) and
+# target_jnt_range={"r_elbow_flex": (0, 2.27)}: a per-env body mass re-drawn at every reset, see BatchedMyoEnv.body_mass.)
 REGISTRY["myoElbowPose1D6MExoFixed-v0"] = dict(_pose_spec([2.0], [2.0], "random", "generate", 0.175, "myoelbow_1dof6muscles_1dofexo"),
                                                weights=dict(pose=1.0, bonus=4.0, act_reg=5.0, penalty=50.0))
 # myoHandObjHoldFixed-v0 (envs/myo/myobase/__init__.py:596-604, obj_hold_v0.py:13-118): MyoHand palm up + a free ellipsoid object; goal = the
@@ -203,7 +204,8 @@ class BatchedMyoEnv:
     """
 
     # env kwargs of the reference that gym.make forwards to the env class and that are honoured here (others raise)
-    ENV_KWARGS = ("reset_type", "fatigue_reset_random", "fatigue_reset_vec")
+    ENV_KWARGS = ("reset_type", "fatigue_reset_random", "fatigue_reset_vec", "weight_bodyname", "weight_range", "target_jnt_range")
+    POSE_KWARGS = ("weight_bodyname", "weight_range", "target_jnt_range")   # PoseEnvV0 kwargs (pose_v0.py:56-75): pose tasks only
 
     def __init__(self, env_id, num_envs=1, device=0, seed=0, env_offset=0, autoreset=True, as_torch=True, **env_kwargs):
         if env_id in UNSUPPORTED:
@@ -213,8 +215,8 @@ class BatchedMyoEnv:
         self.id = env_id
         self.spec = spec = dict(REGISTRY[env_id])
         for k, v in env_kwargs.items():
-            if k not in self.ENV_KWARGS:
-                raise TypeError(f"{env_id}: unsupported env kwarg {k!r} (supported: {self.ENV_KWARGS})")
+            if k not in self.ENV_KWARGS or (k in self.POSE_KWARGS and spec.get("task") != "pose"):
+                raise TypeError(f"{env_id}: unsupported env kwarg {k!r} (supported: {self.ENV_KWARGS}; {self.POSE_KWARGS} for pose tasks only)")
             spec[k] = v
         self.num_envs = int(num_envs)
         self.device = device
@@ -233,6 +235,8 @@ class BatchedMyoEnv:
         self.dt = m.timestep * self.frame_skip                        # env_base.py:616-617
         self.max_episode_steps = spec["max_episode_steps"]
         w = spec["weights"]
+        if spec.get("target_jnt_range") is not None:   # pose_v0.py:67-75: {joint name: (lo, hi)} replaces the registered target range
+            spec["target_lo"], spec["target_hi"] = self._target_jnt_range(m, spec)
         if spec["task"] == "pose":
             self.batch.configure(task=capi.TASK_POSE, frame_skip=self.frame_skip,
                                  reset_random=spec["reset_type"] == "random", target_generate=spec["target_type"] == "generate",
@@ -240,6 +244,10 @@ class BatchedMyoEnv:
                                  pose_thd=spec["pose_thd"], far_th=4 * np.pi / 2,
                                  w_pose=w["pose"], w_bonus=w["bonus"], w_act_reg=w["act_reg"], w_penalty=w["penalty"])
             self.obs_dim = 3 * m.nq + m.n_muscle
+            if spec.get("weight_bodyname") is not None:                # pose_v0.py:163-176: body mass ~ U(weight_range) at every reset
+                if spec.get("weight_range") is None:
+                    raise ValueError(f"{env_id}: weight_bodyname needs weight_range")
+                self.set_body_mass_range(spec["weight_bodyname"], *spec["weight_range"])
         elif spec["task"] == "walk":
             key_qpos = np.asarray(m.key_qpos).reshape(-1, m.nq)
             key_qvel = np.asarray(m.key_qvel).reshape(-1, m.nv)
@@ -337,6 +345,43 @@ class BatchedMyoEnv:
             import torch
             self._torch = torch
             self._action_buf = torch.empty((self.num_envs, m.nu), dtype=torch.float32, device=f"cuda:{device}")
+
+    @staticmethod
+    def _target_jnt_range(m, spec):
+        n = len(spec["target_lo"])
+        targeted = [m.names["joint"][j] for j in range(m.njnt) if int(m.jnt_qposadr[j]) < n]
+        rng = dict(spec["target_jnt_range"])
+        if sorted(rng) != sorted(targeted):
+            raise ValueError(f"target_jnt_range must name exactly the joints {targeted} (got {sorted(rng)})")
+        lo, hi = np.array(spec["target_lo"], float), np.array(spec["target_hi"], float)
+        for name, (a, b) in rng.items():
+            q = int(m.jnt_qposadr[m.name2id("joint", name)])
+            lo[q], hi[q] = float(a), float(b)
+        return lo, hi
+
+    # -- per-env body masses (MYO_F_BODYMASS) -----------------------------------------------------------------
+    @property
+    def body_mass(self):
+        """[num_envs, nbody] mass of every body in every env: a torch view of the library's buffer (no copy; writes take effect at the
+        next step) -- the batched `sim.model.body_mass[bid] = ...`.  First use starts the per-env body-mass override, which steps the model
+        on the run-time-sizes kernel of its class.  With as_torch=False: a numpy copy (assign the property to write it back)."""
+        return self.view(capi.F_BODYMASS)
+
+    @body_mass.setter
+    def body_mass(self, value):
+        if self.as_torch:
+            self.view(capi.F_BODYMASS).copy_(self._torch.as_tensor(value, dtype=self._torch.float32).expand(self.num_envs, -1))
+        else:
+            self.batch.write(capi.F_BODYMASS, np.broadcast_to(np.asarray(value, np.float32), (self.num_envs, self.mjmodel.nbody)))
+
+    def set_body_mass_range(self, body, lo, hi):
+        """Re-draw the mass of `body` (id or name) ~ U(lo, hi) at every reset of every env (PoseEnvV0 weight_bodyname / weight_range);
+        lo == hi: no re-draw.  Ranges of the other bodies are left as they are."""
+        b = self.mjmodel.body_name2id(body) if isinstance(body, str) else int(body)
+        nb = self.mjmodel.nbody
+        r = self.batch.read(capi.F_BODYMASS_RANGE)
+        r[:, b], r[:, nb + b] = float(lo), float(hi)
+        self.batch.write(capi.F_BODYMASS_RANGE, r)
 
     # -- zero-copy views ---------------------------------------------------------------------------------
     def view(self, field):

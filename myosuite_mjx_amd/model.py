@@ -91,6 +91,40 @@ class Model:
             act[pos, 2] = gp[pos, 2]
         return Model(arrays, self.names, self.source)
 
+    def with_body_mass(self, body, mass) -> "Model":
+        """Copy of the model with `body_mass[body] = mass` for every env (`body`: id or name), as `model.body_mass[bid] = ...` edits a
+        compiled MuJoCo model (PoseEnvV0.reset, envs/myo/myobase/pose_v0.py:163-176).  The mass, COM and inertia about the COM of the
+        body's link (the bodies welded together, lowering.py) are recomposed in float64 with lowering's formulas; nothing else changes
+        (body_inertia, acc0, invweights and lengthranges keep their values, as without mj_setConst)."""
+        from .lowering import _rel_transforms
+        from .mjcf import quat2mat
+        b = self.body_name2id(body) if isinstance(body, str) else int(body)
+        if not 0 <= b < self.nbody:
+            raise ValueError(f"no body {body!r}")
+        if not mass >= 0:
+            raise ValueError("body mass must be >= 0")
+        arrays = {k: np.array(v, copy=True) for k, v in self.arrays.items()}
+        arrays["body_mass"][b] = float(mass)
+        out = Model(arrays, self.names, self.source)
+        link = int(arrays["hip_body_link"][b]) if "hip_body_link" in arrays else -1
+        if link < 0:                     # welded to the world (or no HIP tables): no link to recompose
+            return out
+        _, Rrel, prel = _rel_transforms(out)
+        members = [k for k in range(1, self.nbody) if int(arrays["hip_body_link"][k]) == link]
+        bm, ipos, iquat, inertia = arrays["body_mass"], arrays["body_ipos"], arrays["body_iquat"], arrays["body_inertia"]
+        tot = sum(bm[k] for k in members)
+        com = sum(bm[k] * (prel[k] + Rrel[k] @ ipos[k]) for k in members) / tot
+        I = np.zeros((3, 3))
+        for k in members:
+            Ri = Rrel[k] @ quat2mat(iquat[k])
+            d = prel[k] + Rrel[k] @ ipos[k] - com
+            I += Ri @ np.diag(inertia[k]) @ Ri.T + bm[k] * (d @ d * np.eye(3) - np.outer(d, d))
+        lm, lc, li = arrays["hip_link_mass"], arrays["hip_link_com"], arrays["hip_link_inertia"]
+        lm.reshape(-1)[link] = tot
+        lc.reshape(-1, 3)[link] = com
+        li.reshape(-1, 6)[link] = [I[0, 0], I[1, 1], I[2, 2], I[0, 1], I[0, 2], I[1, 2]]
+        return out
+
     def with_integrator(self, name) -> "Model":
         """Copy of the model with `<option integrator=...>` set: "Euler" (semi-implicit, implicit joint damping) or "RK4" (mj_RungeKutta)."""
         if name not in ("Euler", "RK4"):

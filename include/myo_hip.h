@@ -91,6 +91,23 @@ typedef enum myo_field {
   MYO_F_COUNT
 } myo_field;
 
+/* further per-env fields (ids continue after MYO_F_COUNT, the size of the myo_field list above; myo_batch_field / read / write take them
+ * like any field) */
+enum {
+  MYO_F_BODYPOS = MYO_F_COUNT, /* [B][3] per-env translation of ONE body: the body that carries the model's last joint, which must be a child of the
+                        world heading a kinematic root link (myohand_keyturn: the key) -- KeyTurnEnvV0.reset's `model.body_pos[-1] = ...`
+                        (envs/myo/myobase/key_turn_v0.py:157-169) as an offset from the compiled body_pos.  Starts like MYO_F_BODYMASS: on the
+                        first write of this field or MYO_F_BODYPOS_RANGE, or the first request for either device pointer (both buffers
+                        zero-filled); before that myo_batch_read returns zeros and starts nothing.  The step and the key-turn observation use
+                        the offsets as they are at the launch.  Nothing else changes (the body's inertia, acc0, invweights keep their compiled
+                        values, as without mj_setConst).  Refused (MYO_E_UNSUPPORTED) for models outside the TrackEnv class and when that
+                        body is not a root body; a host write with a non-finite value returns MYO_E_ARG */
+  MYO_F_BODYPOS_RANGE,   /* [B][6] per-env offset range: lo (3) then hi (3).  At every reset of an env (myo_reset, myo_autoreset) each
+                        component with hi > lo gets offset = lo + (hi - lo) u, u ~ U(0,1) from the counter RNG keyed by (episode seed, global
+                        env id, component); components with lo == hi keep their offset.  Starts the offset like MYO_F_BODYPOS; a host write with
+                        hi < lo or a non-finite value returns MYO_E_ARG */
+};
+
 enum { MYO_FLAG_BAD_STATE = 1, MYO_FLAG_BAD_QACC = 2, MYO_FLAG_CONTACT_OVERFLOW = 4, MYO_FLAG_CAND_OVERFLOW = 8,
        MYO_FLAG_SCHED_TIMEOUT = 16 /* opt-in substep scheduler gave up waiting (raised on env 0); the step is incomplete */ };
 
@@ -109,6 +126,14 @@ typedef enum myo_task { MYO_TASK_NONE = 0, MYO_TASK_POSE = 1, MYO_TASK_REACH = 2
                         MYO_TASK_STAND = 5, /* walk_v0.py:13-183 ReachEnvV0 (myoLegStandRandom-v0): reach with a site of the free root link; obs = qpos, qvel*dt,
                                                tip (3), target - tip (3), act; reward 10 - d - 10 |qvel dt| + bonus - 100 |act|/na - penalty */
                         MYO_TASK_TRACK = 6, /* MyoDM TrackEnv (mjx/myodm_v0.py:14-304): see myo_track_config */
+                        MYO_TASK_KEYTURN = 7, /* KeyTurnEnvV0 (envs/myo/myobase/key_turn_v0.py), models of the TrackEnv class whose last
+                                                 joint is the one hinge of a root body (the key).  ntip = 3 sites: key head, index tip, thumb
+                                                 tip.  obs = hand qpos, hand qvel*dt, key qpos, key qvel*dt, head - index tip (3), head -
+                                                 thumb tip (3), act, with the site positions of the post-step state (also MYO_F_SITEXPOS).
+                                                 d_k = | |head - tip_k| - near_th |; reward = w_pose key_q - w_reach (d_IF + d_TH) - w_act_reg
+                                                 |act|/na + w_bonus ([key_q > pi/2] + [key_q > pi]) - w_penalty ([d_IF > far_th/2] + [d_TH >
+                                                 far_th/2]); solved = key_q > pose_thd (goal_th); done = d_IF > far_th or d_TH > far_th.
+                                                 ntarget = 0; the reset draws the key angle through reset_noise / reset_clip */
                         MYO_TASK_HOLD = 4 /* ObjHoldFixedEnvV0 (envs/myo/myobase/obj_hold_v0.py:13-118): the model's LAST joint is the free
                                              object; obs = hand qpos, hand qvel*dt, object position, goal - object, act; target = goal (3) */
 } myo_task;

@@ -15,7 +15,7 @@ SRC_PATH = os.path.join(_HERE, "csrc", "myo_hip.hip")
 # field ids (myo_field)
 (F_QPOS, F_QVEL, F_ACT, F_CTRL, F_WARMSTART, F_TIME, F_TARGET, F_OBS, F_REWARD, F_DONE, F_SOLVED, F_FLAGS, F_DIAG,
  F_QACC, F_TENLEN, F_ACTFORCE, F_SITEXPOS, F_ELAPSED, F_ACTION, F_FATIGUE, F_HFIELD, F_GEOMSIZE, F_LINKX, F_METRICS,
- F_BODYMASS, F_BODYMASS_RANGE) = range(26)
+ F_BODYMASS, F_BODYMASS_RANGE, F_BODYPOS, F_BODYPOS_RANGE) = range(28)
 INT_FIELDS = (F_FLAGS, F_DIAG, F_ELAPSED)
 BENCH_OBS, BENCH_FRESH_ACTIONS, BENCH_AUTORESET = 1, 2, 4
 ACTMAP_NONE, ACTMAP_MUSCLE_SIGMOID, ACTMAP_SIGMOID_FATIGUE, ACTMAP_SIGMOID_REAFFERENTATION, ACTMAP_CTRLRANGE = 0, 1, 2, 3, 4
@@ -23,6 +23,7 @@ TASK_NONE, TASK_POSE, TASK_REACH = 0, 1, 2
 TASK_HOLD = 4
 TASK_STAND = 5
 TASK_TRACK = 6
+TASK_KEYTURN = 7
 FLAG_BAD_STATE, FLAG_BAD_QACC, FLAG_CONTACT_OVERFLOW, FLAG_CAND_OVERFLOW = 1, 2, 4, 8
 
 
@@ -351,6 +352,13 @@ class HipBatch:
         hi = np.broadcast_to(np.asarray(hi, np.float32), (self.B, nb))
         self.write(F_BODYMASS_RANGE, np.concatenate([lo, hi], axis=1))
 
+    def set_body_pos_range(self, lo, hi):
+        """Per-env offset ranges of the root body of MYO_F_BODYPOS ([B, 3] or [3] each): every reset of an env draws offset ~ U(lo, hi) for
+        the components with hi > lo (MYO_F_BODYPOS_RANGE); starts the per-env offset."""
+        lo = np.broadcast_to(np.asarray(lo, np.float32), (self.B, 3))
+        hi = np.broadcast_to(np.asarray(hi, np.float32), (self.B, 3))
+        self.write(F_BODYPOS_RANGE, np.concatenate([lo, hi], axis=1))
+
     def field_ptr(self, field):
         p, pitch, width = C.c_void_p(), C.c_size_t(), C.c_size_t()
         _chk(lib().myo_batch_field(self.h, field, C.byref(p), C.byref(pitch), C.byref(width)))
@@ -362,6 +370,8 @@ class HipBatch:
             return self.model.dims.nbody
         if field == F_BODYMASS_RANGE:
             return 2 * self.model.dims.nbody
+        if field in (F_BODYPOS, F_BODYPOS_RANGE):    # likewise for the per-env root-body offset
+            return 3 if field == F_BODYPOS else 6
         return self.field_ptr(field)[2]
 
     def read(self, field) -> np.ndarray:

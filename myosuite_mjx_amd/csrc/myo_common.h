@@ -134,6 +134,11 @@ struct DevBatch {
   float* bmass_range;      // [B][2 * nbody] lo | hi: a fresh mass ~ U(lo, hi) at every reset of an env for the bodies with hi > lo
   float* linkc;            // [B][nl][10] link mass, COM (3, link frame), inertia about the COM (xx yy zz xy xz yz), recomposed per launch
   int nbody;
+  // per-env translation of one root link (MYO_F_BODYPOS, KeyTurnRandom's key): the TRK instantiation and the key-turn observation kernels add
+  // it to the link's compiled origin; NULL: off
+  float* bpos;             // [B][3] offset
+  float* bpos_range;       // [B][6] lo | hi: a fresh offset ~ U(lo, hi) per component at every reset of an env for the components with hi > lo
+  int bpos_link;           // the root link it moves
   // overflow of the LDS contact table (wave kernel): contacts NC .. NC + NCX - 1 of an env keep their point / normal / jacobian rows in
   // HBM (L2-resident in practice; touched by ~0.4 % of myoHandPoseRandom reset poses), candidates beyond NCAND their pair ids
   float* ovf;              // [B][NCX][ovf_row] floats: dist, pos[3], normal[3], pair id, cJ[3 * KC], dof ids (byte-packed)

@@ -23,6 +23,7 @@
 #include "myo_kernel_lanes.h"
 #include "myo_kernel_wave.h"
 #include "myo_kernels_aux.h"
+#include "myo_task_keyturn.h"
 
 // ================================================================================================
 // host side
@@ -64,6 +65,9 @@ struct myo_model {
   std::vector<float> body_mass0;
   const int *d_lm_adr = nullptr, *d_lm_body = nullptr;
   const double* d_lm_tab = nullptr;
+  // per-env translation of one root body (MYO_F_BODYPOS): the link headed by the body that carries the model's last joint, when that body
+  // is a child of the world heading a root link of a TrackEnv-class model; -1 otherwise
+  int bp_link = -1;
 };
 
 struct myo_batch {
@@ -88,6 +92,7 @@ struct myo_batch {
   int sched_stride = 0;
   int balance = 1;
   bool bm_on = false;            // per-env body-mass override started (DevBatch.bmass / bmass_range / linkc allocated)
+  bool bp_on = false;            // per-env root-body offset started (DevBatch.bpos / bpos_range allocated)
   std::vector<hipEvent_t> kev;   // per-launch event pairs around the step kernel (bench only)
   int kev_pending = 0;           // pairs recorded by asynchronous bench calls and not collected yet
   float last_kernel_ms = 0.f;
@@ -293,6 +298,18 @@ int myo_model_load(const void* blobv, size_t nbytes, int device, myo_model** out
       if ((rc = load_i(m, blob, "hip_trk", &tmpi, &tk)) || (rc = load_f(m, blob, "hip_fl", &w.fl)) || (rc = load_f(m, blob, "hip_mesh_vert", &w.mesh_vert)) ||
           (rc = load_f(m, blob, "hip_mesh_rec", &w.mesh_rec)) || (rc = load_f(m, blob, "hip_mesh_startrec", &w.mesh_startrec)) || (rc = load_f(m, blob, "hip_mesh_aabb", &w.mesh_aabb))) { myo_model_free(m); return rc; }
       m->trk = tk[0] || tk[1] || tk[2];
+      if (m->trk) {   // the root body of MYO_F_BODYPOS: the body of the last joint, a child of the world at the origin of its own root link
+        auto BI = [&](const char* n) { std::vector<int> v; const BlobRec* r = blob_find(blob, n); if (r && r->dtype == 1) { v.resize(r->nbytes / 4); memcpy(v.data(), blob + r->offset, r->nbytes); } return v; };
+        const std::vector<int> jb = BI("jnt_bodyid"), jt = BI("jnt_type"), bp = BI("body_parentid"), bl = BI("hip_body_link"), lpar = BI("hip_link_parent");
+        const int bb = jb.empty() ? -1 : jb.back();
+        if (bb > 0 && jt.size() == jb.size() && (jt.back() == 2 || jt.back() == 3)   // a slide / hinge (a free root takes its pose from qpos)
+            && bb < (int)bp.size() && bb < (int)bl.size() && bp[bb] == 0) {
+          const int l = bl[bb];
+          bool head = l >= 0 && l < (int)lpar.size() && lpar[l] < 0;
+          for (int k = 1; head && k < bb; k++) if (bl[k] == l) head = false;   // the body heads its link (no earlier body welded into it)
+          if (head) m->bp_link = l;
+        }
+      }
     }
     {  // self-contained per-lane records (DevModelW::seg_rec, dl_pk, ...): denormalised copies of the tables loaded above
       auto BI = [&](const char* n) { std::vector<int> v; const BlobRec* r = blob_find(blob, n); if (r && r->dtype == 1) { v.resize(r->nbytes / 4); memcpy(v.data(), blob + r->offset, r->nbytes); } return v; };
@@ -628,6 +645,20 @@ int myo_batch_configure(myo_batch* b, const myo_task_config* c) {
     if (!(b->model->wave_ok && b->model->dw.has_free && b->model->nq == nv + 1)) return fail(MYO_E_UNSUPPORTED, "stand task needs a model with a free root joint");
     T.obs_dim = b->model->nq + nv + 6 + b->model->dm.na_obs;
   }
+  else if (c->task == MYO_TASK_KEYTURN) {
+    // key_turn_v0.py: the key is the model's last joint, one hinge of a root body; sites = key head, index tip, thumb tip
+    const myo_model* m = b->model;
+    if (!(m->wave_ok && m->trk) || m->bp_link < 0 || m->nq != nv) return fail(MYO_E_UNSUPPORTED, "key-turn task: a TrackEnv-class model without free / ball joints whose last joint is the hinge of a root body");
+    std::vector<int> ltype(1), ldn(1), ldof(1);
+    HIPCHK(hipMemcpy(ltype.data(), dm.dof_type + (nv - 1), 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ldn.data(), dm.link_dofnum + m->bp_link, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ldof.data(), dm.dof_link + (nv - 1), 4, hipMemcpyDeviceToHost));
+    if (ltype[0] != 3 || ldn[0] != 1 || ldof[0] != m->bp_link) return fail(MYO_E_UNSUPPORTED, "key-turn task: the last joint must be the one hinge of its root body");
+    if (c->ntip != 3 || c->ntarget != 0) return fail(MYO_E_ARG, "key-turn task: ntip = 3 (key head, index tip, thumb tip) and ntarget = 0");
+    for (int k = 0; k < 3; k++) if (c->tip_site[k] < 0 || c->tip_site[k] >= m->dims.nsite) return fail(MYO_E_ARG, "key-turn task: site id out of range");
+    if (!(c->near_th >= 0.f) || !(c->far_th > 0.f) || !(c->pose_thd == c->pose_thd)) return fail(MYO_E_ARG, "key-turn task: near_th >= 0, far_th > 0, goal_th (pose_thd) a number");
+    T.obs_dim = 2 * nv + 6 + dm.na_obs;
+  }
   else if (c->task == MYO_TASK_HOLD) {
     if (c->ntarget != 3) return fail(MYO_E_ARG, "hold task: ntarget must be 3 (goal position)");
     if (!(b->model->wave_ok && b->model->dw.has_free && b->model->nq == nv + 1 && nv > 6)) return fail(MYO_E_UNSUPPORTED, "hold task needs a model whose last joint is one free object");
@@ -810,6 +841,27 @@ static int bm_start(myo_batch* b) {
   return MYO_OK;
 }
 
+// per-env root-body offset (MYO_F_BODYPOS / MYO_F_BODYPOS_RANGE): TrackEnv-class models whose last joint sits on a root body only
+static int bp_check(const myo_batch* b) {
+  const myo_model* m = b->model;
+  if (!(m->wave_ok && m->trk)) return fail(MYO_E_UNSUPPORTED, "per-env body position: models of the TrackEnv class only");
+  if (m->bp_link < 0) return fail(MYO_E_UNSUPPORTED, "per-env body position: the body of the model's last joint is not a root body (a child of the world heading its link)");
+  return MYO_OK;
+}
+
+static int bp_start(myo_batch* b) {
+  if (b->bp_on) return MYO_OK;
+  int rc = bp_check(b);
+  if (rc) return rc;
+  DevBatch& d = b->db;
+  float *bp = nullptr, *br = nullptr;
+  HIPCHK(hipSetDevice(b->model->device));
+  if ((rc = balloc(b, (void**)&bp, (size_t)d.B * 3 * 4)) || (rc = balloc(b, (void**)&br, (size_t)d.B * 6 * 4))) return rc;   // zero: no offset
+  d.bpos = bp; d.bpos_range = br; d.bpos_link = b->model->bp_link;
+  b->bp_on = true;
+  return MYO_OK;
+}
+
 static int field_info(myo_batch* b, int f, void** p, size_t* pitch, size_t* width) {
   const DevModel& dm = b->model->dm;
   DevBatch& d = b->db;
@@ -854,6 +906,8 @@ static int field_info(myo_batch* b, int f, void** p, size_t* pitch, size_t* widt
       *pitch = *width = f == MYO_F_BODYMASS ? nb : 2 * nb;
       break;
     }
+    case MYO_F_BODYPOS: *p = d.bpos; *pitch = *width = 3; break;          // (NULL until the offset is started)
+    case MYO_F_BODYPOS_RANGE: *p = d.bpos_range; *pitch = *width = 6; break;
     default: return fail(MYO_E_ARG, "unknown field");
   }
   return MYO_OK;
@@ -862,6 +916,7 @@ static int field_info(myo_batch* b, int f, void** p, size_t* pitch, size_t* widt
 int myo_batch_field(myo_batch* b, int field, void** dev_ptr, size_t* pitch, size_t* width) {
   if (!b || !dev_ptr || !pitch || !width) return fail(MYO_E_ARG, "myo_batch_field: null");
   if (field == MYO_F_BODYMASS || field == MYO_F_BODYMASS_RANGE) { int rc = bm_start(b); if (rc) return rc; }
+  if (field == MYO_F_BODYPOS || field == MYO_F_BODYPOS_RANGE) { int rc = bp_start(b); if (rc) return rc; }
   return field_info(b, field, dev_ptr, pitch, width);
 }
 
@@ -879,6 +934,11 @@ int myo_batch_read(myo_batch* b, int field, void* host, size_t nbytes) {
       if (field == MYO_F_BODYMASS) memcpy(h + (size_t)e * width, m0.data(), width * 4);
       else memset(h + (size_t)e * width, 0, width * 4);
     }
+    return MYO_OK;
+  }
+  if ((field == MYO_F_BODYPOS || field == MYO_F_BODYPOS_RANGE) && !b->bp_on) {   // not started: no offsets, empty ranges
+    if ((rc = bp_check(b))) return rc;
+    memset(host, 0, nbytes);
     return MYO_OK;
   }
   HIPCHK(hipSetDevice(b->model->device));
@@ -906,6 +966,16 @@ int myo_batch_write(myo_batch* b, int field, const void* host, size_t nbytes) {
         }
       }
     if ((rc = bm_start(b))) return rc;
+    if ((rc = field_info(b, field, &p, &pitch, &width))) return rc;
+  }
+  if (field == MYO_F_BODYPOS || field == MYO_F_BODYPOS_RANGE) {
+    if ((rc = bp_check(b))) return rc;
+    const float* h = (const float*)host;
+    for (size_t i = 0; i < (size_t)b->db.B * width; i++) if (!std::isfinite(h[i])) return fail(MYO_E_ARG, "MYO_F_BODYPOS / MYO_F_BODYPOS_RANGE: values must be finite");
+    if (field == MYO_F_BODYPOS_RANGE)
+      for (int e = 0; e < b->db.B; e++)
+        for (int k = 0; k < 3; k++) if (!(h[6 * e + 3 + k] >= h[6 * e + k])) return fail(MYO_E_ARG, "MYO_F_BODYPOS_RANGE: need lo <= hi");
+    if ((rc = bp_start(b))) return rc;
     if ((rc = field_info(b, field, &p, &pitch, &width))) return rc;
   }
   HIPCHK(hipSetDevice(b->model->device));
@@ -1108,6 +1178,8 @@ static int launch_obs(myo_batch* b, hipStream_t s, int obs_only = 0, int reset_o
     return launch_step(b, nullptr, MYO_ACTMAP_NONE, 0, s, KF_AUX | (obs_only ? KF_OBS_ONLY : 0) | (reset_only ? KF_RESET_ONLY : 0));
   } else if (b->task.task == MYO_TASK_POSE || b->task.task == MYO_TASK_HOLD || b->task.task == MYO_TASK_STAND || b->task.task == MYO_TASK_TRACK) {
     hipLaunchKernelGGL(obs_kernel, dim3(B), dim3(64), 0, s, m->dm, b->db, b->task, obs_only, reset_only);
+  } else if (b->task.task == MYO_TASK_KEYTURN) {
+    hipLaunchKernelGGL(keyturn_obs_kernel, dim3(B), dim3(64), 0, s, m->dm, b->db, b->task, obs_only, reset_only);
   } else if (b->task.task == MYO_TASK_REACH) {
     const int EPW = 4;
     hipLaunchKernelGGL(reach_obs_kernel<16>, dim3((B + EPW - 1) / EPW), dim3(64), (size_t)EPW * m->env_lds_bytes, s, m->dm, b->db, b->task, obs_only);
@@ -1218,6 +1290,11 @@ int myo_bench_rollout(myo_batch* b, int steps, int nsubsteps, uint64_t seed, int
     if ((mode & MYO_BENCH_OBS) && (mode & MYO_BENCH_AUTORESET) && max_episode_steps > 0 && (tk == MYO_TASK_POSE || tk == MYO_TASK_HOLD || tk == MYO_TASK_STAND)) {
       // state-only observations: observation + auto-reset + first observation of the new episodes in ONE launch (post_kernel)
       hipLaunchKernelGGL(post_kernel, dim3(b->db.B), dim3(64), 0, s, b->model->dm, b->db, b->task, b->model->nq, b->model->dm.qpos0, seed, b->env_offset, max_episode_steps);
+      HIPCHK(hipGetLastError());
+      continue;
+    }
+    if ((mode & MYO_BENCH_OBS) && (mode & MYO_BENCH_AUTORESET) && max_episode_steps > 0 && tk == MYO_TASK_KEYTURN) {   // the same for the key-turn task
+      hipLaunchKernelGGL(keyturn_post_kernel, dim3(b->db.B), dim3(64), 0, s, b->model->dm, b->db, b->task, b->model->nq, b->model->dm.qpos0, seed, b->env_offset, max_episode_steps);
       HIPCHK(hipGetLastError());
       continue;
     }

@@ -616,6 +616,12 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
       const bool mine = lane < nl_;
       const float* lp = M.link_pos + 3 * l;
       float A[9], c[3] = {lp[0], lp[1], lp[2]};
+      if constexpr (TRK) {   // per-env translation of one root link (MYO_F_BODYPOS): its origin, and with it its joints' anchors, moves
+        if (Bt.bpos && l == Bt.bpos_link) {
+          const float* o = Bt.bpos + 3 * (size_t)env;
+          c[0] += o[0]; c[1] += o[1]; c[2] += o[2];
+        }
+      }
 #pragma unroll
       for (int k = 0; k < 9; k++) A[k] = W.link_mat0[9 * l + k];
       const int da = M.link_dofadr[l];

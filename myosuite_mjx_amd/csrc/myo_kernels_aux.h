@@ -173,6 +173,11 @@ __device__ __forceinline__ bool reset_body(const DevBatch& Bt, const TaskDev& T,
       if (h > l) Bt.bmass[(size_t)e * Bt.nbody + i] = l + (h - l) * u01(seed ^ 0x3C6EF372FE94F82Bull, ge * 4096 + i, 9);
     }
   }
+  if (Bt.bpos_range && lane < 3) {
+    // KeyTurnEnvV0.reset (key_turn_v0.py:164-167, Random variant): the key body's position = its compiled position + U(-0.01, 0.01)^3 per episode
+    const float l = Bt.bpos_range[(size_t)e * 6 + lane], h = Bt.bpos_range[(size_t)e * 6 + 3 + lane];
+    if (h > l) Bt.bpos[(size_t)e * 3 + lane] = l + (h - l) * u01(seed ^ 0x5851F42D4C957F2Dull, ge * 8 + lane, 10);
+  }
   if (T.terrain && Bt.hfield) {
     // TerrainEnvV0.reset (walk_v0.py:563-622): a fresh 100 x 100 elevation grid per episode (in units of the height field's z scale).
     // Distribution parity only for the random draws, as for every reset.

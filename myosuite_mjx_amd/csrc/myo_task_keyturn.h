@@ -1,0 +1,119 @@
+// myo_task_keyturn.h -- KeyTurnEnvV0 (envs/myo/myobase/key_turn_v0.py) observation / reward / done / solved, MYO_TASK_KEYTURN.
+//
+// The model is of the TrackEnv class (the key's box bit and the friction loss of its hinge), whose step kernel keeps no kinematics a
+// separate pass could reuse, and the lanes kernel's reach_obs_kernel is not available to it.  So this kernel runs its own forward
+// kinematics, and only of what the task reads: the ancestor chains of its three sites (key head, index tip, thumb tip), one lane per site,
+// from the post-step qpos -- the site positions of the reference's post-step forward pass.  One 64-lane workgroup per env.
+#ifndef MYO_TASK_KEYTURN_H
+#define MYO_TASK_KEYTURN_H
+
+// world position (relative to the lowered origin) of site s at the joint positions q of env e.  The site's link chain is walked up to its
+// root; each link's own joint chain, in its parent's frame, is applied to the point on the way (the transform the wave kernel's kinematics
+// phase 1 builds per link).  The per-env offset of MYO_F_BODYPOS moves its root link's origin, as in the TRK step kernel.  Hinge / slide
+// joints only (nq == nv, checked at configure).
+__device__ __forceinline__ void keyturn_site_pos(const DevModel& M, const DevBatch& Bt, const float* q, int e, int s, float* p) {
+  p[0] = M.site_lpos[3 * s]; p[1] = M.site_lpos[3 * s + 1]; p[2] = M.site_lpos[3 * s + 2];
+  for (int l = M.site_link[s]; l >= 0; l = M.link_parent[l]) {
+    float A[9], c[3] = {M.link_pos[3 * l], M.link_pos[3 * l + 1], M.link_pos[3 * l + 2]};
+    const float lq[4] = {M.link_quat[4 * l], M.link_quat[4 * l + 1], M.link_quat[4 * l + 2], M.link_quat[4 * l + 3]};
+    quat2mat(A, lq);
+    if (Bt.bpos && l == Bt.bpos_link) {
+      const float* o = Bt.bpos + 3 * (size_t)e;
+      c[0] += o[0]; c[1] += o[1]; c[2] += o[2];
+    }
+    const int da = M.link_dofadr[l], dn = M.link_dofnum[l];
+    for (int k = 0; k < dn; k++) {
+      const int d = da + k;
+      const float al[3] = {M.dof_axis[3 * d], M.dof_axis[3 * d + 1], M.dof_axis[3 * d + 2]};
+      const float dp[3] = {M.dof_pos[3 * d], M.dof_pos[3 * d + 1], M.dof_pos[3 * d + 2]};
+      const float ang = q[d] - M.qpos0[d];
+      float ax[3], an[3];
+      matvec(ax, A, al);
+      matvec(an, A, dp);
+      an[0] += c[0]; an[1] += c[1]; an[2] += c[2];
+      if (M.dof_type[d] == 3) {   // hinge: rotate about the axis through the anchor
+        float sn, cs;
+        sincosf(ang, &sn, &cs);
+        const float oc = 1 - cs, x = al[0], y = al[1], z = al[2];
+        const float Rj[9] = {cs + oc * x * x, oc * x * y - sn * z, oc * x * z + sn * y, oc * x * y + sn * z, cs + oc * y * y, oc * y * z - sn * x,
+                             oc * x * z - sn * y, oc * y * z + sn * x, cs + oc * z * z};
+        float v[3];
+        matmul3(A, A, Rj);
+        matvec(v, A, dp);
+        c[0] = an[0] - v[0]; c[1] = an[1] - v[1]; c[2] = an[2] - v[2];
+      } else {                    // slide
+        c[0] += ax[0] * ang; c[1] += ax[1] * ang; c[2] += ax[2] * ang;
+      }
+    }
+    float w[3];
+    matvec(w, A, p);
+    p[0] = w[0] + c[0]; p[1] = w[1] + c[1]; p[2] = w[2] + c[2];
+  }
+}
+
+// key_turn_v0.py:82-156 (+ act, base_v0.py:34-38).  Row: hand qpos (nq - 1), hand qvel * dt (nv - 1), key qpos, key qvel * dt, head - index
+// tip (3), head - thumb tip (3), act (na).  get_reward_dict reads the approach vectors and act from self.obs_dict but key_q from its argument;
+// at step time both are the obs_dict of the stepped state, so one set of values serves both here.
+__device__ __forceinline__ void keyturn_obs_body(const DevModel& M, const DevBatch& Bt, const TaskDev& T, int obs_only, const int e, const int lane) {
+  const int nv = M.nv, nu = M.nu, nh = nv - 1;
+  const float dt = (float)T.frame_skip * M.timestep;
+  float* o = Bt.obs + (size_t)e * T.obs_dim;
+  const float* q = Bt.qpos + (size_t)e * nv;
+  const float* v = Bt.qvel + (size_t)e * nv;
+  const float* a = Bt.act + (size_t)e * nu;
+  float p[3] = {0.f, 0.f, 0.f};
+  if (lane < 3) {   // lane 0: key head, 1: index tip, 2: thumb tip
+    keyturn_site_pos(M, Bt, q, e, T.tip_site[lane], p);
+#pragma unroll
+    for (int k = 0; k < 3; k++) { p[k] += M.origin[k]; Bt.sitexpos[(size_t)e * 9 + 3 * lane + k] = p[k]; }
+  }
+  float h[3], dk = 0.f;
+#pragma unroll
+  for (int k = 0; k < 3; k++) h[k] = __shfl(p[k], 0);
+  if (lane == 1 || lane == 2) {
+    const float r[3] = {h[0] - p[0], h[1] - p[1], h[2] - p[2]};
+#pragma unroll
+    for (int k = 0; k < 3; k++) o[2 * nv + 3 * (lane - 1) + k] = r[k];
+    dk = fabsf(norm3(r) - T.near_th);
+  }
+  for (int i = lane; i < nv; i += 64) {
+    if (i < nh) { o[i] = q[i]; o[nh + i] = v[i] * dt; }
+    else { o[2 * nh] = q[i]; o[2 * nh + 1] = v[i] * dt; }
+  }
+  float act2 = 0.f;
+  for (int i = lane; i < nu; i += 64) { const float ai = a[i]; const int sl = M.act_obs[i]; if (sl >= 0) { o[2 * nv + 6 + sl] = ai; act2 += ai * ai; } }
+  const float d_if = __shfl(dk, 1), d_th = __shfl(dk, 2);
+  if (obs_only) return;
+  const float actn = sqrtf(wave_sum(act2)) / (float)(M.na_obs > 0 ? M.na_obs : 1);
+  if (lane == 0) {
+    const float key_q = q[nh];
+    const float bonus = (key_q > 1.57079632679489662f ? 1.f : 0.f) + (key_q > 3.14159265358979324f ? 1.f : 0.f);
+    const float pen = -(d_if > 0.5f * T.far_th ? 1.f : 0.f) - (d_th > 0.5f * T.far_th ? 1.f : 0.f);
+    Bt.reward[e] = T.w_pose * key_q + T.w_reach * (-d_if) + T.w_reach * (-d_th) + T.w_act_reg * (-actn) + T.w_bonus * bonus + T.w_penalty * pen;
+    Bt.solved[e] = key_q > T.pose_thd ? 1.f : 0.f;
+    Bt.done[e] = (d_if > T.far_th || d_th > T.far_th) ? 1.f : 0.f;
+  }
+}
+
+__global__ void __launch_bounds__(64) keyturn_obs_kernel(DevModel M, DevBatch Bt, TaskDev T, int obs_only, int reset_only) {
+  const int e = blockIdx.x;
+  if (e >= Bt.B) return;
+  if (reset_only && Bt.elapsed[e] != 0) return;    // refresh only the rows of envs an auto-reset just touched
+  keyturn_obs_body(M, Bt, T, obs_only, e, threadIdx.x);
+}
+
+// myo_bench_rollout's fused epilogue (post_kernel's pattern): observation / reward / done of the stepped state, auto-reset, and the first
+// observation of the new episodes, in one launch
+__global__ void __launch_bounds__(64) keyturn_post_kernel(DevModel M, DevBatch Bt, TaskDev T, int nq, const float* qpos0, uint64_t seed, int env_offset,
+                                                          int auto_max) {
+  const int e = blockIdx.x, lane = threadIdx.x;
+  if (e >= Bt.B) return;
+  keyturn_obs_body(M, Bt, T, 0, e, lane);
+  __syncthreads();                       // reward / done of this env written (lane 0) before every lane tests them
+  if (reset_body(Bt, T, nq, M.nv, M.nu, qpos0, nullptr, seed, env_offset, auto_max, e, lane)) {
+    __syncthreads();                     // the new state rows (and the key offset) are complete before they are read back
+    keyturn_obs_body(M, Bt, T, 1, e, lane);
+  }
+}
+
+#endif  // MYO_TASK_KEYTURN_H

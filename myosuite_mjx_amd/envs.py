@@ -130,6 +130,13 @@ REGISTRY["myoLegStandRandom-v0"] = dict(
 for _id, _kind, _sc in (("myoLegRoughTerrainWalk-v0", "rough", (0.0, 0.0)), ("myoLegHillyTerrainWalk-v0", "hilly", (0.63, 0.63)),
                         ("myoLegStairTerrainWalk-v0", "stairs", (2.5, 2.5))):
     REGISTRY[_id] = dict(REGISTRY["myoLegWalk-v0"], model="myolegs_terrain", terrain=_kind, terrain_scalar=_sc, knee_height=0.61)
+# myoHandKeyTurn{Fixed,Random}-v0 (envs/myo/myobase/__init__.py:574-593, key_turn_v0.py): MyoHand + a key on a hinge with friction loss (a
+# model of the TrackEnv class: the key's box bit, the hinge's frictionloss).  Fully open hand at reset, key angle ~ U(key_init_range); Random
+# also moves the key body by U(-0.01, 0.01)^3 from its compiled position at every reset (BatchedMyoEnv.body_pos)
+REGISTRY["myoHandKeyTurnFixed-v0"] = dict(
+    model="myohand_keyturn", task="keyturn", max_episode_steps=200, frame_skip=10, normalize_act=True, goal_th=3.14, key_init_range=(0.0, 0.0),
+    weights=dict(key_turn=1.0, IFtip_approach=10.0, THtip_approach=10.0, act_reg=1.0, bonus=4.0, penalty=25.0))
+REGISTRY["myoHandKeyTurnRandom-v0"] = dict(REGISTRY["myoHandKeyTurnFixed-v0"], goal_th=2 * np.pi, key_init_range=(-np.pi / 2, np.pi / 2))
 # muscle-condition variants (register_env_with_variants, envs/myo/myobase/__init__.py:14-48): myoSarc* (sarcopenia), myoFati* (fatigue)
 # for every myo* id, myoReaf* (EIP -> EPL tendon transfer) for the myoHand* ids
 for _id in [k for k in list(REGISTRY) if k.startswith("myo")]:
@@ -204,8 +211,10 @@ class BatchedMyoEnv:
     """
 
     # env kwargs of the reference that gym.make forwards to the env class and that are honoured here (others raise)
-    ENV_KWARGS = ("reset_type", "fatigue_reset_random", "fatigue_reset_vec", "weight_bodyname", "weight_range", "target_jnt_range")
+    ENV_KWARGS = ("reset_type", "fatigue_reset_random", "fatigue_reset_vec", "weight_bodyname", "weight_range", "target_jnt_range",
+                  "goal_th", "key_init_range")
     POSE_KWARGS = ("weight_bodyname", "weight_range", "target_jnt_range")   # PoseEnvV0 kwargs (pose_v0.py:56-75): pose tasks only
+    KEYTURN_KWARGS = ("goal_th", "key_init_range")                           # KeyTurnEnvV0._setup kwargs (key_turn_v0.py:54-61): key turn only
 
     def __init__(self, env_id, num_envs=1, device=0, seed=0, env_offset=0, autoreset=True, as_torch=True, **env_kwargs):
         if env_id in UNSUPPORTED:
@@ -215,8 +224,9 @@ class BatchedMyoEnv:
         self.id = env_id
         self.spec = spec = dict(REGISTRY[env_id])
         for k, v in env_kwargs.items():
-            if k not in self.ENV_KWARGS or (k in self.POSE_KWARGS and spec.get("task") != "pose"):
-                raise TypeError(f"{env_id}: unsupported env kwarg {k!r} (supported: {self.ENV_KWARGS}; {self.POSE_KWARGS} for pose tasks only)")
+            if k not in self.ENV_KWARGS or (k in self.POSE_KWARGS and spec.get("task") != "pose") or (k in self.KEYTURN_KWARGS and spec.get("task") != "keyturn"):
+                raise TypeError(f"{env_id}: unsupported env kwarg {k!r} (supported: {self.ENV_KWARGS}; {self.POSE_KWARGS} for pose tasks only, "
+                                f"{self.KEYTURN_KWARGS} for the key-turn task only)")
             spec[k] = v
         self.num_envs = int(num_envs)
         self.device = device
@@ -308,6 +318,24 @@ class BatchedMyoEnv:
             self.obs_dim = (m.nq - 7) + (m.nv - 6) + 6 + m.n_muscle
             if "object_size" in spec:
                 self.batch.set_geom_override(m.name2id("geom", "object"), *spec["object_size"])
+        elif spec["task"] == "keyturn":
+            # key_turn_v0.py:54-75, 157-169: fully open hand (init_qpos[:-1] = 0), key angle ~ U(key_init_range) (a reset noise on the last
+            # coordinate only); the Random variant (key_init_range[0] != key_init_range[1]) also re-draws the key body's position
+            lo_k, hi_k = (float(x) for x in spec["key_init_range"])
+            if not hi_k >= lo_k:
+                raise ValueError(f"{env_id}: key_init_range must be (lo, hi) with lo <= hi")
+            init = np.zeros(m.nq)
+            nlo, nhi = np.zeros(m.nq), np.zeros(m.nq)
+            nlo[-1], nhi[-1] = lo_k, hi_k
+            big = np.full(m.nq, 1e30)
+            self.batch.configure(task=capi.TASK_KEYTURN, frame_skip=self.frame_skip, reset_random=0, target_generate=0, init_qpos=init,
+                                 reset_noise=(nlo, nhi), reset_clip=(-big, big),
+                                 tip_sites=[m.name2id("site", n) for n in ("keyhead", "IFtip", "THtip")],
+                                 pose_thd=float(spec["goal_th"]), near_th=0.030, far_th=0.1,
+                                 w_pose=w["key_turn"], w_reach=w["IFtip_approach"], w_act_reg=w["act_reg"], w_bonus=w["bonus"], w_penalty=w["penalty"])
+            self.obs_dim = 2 * m.nq + 6 + m.n_muscle
+            if lo_k != hi_k:                                           # key_turn_v0.py:164-167: key_init_pos + U(-0.01, 0.01)^3
+                self.batch.set_body_pos_range(np.full(3, -0.01), np.full(3, 0.01))
         else:
             tips = [m.name2id("site", t) for t in spec["tips"]]
             n = len(tips)
@@ -382,6 +410,21 @@ class BatchedMyoEnv:
         r = self.batch.read(capi.F_BODYMASS_RANGE)
         r[:, b], r[:, nb + b] = float(lo), float(hi)
         self.batch.write(capi.F_BODYMASS_RANGE, r)
+
+    # -- per-env root-body offset (MYO_F_BODYPOS) --------------------------------------------------------------
+    @property
+    def body_pos(self):
+        """[num_envs, 3] offset of the key body from its compiled position in every env (the batched `sim.model.body_pos[-1] = ...` of
+        KeyTurnEnvV0.reset, as an offset): a torch view of the library's buffer (no copy; writes take effect at the next step / observation).
+        TrackEnv-class models whose last joint sits on a root body only.  With as_torch=False: a numpy copy (assign the property to write it)."""
+        return self.view(capi.F_BODYPOS)
+
+    @body_pos.setter
+    def body_pos(self, value):
+        if self.as_torch:
+            self.view(capi.F_BODYPOS).copy_(self._torch.as_tensor(value, dtype=self._torch.float32).expand(self.num_envs, -1))
+        else:
+            self.batch.write(capi.F_BODYPOS, np.broadcast_to(np.asarray(value, np.float32), (self.num_envs, 3)))
 
     # -- zero-copy views ---------------------------------------------------------------------------------
     def view(self, field):

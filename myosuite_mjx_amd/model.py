@@ -14,6 +14,9 @@ import numpy as np
 from . import blob as _blob
 
 ASSET_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets")
+# compiled models added since the seed assets are data fixtures of the repository (tests/golden/, like every other binary derived from the
+# reference's files); load_asset looks there after ASSET_DIR
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 
 
 class Model:
@@ -125,6 +128,28 @@ class Model:
         li.reshape(-1, 6)[link] = [I[0, 0], I[1, 1], I[2, 2], I[0, 1], I[0, 2], I[1, 2]]
         return out
 
+    def with_body_pos(self, body, pos) -> "Model":
+        """Copy of the model with `body_pos[body] = pos` (`body`: id or name), as KeyTurnEnvV0.reset moves the key
+        (envs/myo/myobase/key_turn_v0.py:164-167).  The HIP tables follow for a body that heads a kinematic root link (its link origin moves
+        by the same amount); nothing else changes (inertias, invweights and lengthranges keep their values, as without mj_setConst)."""
+        b = self.body_name2id(body) if isinstance(body, str) else int(body)
+        if not 0 < b < self.nbody:
+            raise ValueError(f"no movable body {body!r}")
+        pos = np.asarray(pos, float).reshape(3)
+        if not np.isfinite(pos).all():
+            raise ValueError("body position must be finite")
+        arrays = {k: np.array(v, copy=True) for k, v in self.arrays.items()}
+        delta = pos - arrays["body_pos"][b]
+        arrays["body_pos"][b] = pos
+        if "hip_body_link" in arrays:
+            link = int(arrays["hip_body_link"][b])
+            heads = link >= 0 and int(arrays["hip_link_parent"][link]) < 0 and int(arrays["body_parentid"][b]) == 0 and \
+                min(k for k in range(1, self.nbody) if int(arrays["hip_body_link"][k]) == link) == b
+            if not heads:
+                raise NotImplementedError("with_body_pos: only a child of the world heading a root link (the HIP tables would need re-lowering)")
+            arrays["hip_link_pos"].reshape(-1, 3)[link] += delta
+        return Model(arrays, self.names, self.source)
+
     def with_integrator(self, name) -> "Model":
         """Copy of the model with `<option integrator=...>` set: "Euler" (semi-implicit, implicit joint damping) or "RK4" (mj_RungeKutta)."""
         if name not in ("Euler", "RK4"):
@@ -178,9 +203,15 @@ def from_mjcf(path, terrain=False, replace=None, convex_meshes=False) -> Model:
 _ASSETS = {"myohand_pose": "myohand_pose", "myofinger_v0": "myofinger_v0", "myolegs": "myolegs"}
 
 
+def asset_stem(name) -> str:
+    """Path stem of a committed compiled model: under ASSET_DIR, else under GOLDEN_DIR (e.g. 'myohand_keyturn')."""
+    for d in (ASSET_DIR, GOLDEN_DIR):
+        stem = os.path.join(d, name)
+        if os.path.exists(stem + ".myob") or os.path.exists(stem + ".myob.gz"):
+            return stem
+    raise FileNotFoundError(f"compiled model {name!r} not found under {ASSET_DIR} or {GOLDEN_DIR}; run tools/compile_models.py")
+
+
 def load_asset(name) -> Model:
     """Load a committed compiled model by stem (e.g. 'myohand_pose')."""
-    stem = os.path.join(ASSET_DIR, name)
-    if not (os.path.exists(stem + ".myob") or os.path.exists(stem + ".myob.gz")):
-        raise FileNotFoundError(f"compiled model {name!r} not found under {ASSET_DIR}; run tools/compile_models.py")
-    return Model.load(stem)
+    return Model.load(asset_stem(name))

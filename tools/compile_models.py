@@ -33,6 +33,11 @@ for _obj in ("alarmclock", "banana", "binoculars", "camera", "coffeemug", "cubel
              "teapot", "toothbrush", "toothpaste", "toruslarge", "torusmedium", "torussmall", "train", "watch", "waterbottle", "wineglass"):
     MODELS[f"myohand_object_{_obj}"] = ("myosuite/envs/myo/assets/hand/myohand_object.xml", {"OBJECT_NAME": _obj}, "gz")
 
+# compiled models committed as data fixtures under tests/golden/ (gzip-compressed; model.load_asset finds them there)
+GOLDEN = {
+    "myohand_keyturn": "myosuite/envs/myo/assets/hand/myohand_keyturn.xml",   # KeyTurnEnvV0: a box bit and joint friction loss (TrackEnv class)
+}
+
 if __name__ == "__main__":
     only = sys.argv[1:]
     for stem, rel in MODELS.items():
@@ -43,4 +48,10 @@ if __name__ == "__main__":
         else:
             m = M.from_mjcf(os.path.join(REF, rel[0]), terrain=True) if isinstance(rel, tuple) else M.from_mjcf(os.path.join(REF, rel))
         m.save(os.path.join(M.ASSET_DIR, stem), compress=isinstance(rel, tuple) and len(rel) == 3)
+        print(stem, dict(nq=m.nq, nv=m.nv, nu=m.nu, nbody=m.nbody, ntendon=m.ntendon, bytes=len(m.blob())))
+    for stem, rel in GOLDEN.items():
+        if only and stem not in only:
+            continue
+        m = M.from_mjcf(os.path.join(REF, rel))
+        m.save(os.path.join(M.GOLDEN_DIR, stem), compress=True)
         print(stem, dict(nq=m.nq, nv=m.nv, nu=m.nu, nbody=m.nbody, ntendon=m.ntendon, bytes=len(m.blob())))

@@ -111,6 +111,23 @@ enum {
 enum { MYO_FLAG_BAD_STATE = 1, MYO_FLAG_BAD_QACC = 2, MYO_FLAG_CONTACT_OVERFLOW = 4, MYO_FLAG_CAND_OVERFLOW = 8,
        MYO_FLAG_SCHED_TIMEOUT = 16 /* opt-in substep scheduler gave up waiting (raised on env 0); the step is incomplete */ };
 
+/* per-env orientation of one world-welded body (ids continue after MYO_F_BODYPOS_RANGE) */
+enum {
+  MYO_F_BODYQUAT = MYO_F_BODYPOS_RANGE + 1, /* [B][4] absolute body_quat (w x y z) of the body selected by myo_task_config.quat_body (a jointless
+                        child of the world, myohand_pen: the target) -- PenTwirlRandomEnvV0.reset's `model.body_quat[target] = euler2quat(...)`
+                        (envs/myo/myobase/pen_v0.py:173-184).  Its static collision geoms and sites turn about the body origin: x = p_b +
+                        R(q) R(q0)^T (x0 - p_b).  Starts like MYO_F_BODYPOS: on the first write of this field or MYO_F_BODYQUAT_RANGE, or the
+                        first request for either device pointer (filled with the compiled quaternion, empty ranges); before that
+                        myo_batch_read returns the compiled quaternion and starts nothing.  The body is selected through
+                        myo_task_config.quat_body; without a selected body: MYO_E_ARG.  A host write
+                        with a non-finite value or a quaternion whose norm is not 1 (to 1e-4) returns MYO_E_ARG */
+  MYO_F_BODYQUAT_RANGE,  /* [B][6] per-env Euler range: lo (3) then hi (3).  At every reset of an env with hi > lo in some component, the
+                        angles e_k = lo_k + (hi_k - lo_k) u_k, u ~ U(0,1) from the counter RNG keyed by (episode seed, global env id,
+                        component), give body_quat = euler2quat(e) (the reference's utils/quat_math.py:77-93); ranges with lo == hi in all
+                        components keep the quaternion.  Starts like MYO_F_BODYQUAT; a host write with hi < lo or a non-finite value
+                        returns MYO_E_ARG */
+};
+
 /* action -> control map applied inside myo_step (base_v0.py:87-91) */
 enum {
   MYO_ACTMAP_NONE = 0,
@@ -134,6 +151,16 @@ typedef enum myo_task { MYO_TASK_NONE = 0, MYO_TASK_POSE = 1, MYO_TASK_REACH = 2
                                                  |act|/na + w_bonus ([key_q > pi/2] + [key_q > pi]) - w_penalty ([d_IF > far_th/2] + [d_TH >
                                                  far_th/2]); solved = key_q > pose_thd (goal_th); done = d_IF > far_th or d_TH > far_th.
                                                  ntarget = 0; the reset draws the key angle through reset_noise / reset_clip */
+                        MYO_TASK_PEN = 8, /* PenTwirl{Fixed,Random}EnvV0 (envs/myo/myobase/pen_v0.py), models of the TrackEnv class whose
+                                             last six joints are the free-standing pen (3 slides + 3 hinges of one root body).  ntip = 5
+                                             sites: object top, object bottom, target top, target bottom, eps_ball; tip_lpos = the object
+                                             body's origin in its link frame.  obs = hand qpos (nq - 6), object position (3), object
+                                             qvel*dt (6), obj_rot (3), obj_des_rot (3), object position - eps_ball (3), obj_rot - obj_des_rot
+                                             (3), act, with the site positions of the post-step state (also MYO_F_SITEXPOS, 15 floats);
+                                             rot = (top - bottom) / length.  pos_align = |obj_err_pos|, rot_align = cosine; reward = -w_pose
+                                             pos_align + w_reach rot_align - w_act_reg |act|/na - w_penalty [pos_align > far_th] + w_bonus
+                                             ([rot_align > 0.9] + 5 [rot_align > 0.95]) [pos_align < far_th]; done = pos_align > far_th;
+                                             solved = rot_align > pose_thd and not done.  ntarget = 0 */
                         MYO_TASK_HOLD = 4 /* ObjHoldFixedEnvV0 (envs/myo/myobase/obj_hold_v0.py:13-118): the model's LAST joint is the free
                                              object; obs = hand qpos, hand qvel*dt, object position, goal - object, act; target = goal (3) */
 } myo_task;
@@ -155,7 +182,10 @@ typedef struct myo_task_config {
    * entry; host pointers, nq floats each (copied), all four or none (NULL) */
   const float *reset_noise_lo, *reset_noise_hi, *reset_clip_lo, *reset_clip_hi;
   const float* init_qvel; /* host pointer, nv floats (copied) or NULL = zero */
-  float tip_lpos[3];      /* stand: the tip site's position in the root link's frame */
+  float tip_lpos[3];      /* stand: the tip site's position in the root link's frame; pen: the object body's origin in its link frame */
+  int quat_body;          /* > 0: selects the body of MYO_F_BODYQUAT / MYO_F_BODYQUAT_RANGE (compiled-model body id; 0: no selection, an
+                             earlier one stays).  A batch selects one body once.  MYO_E_UNSUPPORTED for models outside the TrackEnv class
+                             and for a body with joints or whose parent is not the world */
 } myo_task_config;
 
 /* walk task (WalkEnvV0: envs/myo/myobase/walk_v0.py:187-470, registered as myoLegWalk-v0 in envs/myo/myobase/__init__.py:443-459).

@@ -16,6 +16,7 @@ SRC_PATH = os.path.join(_HERE, "csrc", "myo_hip.hip")
 (F_QPOS, F_QVEL, F_ACT, F_CTRL, F_WARMSTART, F_TIME, F_TARGET, F_OBS, F_REWARD, F_DONE, F_SOLVED, F_FLAGS, F_DIAG,
  F_QACC, F_TENLEN, F_ACTFORCE, F_SITEXPOS, F_ELAPSED, F_ACTION, F_FATIGUE, F_HFIELD, F_GEOMSIZE, F_LINKX, F_METRICS,
  F_BODYMASS, F_BODYMASS_RANGE, F_BODYPOS, F_BODYPOS_RANGE) = range(28)
+F_BODYQUAT, F_BODYQUAT_RANGE = 28, 29      # per-env orientation of one world-welded body (TaskConfig.quat_body selects it)
 INT_FIELDS = (F_FLAGS, F_DIAG, F_ELAPSED)
 BENCH_OBS, BENCH_FRESH_ACTIONS, BENCH_AUTORESET = 1, 2, 4
 ACTMAP_NONE, ACTMAP_MUSCLE_SIGMOID, ACTMAP_SIGMOID_FATIGUE, ACTMAP_SIGMOID_REAFFERENTATION, ACTMAP_CTRLRANGE = 0, 1, 2, 3, 4
@@ -24,6 +25,7 @@ TASK_HOLD = 4
 TASK_STAND = 5
 TASK_TRACK = 6
 TASK_KEYTURN = 7
+TASK_PEN = 8
 FLAG_BAD_STATE, FLAG_BAD_QACC, FLAG_CONTACT_OVERFLOW, FLAG_CAND_OVERFLOW = 1, 2, 4, 8
 
 
@@ -41,7 +43,7 @@ class TaskConfig(C.Structure):
                 ("target_lo", C.POINTER(C.c_float)), ("target_hi", C.POINTER(C.c_float)), ("init_qpos", C.POINTER(C.c_float)),
                 ("reset_noise_lo", C.POINTER(C.c_float)), ("reset_noise_hi", C.POINTER(C.c_float)),
                 ("reset_clip_lo", C.POINTER(C.c_float)), ("reset_clip_hi", C.POINTER(C.c_float)),
-                ("init_qvel", C.POINTER(C.c_float)), ("tip_lpos", C.c_float * 3)]
+                ("init_qvel", C.POINTER(C.c_float)), ("tip_lpos", C.c_float * 3), ("quat_body", C.c_int)]
 
 
 class WalkConfig(C.Structure):
@@ -238,8 +240,9 @@ class HipBatch:
     def configure(self, task=TASK_NONE, frame_skip=1, reset_random=0, target_generate=0, target_lo=None, target_hi=None,
                   init_qpos=None, tip_sites=(), pose_thd=0.35, far_th=2 * np.pi, near_th=0.0,
                   w_pose=1.0, w_bonus=4.0, w_act_reg=1.0, w_penalty=50.0, w_reach=1.0, reset_noise=None, reset_clip=None, init_qvel=None,
-                  tip_lpos=(0.0, 0.0, 0.0)):
+                  tip_lpos=(0.0, 0.0, 0.0), quat_body=0):
         c = TaskConfig()
+        c.quat_body = int(quat_body)
         c.task, c.frame_skip, c.reset_random, c.target_generate = task, frame_skip, int(reset_random), int(target_generate)
         lo = np.ascontiguousarray(target_lo if target_lo is not None else [], np.float32)
         hi = np.ascontiguousarray(target_hi if target_hi is not None else lo, np.float32)
@@ -359,6 +362,13 @@ class HipBatch:
         hi = np.broadcast_to(np.asarray(hi, np.float32), (self.B, 3))
         self.write(F_BODYPOS_RANGE, np.concatenate([lo, hi], axis=1))
 
+    def set_body_quat_range(self, lo, hi):
+        """Per-env Euler ranges of the selected body ([B, 3] or [3] each): every reset of an env sets body_quat = euler2quat(U(lo, hi))
+        (MYO_F_BODYQUAT_RANGE); starts the per-env orientation."""
+        lo = np.broadcast_to(np.asarray(lo, np.float32), (self.B, 3))
+        hi = np.broadcast_to(np.asarray(hi, np.float32), (self.B, 3))
+        self.write(F_BODYQUAT_RANGE, np.concatenate([lo, hi], axis=1))
+
     def field_ptr(self, field):
         p, pitch, width = C.c_void_p(), C.c_size_t(), C.c_size_t()
         _chk(lib().myo_batch_field(self.h, field, C.byref(p), C.byref(pitch), C.byref(width)))
@@ -372,6 +382,8 @@ class HipBatch:
             return 2 * self.model.dims.nbody
         if field in (F_BODYPOS, F_BODYPOS_RANGE):    # likewise for the per-env root-body offset
             return 3 if field == F_BODYPOS else 6
+        if field in (F_BODYQUAT, F_BODYQUAT_RANGE):  # ... and the per-env body orientation
+            return 4 if field == F_BODYQUAT else 6
         return self.field_ptr(field)[2]
 
     def read(self, field) -> np.ndarray:

@@ -148,6 +148,12 @@ struct DevBatch {
   float* linkx;            // [B][12 * nl] link frames of the last substep's position stage (TRK models; NULL otherwise)
   const DevTrack* track;   // MYO_TASK_TRACK configured (TRK models): prologue / epilogue of the step kernel; NULL otherwise
   int env_offset;          // global id of env 0 (RNG streams are keyed by global env id)
+  // per-env orientation of one world-welded body (MYO_F_BODYQUAT, PenTwirlRandom's target): the TRK instantiation turns the body's static
+  // collision geoms, the pen observation its static sites, about the body origin; NULL: off
+  float* bquat;            // [B][4] body_quat (w x y z)
+  float* bquat_range;      // [B][6] Euler lo | hi: body_quat = euler2quat(U(lo, hi)) at every reset of an env with hi > lo in some component
+  const float* bq_c;       // [12] R(q0)^T (row-major) | body origin (lowered coordinates)
+  const int* bq_flag;      // [ncg + nsite] 1: collision geom / site of that body
 };
 #define NCX 48      // overflow contact rows ALLOCATED per env; a kernel with NC LDS slots uses 64 - NC of them: 64 contacts in all
 #define NCX2 96     // TRK models: 128 contacts, 32 in LDS + 96 rows; rows of the second bank also hold that contact's solver state
@@ -206,6 +212,18 @@ __device__ __forceinline__ void quat2mat(float* R, const float* q) {
   R[0] = w * w + x * x - y * y - z * z; R[1] = 2 * (x * y - w * z); R[2] = 2 * (x * z + w * y);
   R[3] = 2 * (x * y + w * z); R[4] = w * w - x * x + y * y - z * z; R[5] = 2 * (y * z - w * x);
   R[6] = 2 * (x * z - w * y); R[7] = 2 * (y * z + w * x); R[8] = w * w - x * x - y * y + z * z;
+}
+// the reference's utils/quat_math.py:77-93 euler2quat (not the MJCF compiler's eulerseq): q = (w, x, y, z) of Euler angles e
+__device__ __forceinline__ void euler2quat(float* q, const float* e) {
+  float si, ci, sj, cj, sk, ck;
+  sincosf(0.5f * e[2], &si, &ci);
+  sincosf(-0.5f * e[1], &sj, &cj);
+  sincosf(0.5f * e[0], &sk, &ck);
+  const float cc = ci * ck, cs = ci * sk, sc = si * ck, ss = si * sk;
+  q[0] = cj * cc + sj * ss;
+  q[1] = cj * cs - sj * sc;
+  q[2] = -(cj * ss + sj * cc);
+  q[3] = cj * sc - sj * cs;
 }
 __device__ __forceinline__ void mulquat(float* r, const float* a, const float* b) {
   float t0 = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];

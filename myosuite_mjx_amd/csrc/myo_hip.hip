@@ -24,6 +24,7 @@
 #include "myo_kernel_wave.h"
 #include "myo_kernels_aux.h"
 #include "myo_task_keyturn.h"
+#include "myo_task_pen.h"
 
 // ================================================================================================
 // host side
@@ -68,6 +69,9 @@ struct myo_model {
   // per-env translation of one root body (MYO_F_BODYPOS): the link headed by the body that carries the model's last joint, when that body
   // is a child of the world heading a root link of a TrackEnv-class model; -1 otherwise
   int bp_link = -1;
+  // per-env orientation of one world-welded body (MYO_F_BODYQUAT): compiled body tree, poses and the bodies of the collision geoms / sites
+  std::vector<int> body_parent, body_jntnum, cg_body, site_body;
+  std::vector<double> body_pos0, body_quat0;
 };
 
 struct myo_batch {
@@ -93,6 +97,8 @@ struct myo_batch {
   int balance = 1;
   bool bm_on = false;            // per-env body-mass override started (DevBatch.bmass / bmass_range / linkc allocated)
   bool bp_on = false;            // per-env root-body offset started (DevBatch.bpos / bpos_range allocated)
+  int bq_body = -1;              // body of MYO_F_BODYQUAT (myo_task_config.quat_body; -1: none selected)
+  bool bq_on = false;            // per-env body orientation started (DevBatch.bquat / bquat_range / bq_c / bq_flag allocated)
   std::vector<hipEvent_t> kev;   // per-launch event pairs around the step kernel (bench only)
   int kev_pending = 0;           // pairs recorded by asynchronous bench calls and not collected yet
   float last_kernel_ms = 0.f;
@@ -298,6 +304,14 @@ int myo_model_load(const void* blobv, size_t nbytes, int device, myo_model** out
       if ((rc = load_i(m, blob, "hip_trk", &tmpi, &tk)) || (rc = load_f(m, blob, "hip_fl", &w.fl)) || (rc = load_f(m, blob, "hip_mesh_vert", &w.mesh_vert)) ||
           (rc = load_f(m, blob, "hip_mesh_rec", &w.mesh_rec)) || (rc = load_f(m, blob, "hip_mesh_startrec", &w.mesh_startrec)) || (rc = load_f(m, blob, "hip_mesh_aabb", &w.mesh_aabb))) { myo_model_free(m); return rc; }
       m->trk = tk[0] || tk[1] || tk[2];
+      if (m->trk) {   // bodies of MYO_F_BODYQUAT: the tree, compiled poses, and the body of every collision geom and site
+        auto BI = [&](const char* n) { std::vector<int> v; const BlobRec* r = blob_find(blob, n); if (r && r->dtype == 1) { v.resize(r->nbytes / 4); memcpy(v.data(), blob + r->offset, r->nbytes); } return v; };
+        auto BD = [&](const char* n) { std::vector<double> v; const BlobRec* r = blob_find(blob, n); if (r && r->dtype == 0) { v.resize(r->nbytes / 8); memcpy(v.data(), blob + r->offset, r->nbytes); } return v; };
+        const std::vector<int> gb = BI("geom_bodyid");
+        m->body_parent = BI("body_parentid"); m->body_jntnum = BI("body_jntnum"); m->site_body = BI("site_bodyid");
+        m->body_pos0 = BD("body_pos"); m->body_quat0 = BD("body_quat");
+        for (int g : m->cg_geom) m->cg_body.push_back(g >= 0 && g < (int)gb.size() ? gb[g] : -1);
+      }
       if (m->trk) {   // the root body of MYO_F_BODYPOS: the body of the last joint, a child of the world at the origin of its own root link
         auto BI = [&](const char* n) { std::vector<int> v; const BlobRec* r = blob_find(blob, n); if (r && r->dtype == 1) { v.resize(r->nbytes / 4); memcpy(v.data(), blob + r->offset, r->nbytes); } return v; };
         const std::vector<int> jb = BI("jnt_bodyid"), jt = BI("jnt_type"), bp = BI("body_parentid"), bl = BI("hip_body_link"), lpar = BI("hip_link_parent");
@@ -310,6 +324,13 @@ int myo_model_load(const void* blobv, size_t nbytes, int device, myo_model** out
           if (head) m->bp_link = l;
         }
       }
+    }
+    {  // plane - cylinder pairs (lowering.py pair types 6 / 7) have a narrow phase in the TRK instantiation only: never dropped silently
+      std::vector<int> pi2;
+      const int* t3;
+      if ((rc = load_i(m, blob, "hip_pair_i", &t3, &pi2))) { myo_model_free(m); return rc; }
+      for (int p = 0; p < d.npair; p++)
+        if ((pi2[6 * p + 4] == 6 || pi2[6 * p + 4] == 7) && !m->trk) { myo_model_free(m); return fail(MYO_E_UNSUPPORTED, "plane - cylinder pairs need a model of the TrackEnv class"); }
     }
     {  // self-contained per-lane records (DevModelW::seg_rec, dl_pk, ...): denormalised copies of the tables loaded above
       auto BI = [&](const char* n) { std::vector<int> v; const BlobRec* r = blob_find(blob, n); if (r && r->dtype == 1) { v.resize(r->nbytes / 4); memcpy(v.data(), blob + r->offset, r->nbytes); } return v; };
@@ -615,6 +636,8 @@ void myo_batch_free(myo_batch* b) {
 
 int myo_batch_size(const myo_batch* b) { return b ? b->db.B : 0; }
 
+static int set_quat_body(myo_batch* b, int body);   // (below, with the rest of MYO_F_BODYQUAT)
+
 int myo_batch_configure(myo_batch* b, const myo_task_config* c) {
   if (!b || !c) return fail(MYO_E_ARG, "myo_batch_configure: null");
   if (b->bm_on && c->task == MYO_TASK_STAND) return fail(MYO_E_UNSUPPORTED, "per-env body masses: the stand task uses model-wide mass totals");
@@ -622,6 +645,7 @@ int myo_batch_configure(myo_batch* b, const myo_task_config* c) {
   TaskDev& T = b->task;
   int nv = dm.nv, nu = dm.nu;
   if (c->ntarget > b->ntarget_alloc || c->ntip > 8) return fail(MYO_E_ARG, "myo_batch_configure: ntarget/ntip too large");
+  if (c->quat_body > 0) { int rc = set_quat_body(b, c->quat_body); if (rc) return rc; }
   if (c->task == MYO_TASK_WALK) return fail(MYO_E_ARG, "use myo_batch_configure_walk for the walk task");
   T.init_qvel = nullptr; T.rnd = nullptr;
   T.terrain = 0; T.hf_n = 0;
@@ -658,6 +682,25 @@ int myo_batch_configure(myo_batch* b, const myo_task_config* c) {
     for (int k = 0; k < 3; k++) if (c->tip_site[k] < 0 || c->tip_site[k] >= m->dims.nsite) return fail(MYO_E_ARG, "key-turn task: site id out of range");
     if (!(c->near_th >= 0.f) || !(c->far_th > 0.f) || !(c->pose_thd == c->pose_thd)) return fail(MYO_E_ARG, "key-turn task: near_th >= 0, far_th > 0, goal_th (pose_thd) a number");
     T.obs_dim = 2 * nv + 6 + dm.na_obs;
+  }
+  else if (c->task == MYO_TASK_PEN) {
+    // pen_v0.py: the pen is the model's last six joints, 3 slides + 3 hinges of one root body; sites = object top / bottom, target top /
+    // bottom, eps_ball
+    const myo_model* m = b->model;
+    if (!(m->wave_ok && m->trk) || m->nq != nv || nv < 7) return fail(MYO_E_UNSUPPORTED, "pen task: a TrackEnv-class model without free / ball joints whose last six joints are the pen's");
+    std::vector<int> dtype(6), dlink(6), lpar(1), ldn(1);
+    HIPCHK(hipMemcpy(dtype.data(), dm.dof_type + (nv - 6), 24, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(dlink.data(), dm.dof_link + (nv - 6), 24, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(lpar.data(), dm.link_parent + dlink[5], 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ldn.data(), dm.link_dofnum + dlink[5], 4, hipMemcpyDeviceToHost));
+    bool ok = lpar[0] < 0 && ldn[0] == 6;
+    for (int k = 0; k < 6; k++) ok = ok && dlink[k] == dlink[5] && dtype[k] == (k < 3 ? 2 : 3);
+    if (!ok) return fail(MYO_E_UNSUPPORTED, "pen task: the last six joints must be 3 slides + 3 hinges of one root body");
+    if (c->ntip != 5 || c->ntarget != 0) return fail(MYO_E_ARG, "pen task: ntip = 5 (object top, object bottom, target top, target bottom, eps_ball) and ntarget = 0");
+    for (int k = 0; k < 5; k++) if (c->tip_site[k] < 0 || c->tip_site[k] >= m->dims.nsite) return fail(MYO_E_ARG, "pen task: site id out of range");
+    for (int k = 0; k < 3; k++) if (!std::isfinite(c->tip_lpos[k])) return fail(MYO_E_ARG, "pen task: tip_lpos must be finite");
+    if (!(c->far_th > 0.f) || !(c->pose_thd == c->pose_thd)) return fail(MYO_E_ARG, "pen task: far_th > 0, pose_thd a number");
+    T.obs_dim = (nv - 6) + 21 + dm.na_obs;
   }
   else if (c->task == MYO_TASK_HOLD) {
     if (c->ntarget != 3) return fail(MYO_E_ARG, "hold task: ntarget must be 3 (goal position)");
@@ -862,6 +905,61 @@ static int bp_start(myo_batch* b) {
   return MYO_OK;
 }
 
+// per-env orientation of one world-welded body (MYO_F_BODYQUAT / MYO_F_BODYQUAT_RANGE): TrackEnv-class models, the body selected first
+// (myo_task_config.quat_body)
+static int set_quat_body(myo_batch* b, int body) {
+  const myo_model* m = b->model;
+  if (!(m->wave_ok && m->trk)) return fail(MYO_E_UNSUPPORTED, "per-env body orientation: models of the TrackEnv class only");
+  if (body <= 0 || body >= (int)m->body_parent.size()) return fail(MYO_E_ARG, "quat_body: body id out of range");
+  if (m->body_parent[body] != 0 || m->body_jntnum[body] != 0) return fail(MYO_E_UNSUPPORTED, "per-env body orientation: a jointless child of the world only");
+  if (b->bq_on && body != b->bq_body) return fail(MYO_E_ARG, "quat_body: the orientation of another body has started");
+  b->bq_body = body;
+  return MYO_OK;
+}
+
+static int bq_check(const myo_batch* b) {
+  const myo_model* m = b->model;
+  if (!(m->wave_ok && m->trk)) return fail(MYO_E_UNSUPPORTED, "per-env body orientation: models of the TrackEnv class only");
+  if (b->bq_body < 0) return fail(MYO_E_ARG, "per-env body orientation: no body selected (myo_task_config.quat_body)");
+  return MYO_OK;
+}
+
+static void quat2mat_d(double* R, const double* q) {
+  const double w = q[0], x = q[1], y = q[2], z = q[3];
+  R[0] = w * w + x * x - y * y - z * z; R[1] = 2 * (x * y - w * z); R[2] = 2 * (x * z + w * y);
+  R[3] = 2 * (x * y + w * z); R[4] = w * w - x * x + y * y - z * z; R[5] = 2 * (y * z - w * x);
+  R[6] = 2 * (x * z - w * y); R[7] = 2 * (y * z + w * x); R[8] = w * w - x * x - y * y + z * z;
+}
+
+static int bq_start(myo_batch* b) {
+  if (b->bq_on) return MYO_OK;
+  int rc = bq_check(b);
+  if (rc) return rc;
+  const myo_model* m = b->model;
+  DevBatch& d = b->db;
+  const int bd = b->bq_body, ncg = m->dm.ncg, ns = m->dims.nsite;
+  std::vector<float> q((size_t)d.B * 4), c(12);
+  double R0[9];
+  quat2mat_d(R0, &m->body_quat0[4 * (size_t)bd]);
+  for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) c[3 * i + j] = (float)R0[3 * j + i];   // R(q0)^T
+  for (int k = 0; k < 3; k++) c[9 + k] = (float)(m->body_pos0[3 * (size_t)bd + k] - m->dm.origin[k]);   // (lowered coordinates)
+  for (int e = 0; e < d.B; e++) for (int k = 0; k < 4; k++) q[4 * (size_t)e + k] = (float)m->body_quat0[4 * (size_t)bd + k];
+  std::vector<int> fl((size_t)ncg + ns, 0);
+  for (int g = 0; g < ncg; g++) fl[g] = m->cg_body[g] == bd;
+  for (int s2 = 0; s2 < ns; s2++) fl[ncg + s2] = m->site_body[s2] == bd;
+  float *bq = nullptr, *br = nullptr, *bc = nullptr;
+  int* bf = nullptr;
+  HIPCHK(hipSetDevice(m->device));
+  if ((rc = balloc(b, (void**)&bq, (size_t)d.B * 4 * 4)) || (rc = balloc(b, (void**)&br, (size_t)d.B * 6 * 4)) ||
+      (rc = balloc(b, (void**)&bc, 12 * 4)) || (rc = balloc(b, (void**)&bf, fl.size() * 4))) return rc;
+  HIPCHK(hipMemcpy(bq, q.data(), q.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(bc, c.data(), c.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(bf, fl.data(), fl.size() * 4, hipMemcpyHostToDevice));
+  d.bquat = bq; d.bquat_range = br; d.bq_c = bc; d.bq_flag = bf;
+  b->bq_on = true;
+  return MYO_OK;
+}
+
 static int field_info(myo_batch* b, int f, void** p, size_t* pitch, size_t* width) {
   const DevModel& dm = b->model->dm;
   DevBatch& d = b->db;
@@ -908,6 +1006,8 @@ static int field_info(myo_batch* b, int f, void** p, size_t* pitch, size_t* widt
     }
     case MYO_F_BODYPOS: *p = d.bpos; *pitch = *width = 3; break;          // (NULL until the offset is started)
     case MYO_F_BODYPOS_RANGE: *p = d.bpos_range; *pitch = *width = 6; break;
+    case MYO_F_BODYQUAT: *p = d.bquat; *pitch = *width = 4; break;         // (NULL until the orientation is started)
+    case MYO_F_BODYQUAT_RANGE: *p = d.bquat_range; *pitch = *width = 6; break;
     default: return fail(MYO_E_ARG, "unknown field");
   }
   return MYO_OK;
@@ -917,6 +1017,7 @@ int myo_batch_field(myo_batch* b, int field, void** dev_ptr, size_t* pitch, size
   if (!b || !dev_ptr || !pitch || !width) return fail(MYO_E_ARG, "myo_batch_field: null");
   if (field == MYO_F_BODYMASS || field == MYO_F_BODYMASS_RANGE) { int rc = bm_start(b); if (rc) return rc; }
   if (field == MYO_F_BODYPOS || field == MYO_F_BODYPOS_RANGE) { int rc = bp_start(b); if (rc) return rc; }
+  if (field == MYO_F_BODYQUAT || field == MYO_F_BODYQUAT_RANGE) { int rc = bq_start(b); if (rc) return rc; }
   return field_info(b, field, dev_ptr, pitch, width);
 }
 
@@ -939,6 +1040,13 @@ int myo_batch_read(myo_batch* b, int field, void* host, size_t nbytes) {
   if ((field == MYO_F_BODYPOS || field == MYO_F_BODYPOS_RANGE) && !b->bp_on) {   // not started: no offsets, empty ranges
     if ((rc = bp_check(b))) return rc;
     memset(host, 0, nbytes);
+    return MYO_OK;
+  }
+  if ((field == MYO_F_BODYQUAT || field == MYO_F_BODYQUAT_RANGE) && !b->bq_on) {   // not started: the compiled quaternion, empty ranges
+    if ((rc = bq_check(b))) return rc;
+    float* h = (float*)host;
+    for (int e = 0; e < b->db.B; e++)
+      for (size_t k = 0; k < width; k++) h[(size_t)e * width + k] = field == MYO_F_BODYQUAT ? (float)b->model->body_quat0[4 * (size_t)b->bq_body + k] : 0.f;
     return MYO_OK;
   }
   HIPCHK(hipSetDevice(b->model->device));
@@ -976,6 +1084,22 @@ int myo_batch_write(myo_batch* b, int field, const void* host, size_t nbytes) {
       for (int e = 0; e < b->db.B; e++)
         for (int k = 0; k < 3; k++) if (!(h[6 * e + 3 + k] >= h[6 * e + k])) return fail(MYO_E_ARG, "MYO_F_BODYPOS_RANGE: need lo <= hi");
     if ((rc = bp_start(b))) return rc;
+    if ((rc = field_info(b, field, &p, &pitch, &width))) return rc;
+  }
+  if (field == MYO_F_BODYQUAT || field == MYO_F_BODYQUAT_RANGE) {
+    if ((rc = bq_check(b))) return rc;
+    const float* h = (const float*)host;
+    for (size_t i = 0; i < (size_t)b->db.B * width; i++) if (!std::isfinite(h[i])) return fail(MYO_E_ARG, "MYO_F_BODYQUAT / MYO_F_BODYQUAT_RANGE: values must be finite");
+    for (int e = 0; e < b->db.B; e++) {
+      const float* r = h + (size_t)e * width;
+      if (field == MYO_F_BODYQUAT) {
+        const double n = std::sqrt((double)r[0] * r[0] + (double)r[1] * r[1] + (double)r[2] * r[2] + (double)r[3] * r[3]);
+        if (!(std::fabs(n - 1.0) <= 1e-4)) return fail(MYO_E_ARG, "MYO_F_BODYQUAT: quaternions must have norm 1");
+      } else {
+        for (int k = 0; k < 3; k++) if (!(r[3 + k] >= r[k])) return fail(MYO_E_ARG, "MYO_F_BODYQUAT_RANGE: need lo <= hi");
+      }
+    }
+    if ((rc = bq_start(b))) return rc;
     if ((rc = field_info(b, field, &p, &pitch, &width))) return rc;
   }
   HIPCHK(hipSetDevice(b->model->device));
@@ -1180,6 +1304,8 @@ static int launch_obs(myo_batch* b, hipStream_t s, int obs_only = 0, int reset_o
     hipLaunchKernelGGL(obs_kernel, dim3(B), dim3(64), 0, s, m->dm, b->db, b->task, obs_only, reset_only);
   } else if (b->task.task == MYO_TASK_KEYTURN) {
     hipLaunchKernelGGL(keyturn_obs_kernel, dim3(B), dim3(64), 0, s, m->dm, b->db, b->task, obs_only, reset_only);
+  } else if (b->task.task == MYO_TASK_PEN) {
+    hipLaunchKernelGGL(pen_obs_kernel, dim3(B), dim3(64), 0, s, m->dm, b->db, b->task, obs_only, reset_only);
   } else if (b->task.task == MYO_TASK_REACH) {
     const int EPW = 4;
     hipLaunchKernelGGL(reach_obs_kernel<16>, dim3((B + EPW - 1) / EPW), dim3(64), (size_t)EPW * m->env_lds_bytes, s, m->dm, b->db, b->task, obs_only);
@@ -1295,6 +1421,11 @@ int myo_bench_rollout(myo_batch* b, int steps, int nsubsteps, uint64_t seed, int
     }
     if ((mode & MYO_BENCH_OBS) && (mode & MYO_BENCH_AUTORESET) && max_episode_steps > 0 && tk == MYO_TASK_KEYTURN) {   // the same for the key-turn task
       hipLaunchKernelGGL(keyturn_post_kernel, dim3(b->db.B), dim3(64), 0, s, b->model->dm, b->db, b->task, b->model->nq, b->model->dm.qpos0, seed, b->env_offset, max_episode_steps);
+      HIPCHK(hipGetLastError());
+      continue;
+    }
+    if ((mode & MYO_BENCH_OBS) && (mode & MYO_BENCH_AUTORESET) && max_episode_steps > 0 && tk == MYO_TASK_PEN) {       // ... and the pen task
+      hipLaunchKernelGGL(pen_post_kernel, dim3(b->db.B), dim3(64), 0, s, b->model->dm, b->db, b->task, b->model->nq, b->model->dm.qpos0, seed, b->env_offset, max_episode_steps);
       HIPCHK(hipGetLastError());
       continue;
     }

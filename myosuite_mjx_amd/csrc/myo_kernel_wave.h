@@ -237,6 +237,19 @@ template <class LY> __device__ __forceinline__ void frame_point(const LY& Y, con
   out[1] = P[1] + R[3] * lp[0] + R[4] * lp[1] + R[5] * lp[2];
   out[2] = P[2] + R[6] * lp[0] + R[7] * lp[1] + R[8] * lp[2];
 }
+// per-env orientation of one world-welded body (MYO_F_BODYQUAT; the TRK instantiation passes it, every other one a constant nullptr): the
+// body's static collision geoms turn about its origin p_b, x = p_b + D (x0 - p_b) and R = D R0 with D = R(q_env) R(q0)^T.  Wave-uniform.
+struct BodyRot {
+  const float* q;      // this env's quaternion (NULL: off)
+  const float* c;      // R(q0)^T (9, row-major) | p_b (3)
+  const int* flag;     // per collision geom: 1 on that body
+};
+__device__ __forceinline__ void body_rot(const BodyRot& br, float* D) {
+  const float q[4] = {br.q[0], br.q[1], br.q[2], br.q[3]};
+  float Rq[9];
+  quat2mat(Rq, q);
+  matmul3(D, Rq, br.c);
+}
 // world centre / rotation of collision geom g from its record (DevModelW::cg_rec: link, lpos | rotation | type, bounding radius)
 template <class LY> __device__ __forceinline__ void geom_world_pos(const DevModelW& W, const LY& Y, const float* E, int g, float* out) {
   const float4 r0 = W.cg_rec[4 * g];
@@ -253,6 +266,25 @@ template <class LY> __device__ __forceinline__ void geom_world_mat(const DevMode
     for (int k = 0; k < 9; k++) R[k] = lm[k];
   } else {
     matmul3(R, E + Y.lmat + 9 * l, lm);
+  }
+}
+// ... with the per-env orientation of BodyRot (br: a constant nullptr outside the TRK instantiation, which leaves the two calls above)
+template <class LY> __device__ __forceinline__ void geom_world_pos(const DevModelW& W, const LY& Y, const float* E, int g, float* out, const BodyRot* br) {
+  geom_world_pos(W, Y, E, g, out);
+  if (br && br->q && __float_as_int(W.cg_rec[4 * g].x) < 0 && br->flag[g]) {
+    float D[9], v[3];
+    const float d[3] = {out[0] - br->c[9], out[1] - br->c[10], out[2] - br->c[11]};
+    body_rot(*br, D);
+    matvec(v, D, d);
+    out[0] = br->c[9] + v[0]; out[1] = br->c[10] + v[1]; out[2] = br->c[11] + v[2];
+  }
+}
+template <class LY> __device__ __forceinline__ void geom_world_mat(const DevModelW& W, const LY& Y, const float* E, int g, float* R, const BodyRot* br) {
+  geom_world_mat(W, Y, E, g, R);
+  if (br && br->q && __float_as_int(W.cg_rec[4 * g].x) < 0 && br->flag[g]) {
+    float D[9];
+    body_rot(*br, D);
+    matmul3(R, D, R);   // (matmul3 writes through a temporary)
   }
 }
 // moment-arm entries of one straight tendon piece
@@ -1073,13 +1105,16 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
     // ---------------------------------------------------------------- collision (geom frames computed on the fly)
     int ncon = 0;
     if (!M.disable_contact) {
+      // TRK: per-env orientation of one world-welded body (MYO_F_BODYQUAT), applied wherever a geom frame is built; a constant nullptr elsewhere
+      const BodyRot BR{TRK && Bt.bquat ? Bt.bquat + 4 * (size_t)env : nullptr, Bt.bq_c, Bt.bq_flag};
+      const BodyRot* const brp = TRK ? &BR : nullptr;
       int ncand = 0;
       int* cand = (int*)(E + Y.cand);
       PairRaw pnext = pair_raw(min(lane, npair_ > 0 ? npair_ - 1 : 0));   // broad phase, round 0: requested here, behind the geom frames
       for (int g = lane; g < ncg_; g += 64) {   // world centre and long axis (3rd column) of every collision geom (more than 64: MyoDM teapot, wineglass)
         float x[3], R[9];
-        geom_world_pos(W, Y, E, g, x);
-        geom_world_mat(W, Y, E, g, R);
+        geom_world_pos(W, Y, E, g, x, brp);
+        geom_world_mat(W, Y, E, g, R, brp);
         E[Y.gpos + 3 * g] = x[0]; E[Y.gpos + 3 * g + 1] = x[1]; E[Y.gpos + 3 * g + 2] = x[2];
         E[Y.gax + 3 * g] = R[2]; E[Y.gax + 3 * g + 1] = R[5]; E[Y.gax + 3 * g + 2] = R[8];
       }
@@ -1101,7 +1136,7 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
             float ext[3];
             if (ty == GEOM_ELLIPSOID) {
               float R[9];
-              geom_world_mat(W, Y, E, g2, R);
+              geom_world_mat(W, Y, E, g2, R, brp);
 #pragma unroll
               for (int k = 0; k < 3; k++) { const float a = R[3 * k] * sz[0], b = R[3 * k + 1] * sz[1], c = R[3 * k + 2] * sz[2]; ext[k] = sqrtf(a * a + b * b + c * c); }
             } else {
@@ -1129,7 +1164,7 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
               if (hit && P[4] == 5) {   // plane - hull: the lowest corner of the hull's vertex bounding box along the plane normal
                 float R2[9], nl[3];
                 const float* n = E + Y.gax + 3 * g1;
-                geom_world_mat(W, Y, E, g2, R2);
+                geom_world_mat(W, Y, E, g2, R2, brp);
                 matTvec(nl, R2, n);
                 gpf bx = W.mesh_aabb + 6 * (int)Q.s2[2];
                 const float low = dot3(dif, n) + nl[0] * bx[0] + nl[1] * bx[1] + nl[2] * bx[2] - (fabsf(nl[0]) * bx[3] + fabsf(nl[1]) * bx[4] + fabsf(nl[2]) * bx[5]);
@@ -1141,7 +1176,7 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
                   const int gb = side ? g2 : g1, go = side ? g1 : g2, tb = side ? t2 : t1;
                   if (tb < 6 || !hit) continue;
                   float Rb[9], cl[3], dd[3] = {E[Y.gpos + 3 * go] - E[Y.gpos + 3 * gb], E[Y.gpos + 3 * go + 1] - E[Y.gpos + 3 * gb + 1], E[Y.gpos + 3 * go + 2] - E[Y.gpos + 3 * gb + 2]};
-                  geom_world_mat(W, Y, E, gb, Rb);
+                  geom_world_mat(W, Y, E, gb, Rb, brp);
                   matTvec(cl, Rb, dd);
                   const float* sb = side ? Q.s2 : Q.s1;
                   float hx = sb[0], hy = sb[1], hz = sb[2];
@@ -1190,7 +1225,7 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
                     else if (ty == GEOM_SPHERE) wsum += sz[0];
                     else {
                       float R[9], dl[3];
-                      geom_world_mat(W, Y, E, g, R);
+                      geom_world_mat(W, Y, E, g, R, brp);
                       matTvec(dl, R, ax);
                       if (ty == GEOM_ELLIPSOID) { float sv[3] = {sz[0] * dl[0], sz[1] * dl[1], sz[2] * dl[2]}; wsum += norm3(sv); }
                       else wsum += sz[0] * sqrtf(dl[0] * dl[0] + dl[1] * dl[1]) + sz[1] * fabsf(dl[2]);   // cylinder
@@ -1291,7 +1326,7 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
           } else if (FULL && TRK && P[4] == 5) {   // plane - convex hull: deepest vertex along -normal (one contact)
             const float* n = E + Y.gax + 3 * g1;
             float R2[9], nl[3], pw[3];
-            geom_world_mat(W, Y, E, g2, R2);
+            geom_world_mat(W, Y, E, g2, R2, brp);
             matTvec(nl, R2, n);
             CObj oh;
             cobj_shape_poly(oh, 7, sz2);
@@ -1308,10 +1343,63 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
 #pragma unroll
               for (int k = 0; k < 3; k++) cpos[k] = x2[k] + pw[k] - n[k] * 0.5f * d;
             }
+          } else if (FULL && TRK && (P[4] == 6 || P[4] == 7)) {
+            // plane - cylinder (mjc_PlaneCylinder as oracle/myo_oracle.c states it), one pair lowered as two records: 6 gives the deepest rim
+            // point and the opposite cap's rim point, 7 the two triangle points at 0.8660254 r on the deep cap; both need the deepest point
+            // within the margin
+            const float* n = E + Y.gax + 3 * g1;
+            const float r = sz2[0];
+            float ax[3] = {E[Y.gax + 3 * g2], E[Y.gax + 3 * g2 + 1], E[Y.gax + 3 * g2 + 2]};
+            float prjaxis = dot3(n, ax);
+            if (prjaxis > 0) { ax[0] = -ax[0]; ax[1] = -ax[1]; ax[2] = -ax[2]; prjaxis = -prjaxis; }
+            float vec[3] = {ax[0] * prjaxis - n[0], ax[1] * prjaxis - n[1], ax[2] * prjaxis - n[2]};
+            const float len2 = dot3(vec, vec);
+            if (len2 >= MINVALF) {
+              const float sc = r / sqrtf(len2);
+              vec[0] *= sc; vec[1] *= sc; vec[2] *= sc;
+            } else {   // axis along the normal: any radius
+              float R2[9];
+              geom_world_mat(W, Y, E, g2, R2, brp);
+              vec[0] = R2[0] * r; vec[1] = R2[3] * r; vec[2] = R2[6] * r;
+            }
+            const float prjvec = dot3(vec, n);
+            ax[0] *= sz2[1]; ax[1] *= sz2[1]; ax[2] *= sz2[1];
+            prjaxis *= sz2[1];
+            const float rel[3] = {x2[0] - x1[0], x2[1] - x1[1], x2[2] - x1[2]};
+            const float dist0 = dot3(rel, n), d1 = dist0 + prjaxis + prjvec;
+#pragma unroll
+            for (int k = 0; k < 3; k++) nrm[k] = n[k];
+            if (d1 <= margin) {
+              if (P[4] == 6) {
+                const float d2 = dist0 - prjaxis + prjvec;
+                hit = true; dist = d1;
+#pragma unroll
+                for (int k = 0; k < 3; k++) cpos[k] = x2[k] + vec[k] + ax[k] - n[k] * d1 * 0.5f;
+                if (d2 <= margin) {
+                  hit2 = true; dist2 = d2;
+#pragma unroll
+                  for (int k = 0; k < 3; k++) cpos2[k] = x2[k] + vec[k] - ax[k] - n[k] * d2 * 0.5f;
+                }
+              } else {
+                const float d3 = dist0 + prjaxis - 0.5f * prjvec;
+                if (d3 <= margin) {
+                  float v1[3];
+                  cross3(v1, vec, ax);
+                  normalize3(v1);
+                  const float s3 = r * 0.8660254037844386f;
+                  hit = hit2 = true; dist = dist2 = d3;
+#pragma unroll
+                  for (int k = 0; k < 3; k++) {
+                    const float c = x2[k] + ax[k] - vec[k] * 0.5f - n[k] * d3 * 0.5f;
+                    cpos[k] = c + s3 * v1[k]; cpos2[k] = c - s3 * v1[k];
+                  }
+                }
+              }
+            }
           } else if (FULL && P[4] == 3) {   // plane - ellipsoid (mjc_PlaneConvex): deepest support point along -normal
             const float* n = E + Y.gax + 3 * g1;
             float R2[9], nl[3], sp[3], pw[3];
-            geom_world_mat(W, Y, E, g2, R2);
+            geom_world_mat(W, Y, E, g2, R2, brp);
             matTvec(nl, R2, n);
             float sv[3] = {sz2[0] * nl[0], sz2[1] * nl[1], sz2[2] * nl[2]};
             float nn = norm3(sv), inv = nn > MINVALF ? -1.0f / nn : 0.f;
@@ -1345,15 +1433,15 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
               o1.S[0] = -W.hf.size[3] - cen[2]; o1.S[1] = o1.S[2] = 0.f; o1.h = -1.f;
 #pragma unroll
               for (int k = 0; k < 9; k++) R1[k] = (k == 0 || k == 4 || k == 8) ? 1.f : 0.f;
-              geom_world_mat(W, Y, E, g2, o2.mat);
+              geom_world_mat(W, Y, E, g2, o2.mat, brp);
 #pragma unroll
               for (int k = 0; k < 3; k++) o2.pos[k] = x2[k] - x1[k] - cen[k];
               cobj_shape(o2, Q.t2, sz2);
             } else {
-            geom_world_mat(W, Y, E, g1, R1);
+            geom_world_mat(W, Y, E, g1, R1, brp);
             {
               float R2[9], rel[3] = {x2[0] - x1[0], x2[1] - x1[1], x2[2] - x1[2]};
-              geom_world_mat(W, Y, E, g2, R2);
+              geom_world_mat(W, Y, E, g2, R2, brp);
 #pragma unroll
               for (int i = 0; i < 3; i++)
 #pragma unroll
@@ -1392,11 +1480,11 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
             // MPR in geom1's own frame: obj1 needs no rotation / translation at all (identity frame), obj2 carries the
             // relative pose R1^T R2, R1^T (x2 - x1); normal and position are rotated back afterwards
             float R1[9];
-            geom_world_mat(W, Y, E, g1, R1);
+            geom_world_mat(W, Y, E, g1, R1, brp);
             CObj o1, o2;
             {
               float R2[9], rel[3] = {x2[0] - x1[0], x2[1] - x1[1], x2[2] - x1[2]};
-              geom_world_mat(W, Y, E, g2, R2);
+              geom_world_mat(W, Y, E, g2, R2, brp);
 #pragma unroll
               for (int i = 0; i < 3; i++)
 #pragma unroll
@@ -1425,7 +1513,7 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
               normalize3(dir);
               mpr_hit = true; mpr_n[0] = dir[0]; mpr_n[1] = dir[1]; mpr_n[2] = dir[2];
               float dw[3], pw[3], R1b[9];
-              geom_world_mat(W, Y, E, g1, R1b);   // recomputed (9 LDS reads + a 3x3 product) instead of kept live across the portal refinement
+              geom_world_mat(W, Y, E, g1, R1b, brp);   // recomputed (9 LDS reads + a 3x3 product) instead of kept live across the portal refinement
               matvec(dw, R1b, dir);
               matvec(pw, R1b, pos);
 #pragma unroll

@@ -178,6 +178,16 @@ __device__ __forceinline__ bool reset_body(const DevBatch& Bt, const TaskDev& T,
     const float l = Bt.bpos_range[(size_t)e * 6 + lane], h = Bt.bpos_range[(size_t)e * 6 + 3 + lane];
     if (h > l) Bt.bpos[(size_t)e * 3 + lane] = l + (h - l) * u01(seed ^ 0x5851F42D4C957F2Dull, ge * 8 + lane, 10);
   }
+  if (Bt.bquat_range && lane == 0) {
+    // PenTwirlRandomEnvV0.reset (pen_v0.py:173-184): the target's body_quat = euler2quat(U(-1, 1), U(-1, 1), 0) per episode
+    const float* r = Bt.bquat_range + (size_t)e * 6;
+    if (r[3] > r[0] || r[4] > r[1] || r[5] > r[2]) {
+      float a[3];
+#pragma unroll
+      for (int k = 0; k < 3; k++) a[k] = r[3 + k] > r[k] ? r[k] + (r[3 + k] - r[k]) * u01(seed ^ 0x2545F4914F6CDD1Dull, ge * 8 + k, 11) : r[k];
+      euler2quat(Bt.bquat + (size_t)e * 4, a);
+    }
+  }
   if (T.terrain && Bt.hfield) {
     // TerrainEnvV0.reset (walk_v0.py:563-622): a fresh 100 x 100 elevation grid per episode (in units of the height field's z scale).
     // Distribution parity only for the random draws, as for every reset.

@@ -7,13 +7,13 @@
 #ifndef MYO_TASK_KEYTURN_H
 #define MYO_TASK_KEYTURN_H
 
-// world position (relative to the lowered origin) of site s at the joint positions q of env e.  The site's link chain is walked up to its
-// root; each link's own joint chain, in its parent's frame, is applied to the point on the way (the transform the wave kernel's kinematics
-// phase 1 builds per link).  The per-env offset of MYO_F_BODYPOS moves its root link's origin, as in the TRK step kernel.  Hinge / slide
-// joints only (nq == nv, checked at configure).
-__device__ __forceinline__ void keyturn_site_pos(const DevModel& M, const DevBatch& Bt, const float* q, int e, int s, float* p) {
-  p[0] = M.site_lpos[3 * s]; p[1] = M.site_lpos[3 * s + 1]; p[2] = M.site_lpos[3 * s + 2];
-  for (int l = M.site_link[s]; l >= 0; l = M.link_parent[l]) {
+// world position (relative to the lowered origin) of the point lp of link `link` (-1: the world) at the joint positions q of env e.  The
+// link chain is walked up to its root; each link's own joint chain, in its parent's frame, is applied to the point on the way (the
+// transform the wave kernel's kinematics phase 1 builds per link).  The per-env offset of MYO_F_BODYPOS moves its root link's origin, as in
+// the TRK step kernel.  Hinge / slide joints only (nq == nv, checked at configure).
+__device__ __forceinline__ void link_point_pos(const DevModel& M, const DevBatch& Bt, const float* q, int e, int link, const float* lp, float* p) {
+  p[0] = lp[0]; p[1] = lp[1]; p[2] = lp[2];
+  for (int l = link; l >= 0; l = M.link_parent[l]) {
     float A[9], c[3] = {M.link_pos[3 * l], M.link_pos[3 * l + 1], M.link_pos[3 * l + 2]};
     const float lq[4] = {M.link_quat[4 * l], M.link_quat[4 * l + 1], M.link_quat[4 * l + 2], M.link_quat[4 * l + 3]};
     quat2mat(A, lq);
@@ -49,6 +49,10 @@ __device__ __forceinline__ void keyturn_site_pos(const DevModel& M, const DevBat
     matvec(w, A, p);
     p[0] = w[0] + c[0]; p[1] = w[1] + c[1]; p[2] = w[2] + c[2];
   }
+}
+// ... of site s
+__device__ __forceinline__ void keyturn_site_pos(const DevModel& M, const DevBatch& Bt, const float* q, int e, int s, float* p) {
+  link_point_pos(M, Bt, q, e, M.site_link[s], M.site_lpos + 3 * s, p);
 }
 
 // key_turn_v0.py:82-156 (+ act, base_v0.py:34-38).  Row: hand qpos (nq - 1), hand qvel * dt (nv - 1), key qpos, key qvel * dt, head - index

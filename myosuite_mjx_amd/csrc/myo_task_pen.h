@@ -1,0 +1,107 @@
+// myo_task_pen.h -- PenTwirl{Fixed,Random}EnvV0 (envs/myo/myobase/pen_v0.py) observation / reward / done / solved, MYO_TASK_PEN.
+//
+// The model (myohand_pen) is of the TrackEnv class (the pen's condim-4 pairs), so, as for the key turn, this kernel runs its own forward
+// kinematics of what the task reads, from the post-step qpos: five sites (object top / bottom, target top / bottom, eps_ball) and the
+// object body's origin, one lane each.  The target is world-welded: its sites are static and turn with the per-env orientation of
+// MYO_F_BODYQUAT.  One 64-lane workgroup per env.
+#ifndef MYO_TASK_PEN_H
+#define MYO_TASK_PEN_H
+
+// pen_v0.py:98-170 (+ act, base_v0.py:34-38).  Row: hand qpos (nq - 6), object position (3), object qvel * dt (6), obj_rot (3), obj_des_rot
+// (3), object position - eps_ball (3), obj_rot - obj_des_rot (3), act (na).  T.tip_site = object top, object bottom, target top, target
+// bottom, eps_ball; T.tip_lpos = the object body's origin in the frame of the link of the last dof.
+__device__ __forceinline__ void pen_obs_body(const DevModel& M, const DevBatch& Bt, const TaskDev& T, int obs_only, const int e, const int lane) {
+  const int nv = M.nv, nu = M.nu, nh = nv - 6;
+  const float dt = (float)T.frame_skip * M.timestep;
+  float* o = Bt.obs + (size_t)e * T.obs_dim;
+  const float* q = Bt.qpos + (size_t)e * nv;
+  const float* v = Bt.qvel + (size_t)e * nv;
+  const float* a = Bt.act + (size_t)e * nu;
+  float p[3] = {0.f, 0.f, 0.f};
+  if (lane < 6) {   // lanes 0-4: the sites, 5: the object body's origin
+    const int s = lane < 5 ? T.tip_site[lane] : 0;
+    const int link = lane < 5 ? M.site_link[s] : M.dof_link[nv - 1];
+    link_point_pos(M, Bt, q, e, link, lane < 5 ? M.site_lpos + 3 * s : T.tip_lpos, p);
+    if (Bt.bquat && lane < 5 && link < 0 && Bt.bq_flag[M.ncg + s]) {   // a static site of the per-env oriented body
+      float D[9], w[3];
+      const float* c = Bt.bq_c;
+      const float* bq = Bt.bquat + 4 * (size_t)e;
+      const float qe[4] = {bq[0], bq[1], bq[2], bq[3]};
+      float Rq[9];
+      quat2mat(Rq, qe);
+      matmul3(D, Rq, c);
+      const float d[3] = {p[0] - c[9], p[1] - c[10], p[2] - c[11]};
+      matvec(w, D, d);
+      p[0] = c[9] + w[0]; p[1] = c[10] + w[1]; p[2] = c[11] + w[2];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) p[k] += M.origin[k];
+    if (lane < 5) {
+#pragma unroll
+      for (int k = 0; k < 3; k++) Bt.sitexpos[(size_t)e * 15 + 3 * lane + k] = p[k];
+    }
+  }
+  float x[6][3];
+#pragma unroll
+  for (int i = 0; i < 6; i++)
+#pragma unroll
+    for (int k = 0; k < 3; k++) x[i][k] = __shfl(p[k], i);
+  const int so_t = T.tip_site[0], so_b = T.tip_site[1], st_t = T.tip_site[2], st_b = T.tip_site[3];
+  float lo[3], lt[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) { lo[k] = M.site_lpos[3 * so_t + k] - M.site_lpos[3 * so_b + k]; lt[k] = M.site_lpos[3 * st_t + k] - M.site_lpos[3 * st_b + k]; }
+  const float plen = norm3(lo), tlen = norm3(lt);   // pen_v0.py:73-80: from the model's site_pos (rotation invariant)
+  float rot[3], drot[3], epos[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) { rot[k] = (x[0][k] - x[1][k]) / plen; drot[k] = (x[2][k] - x[3][k]) / tlen; epos[k] = x[5][k] - x[4][k]; }
+  if (lane < 3) {
+    o[nh + lane] = x[5][lane];
+    o[nh + 9 + lane] = rot[lane];
+    o[nh + 12 + lane] = drot[lane];
+    o[nh + 15 + lane] = epos[lane];
+    o[nh + 18 + lane] = rot[lane] - drot[lane];
+  }
+  for (int i = lane; i < nv; i += 64) {
+    if (i < nh) o[i] = q[i];
+    else o[nh + 3 + (i - nh)] = v[i] * dt;
+  }
+  float act2 = 0.f;
+  for (int i = lane; i < nu; i += 64) { const float ai = a[i]; const int sl = M.act_obs[i]; if (sl >= 0) { o[nh + 21 + sl] = ai; act2 += ai * ai; } }
+  if (obs_only) return;
+  const float actn = sqrtf(wave_sum(act2)) / (float)(M.na_obs > 0 ? M.na_obs : 1);
+  if (lane == 0) {
+    const float pos_align = norm3(epos);
+    float np = norm3(rot) * norm3(drot);
+    if (np == 0.f) np = 1.f;                       // vector_math.calculate_cosine
+    const float rot_align = dot3(rot, drot) / np;
+    const bool dropped = pos_align > T.far_th;
+    const float near = pos_align < T.far_th ? 1.f : 0.f;
+    const float bonus = (rot_align > 0.9f ? 1.f : 0.f) * near + 5.f * (rot_align > 0.95f ? 1.f : 0.f) * near;
+    Bt.reward[e] = T.w_pose * (-pos_align) + T.w_reach * rot_align + T.w_act_reg * (-actn) + T.w_penalty * (dropped ? -1.f : 0.f) + T.w_bonus * bonus;
+    Bt.solved[e] = (rot_align > T.pose_thd && !dropped) ? 1.f : 0.f;
+    Bt.done[e] = dropped ? 1.f : 0.f;
+  }
+}
+
+__global__ void __launch_bounds__(64) pen_obs_kernel(DevModel M, DevBatch Bt, TaskDev T, int obs_only, int reset_only) {
+  const int e = blockIdx.x;
+  if (e >= Bt.B) return;
+  if (reset_only && Bt.elapsed[e] != 0) return;    // refresh only the rows of envs an auto-reset just touched
+  pen_obs_body(M, Bt, T, obs_only, e, threadIdx.x);
+}
+
+// myo_bench_rollout's fused epilogue (keyturn_post_kernel's pattern): observation / reward / done of the stepped state, auto-reset, and the
+// first observation of the new episodes, in one launch
+__global__ void __launch_bounds__(64) pen_post_kernel(DevModel M, DevBatch Bt, TaskDev T, int nq, const float* qpos0, uint64_t seed, int env_offset,
+                                                      int auto_max) {
+  const int e = blockIdx.x, lane = threadIdx.x;
+  if (e >= Bt.B) return;
+  pen_obs_body(M, Bt, T, 0, e, lane);
+  __syncthreads();                       // reward / done of this env written (lane 0) before every lane tests them
+  if (reset_body(Bt, T, nq, M.nv, M.nu, qpos0, nullptr, seed, env_offset, auto_max, e, lane)) {
+    __syncthreads();                     // the new state rows (and the target orientation) are complete before they are read back
+    pen_obs_body(M, Bt, T, 1, e, lane);
+  }
+}
+
+#endif  // MYO_TASK_PEN_H

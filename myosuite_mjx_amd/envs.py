@@ -137,6 +137,13 @@ REGISTRY["myoHandKeyTurnFixed-v0"] = dict(
     model="myohand_keyturn", task="keyturn", max_episode_steps=200, frame_skip=10, normalize_act=True, goal_th=3.14, key_init_range=(0.0, 0.0),
     weights=dict(key_turn=1.0, IFtip_approach=10.0, THtip_approach=10.0, act_reg=1.0, bonus=4.0, penalty=25.0))
 REGISTRY["myoHandKeyTurnRandom-v0"] = dict(REGISTRY["myoHandKeyTurnFixed-v0"], goal_th=2 * np.pi, key_init_range=(-np.pi / 2, np.pi / 2))
+# myoHandPenTwirl{Fixed,Random}-v0 (envs/myo/myobase/__init__.py:616-635, pen_v0.py): MyoHand + a free-standing pen (TrackEnv class: its
+# condim-4 pairs).  Palm-up open hand at reset (init_qpos[:-6] = 0, init_qpos[0] = -1.5), pen at qpos0; Random also turns the world-welded
+# target by euler2quat(U(-1, 1), U(-1, 1), 0) at every reset (BatchedMyoEnv.body_quat)
+REGISTRY["myoHandPenTwirlFixed-v0"] = dict(
+    model="myohand_pen", task="pen", max_episode_steps=50, frame_skip=5, normalize_act=True, target_euler_range=None,
+    weights=dict(pos_align=1.0, rot_align=1.0, act_reg=5.0, drop=5.0, bonus=10.0))
+REGISTRY["myoHandPenTwirlRandom-v0"] = dict(REGISTRY["myoHandPenTwirlFixed-v0"], target_euler_range=((-1.0, -1.0, 0.0), (1.0, 1.0, 0.0)))
 # muscle-condition variants (register_env_with_variants, envs/myo/myobase/__init__.py:14-48): myoSarc* (sarcopenia), myoFati* (fatigue)
 # for every myo* id, myoReaf* (EIP -> EPL tendon transfer) for the myoHand* ids
 for _id in [k for k in list(REGISTRY) if k.startswith("myo")]:
@@ -336,6 +343,22 @@ class BatchedMyoEnv:
             self.obs_dim = 2 * m.nq + 6 + m.n_muscle
             if lo_k != hi_k:                                           # key_turn_v0.py:164-167: key_init_pos + U(-0.01, 0.01)^3
                 self.batch.set_body_pos_range(np.full(3, -0.01), np.full(3, 0.01))
+        elif spec["task"] == "pen":
+            # pen_v0.py:60-96: palm-up open hand, pen at qpos0; sites object top / bottom, target top / bottom, eps_ball; the object body's
+            # origin in its link frame.  Random (pen_v0.py:173-184): the target's orientation is re-drawn at every reset
+            init = np.array(m.qpos0, float)
+            init[:-6] = 0.0
+            init[0] = -1.5
+            ob = m.name2id("body", "Object")
+            self.batch.configure(task=capi.TASK_PEN, frame_skip=self.frame_skip, reset_random=0, target_generate=0, init_qpos=init,
+                                 tip_sites=[m.name2id("site", n) for n in ("object_top", "object_bottom", "target_top", "target_bottom", "eps_ball")],
+                                 tip_lpos=tuple(np.asarray(m.hip_body_lpos).reshape(-1, 3)[ob]), pose_thd=0.95, far_th=0.075,
+                                 w_pose=w["pos_align"], w_reach=w["rot_align"], w_act_reg=w["act_reg"], w_bonus=w["bonus"], w_penalty=w["drop"],
+                                 quat_body=m.name2id("body", "target"))
+            self.obs_dim = (m.nq - 6) + 21 + m.n_muscle
+            if spec.get("target_euler_range") is not None:
+                lo, hi = spec["target_euler_range"]
+                self.batch.set_body_quat_range(lo, hi)
         else:
             tips = [m.name2id("site", t) for t in spec["tips"]]
             n = len(tips)
@@ -425,6 +448,21 @@ class BatchedMyoEnv:
             self.view(capi.F_BODYPOS).copy_(self._torch.as_tensor(value, dtype=self._torch.float32).expand(self.num_envs, -1))
         else:
             self.batch.write(capi.F_BODYPOS, np.broadcast_to(np.asarray(value, np.float32), (self.num_envs, 3)))
+
+    # -- per-env body orientation (MYO_F_BODYQUAT) ------------------------------------------------------------
+    @property
+    def body_quat(self):
+        """[num_envs, 4] body_quat (w x y z) of the pen task's target in every env (the batched `sim.model.body_quat[target] = ...` of
+        PenTwirlRandomEnvV0.reset): a torch view of the library's buffer (no copy; writes take effect at the next step / observation).
+        With as_torch=False: a numpy copy (assign the property to write it)."""
+        return self.view(capi.F_BODYQUAT)
+
+    @body_quat.setter
+    def body_quat(self, value):
+        if self.as_torch:
+            self.view(capi.F_BODYQUAT).copy_(self._torch.as_tensor(value, dtype=self._torch.float32).expand(self.num_envs, -1))
+        else:
+            self.batch.write(capi.F_BODYQUAT, np.broadcast_to(np.asarray(value, np.float32), (self.num_envs, 4)))
 
     # -- zero-copy views ---------------------------------------------------------------------------------
     def view(self, field):

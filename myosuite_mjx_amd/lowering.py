@@ -401,16 +401,20 @@ def lower(cm):
             continue
         stat, mov = (g1, g2) if geom_link[g1] < 0 else ((g2, g1) if geom_link[g2] < 0 else (None, None))
         if stat is not None and m.geom_type[stat] in (GEOM_PLANE, GEOM_CYLINDER):
-            c, r = geom_reach(mov)
-            R = geom_lmat[stat].reshape(3, 3)
-            axis = R[:, 2]
-            top = geom_lpos[stat] + (axis * m.geom_size[stat, 1] if m.geom_type[stat] == GEOM_CYLINDER else 0)
-            if np.isfinite(r) and (c - top) @ axis - r > margin:
-                pruned += 1
-                continue
+            # only geoms of the world body itself are pruned: a static geom of a jointless child of the world (myohand_pen's target) keeps
+            # its pairs, so that they stay right in any per-env orientation of that body (MYO_F_BODYQUAT)
+            if m.geom_bodyid[stat] == 0:
+                c, r = geom_reach(mov)
+                R = geom_lmat[stat].reshape(3, 3)
+                axis = R[:, 2]
+                top = geom_lpos[stat] + (axis * m.geom_size[stat, 1] if m.geom_type[stat] == GEOM_CYLINDER else 0)
+                if np.isfinite(r) and (c - top) @ axis - r > margin:
+                    pruned += 1
+                    continue
             # not provably out of reach (e.g. a free object over the scene's floor / pedestal): a plane goes to the analytic plane
-            # narrow phases, a static cylinder to the generic convex one (the kernel's geom frames accept world-fixed geoms)
-            plane_ok = m.geom_type[stat] == GEOM_PLANE and stat == g1 and m.geom_type[mov] in (GEOM_CAPSULE, GEOM_ELLIPSOID, GEOM_MESH)
+            # narrow phases (a moving cylinder: TrackEnv-class models only, checked below), a static cylinder to the generic convex one
+            # (the kernel's geom frames accept world-fixed geoms)
+            plane_ok = m.geom_type[stat] == GEOM_PLANE and stat == g1 and m.geom_type[mov] in (GEOM_CAPSULE, GEOM_ELLIPSOID, GEOM_MESH, GEOM_CYLINDER)
             cyl_ok = m.geom_type[stat] == GEOM_CYLINDER and m.geom_type[mov] in (GEOM_CAPSULE, GEOM_ELLIPSOID, GEOM_SPHERE, GEOM_CYLINDER)
             if not (plane_ok or cyl_ok):
                 raise NotImplementedError(f"HIP path: cannot prune static geom {stat} against moving geom {mov}")
@@ -441,17 +445,20 @@ def lower(cm):
             condim = int(A["pair_condim"][pidx])
         if condim not in (1, 3, 4):
             raise NotImplementedError("HIP path: condim must be 1, 3 or 4")
-        if plane_pair and t2 in (GEOM_BOX, GEOM_SPHERE, GEOM_CYLINDER):
-            raise NotImplementedError("HIP path: plane against a moving box / sphere / cylinder")
+        if plane_pair and t2 in (GEOM_BOX, GEOM_SPHERE):
+            raise NotImplementedError("HIP path: plane against a moving box / sphere")
         b1, b2 = m.geom_bodyid[g1], m.geom_bodyid[g2]
         invw = m.body_invweight0[b1, 0] + m.body_invweight0[b2, 0]
         # narrow-phase type: 1 capsule-capsule (analytic), 2 plane-capsule, 3 plane-ellipsoid, 0 generic convex (MPR)
-        # 5 plane - convex hull (deepest vertex)
+        # 5 plane - convex hull (deepest vertex); 6 and 7 plane - cylinder (mjc_PlaneCylinder, up to four contacts): the pair is lowered as
+        # two records, 6 giving contacts 1-2 (deepest rim point, opposite cap) and 7 contacts 3-4 (the two triangle points), since one
+        # narrow-phase lane produces at most two contacts (TrackEnv-class models only)
         ptype = 1 if (t1 == GEOM_CAPSULE and t2 == GEOM_CAPSULE) else (2 if (plane_pair and t2 == GEOM_CAPSULE) else (
-            5 if (plane_pair and t2 == GEOM_MESH) else (3 if plane_pair else (4 if hfield_pair else 0))))
-        pairs_i.append([cg_index(g1), cg_index(g2), len(pair_dl), len(lst), ptype, condim])
-        pairs_f.append([margin, max(m.geom_gap[g1], m.geom_gap[g2]), fric[0], invw, solref[0], solref[1],
-                        solimp[0], solimp[1], solimp[2], solimp[3], solimp[4], fric[1] if condim >= 4 else 0.0])   # last: torsional coefficient
+            5 if (plane_pair and t2 == GEOM_MESH) else (6 if (plane_pair and t2 == GEOM_CYLINDER) else (3 if plane_pair else (4 if hfield_pair else 0)))))
+        for pt in ((6, 7) if ptype == 6 else (ptype,)):
+            pairs_i.append([cg_index(g1), cg_index(g2), len(pair_dl), len(lst), pt, condim])
+            pairs_f.append([margin, max(m.geom_gap[g1], m.geom_gap[g2]), fric[0], invw, solref[0], solref[1],
+                            solimp[0], solimp[1], solimp[2], solimp[3], solimp[4], fric[1] if condim >= 4 else 0.0])   # last: torsional coefficient
         pair_dl += lst
     cgs = sorted(cg_ids, key=lambda g: cg_ids[g])
     maxkc = max([p[3] for p in pairs_i] + [1])
@@ -704,6 +711,8 @@ def lower(cm):
     A["hip_fl"] = fl
     A["hip_trk"] = np.array([int(any(p[5] >= 4 for p in pairs_i)), int((fl[:, 0] > 0).any()),
                              int(any(m.geom_type[g] in (GEOM_BOX, GEOM_MESH) for g in cgs))], np.int32)
+    if not A["hip_trk"].any() and any(p[4] in (6, 7) for p in pairs_i):
+        raise NotImplementedError("HIP path: plane against a moving cylinder outside the TrackEnv model class")
     A["hip_cg_rbound"] = m.geom_rbound[cgs] if cgs else np.zeros(0)
     A["hip_cg_geom"] = np.array(cgs, np.int32)
     # pair order = candidate order = lane order of the narrow phase, whose 64-lane rounds each cost their slowest lane: the pairs that go

@@ -150,6 +150,28 @@ class Model:
             arrays["hip_link_pos"].reshape(-1, 3)[link] += delta
         return Model(arrays, self.names, self.source)
 
+    def with_body_quat(self, body, quat) -> "Model":
+        """Copy of the model with `body_quat[body] = quat` (`body`: id or name), as PenTwirlRandomEnvV0.reset turns the target
+        (envs/myo/myobase/pen_v0.py:173-184).  World-welded bodies only (no joints, the world as parent): their geoms and sites are static,
+        and the HIP tables are lowered again from the edited arrays."""
+        from .lowering import lower
+        from .mjcf import CompiledModel
+        b = self.body_name2id(body) if isinstance(body, str) else int(body)
+        if not 0 < b < self.nbody:
+            raise ValueError(f"no movable body {body!r}")
+        if int(self.arrays["body_jntnum"][b]) != 0 or int(self.arrays["body_parentid"][b]) != 0:
+            raise NotImplementedError("with_body_quat: only a jointless child of the world")
+        quat = np.asarray(quat, float).reshape(4)
+        if not np.isfinite(quat).all() or abs(np.linalg.norm(quat) - 1) > 1e-6:
+            raise ValueError("body quaternion must be a finite unit quaternion")
+        arrays = {k: np.array(v, copy=True) for k, v in self.arrays.items()}
+        arrays["body_quat"][b] = quat
+        if "hip_cg_link" in arrays:
+            cm = CompiledModel(arrays={k: v for k, v in arrays.items() if not k.startswith("hip_")}, names=self.names)
+            lower(cm)
+            arrays = cm.arrays
+        return Model(arrays, self.names, self.source)
+
     def with_integrator(self, name) -> "Model":
         """Copy of the model with `<option integrator=...>` set: "Euler" (semi-implicit, implicit joint damping) or "RK4" (mj_RungeKutta)."""
         if name not in ("Euler", "RK4"):

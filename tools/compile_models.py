@@ -36,6 +36,7 @@ for _obj in ("alarmclock", "banana", "binoculars", "camera", "coffeemug", "cubel
 # compiled models committed as data fixtures under tests/golden/ (gzip-compressed; model.load_asset finds them there)
 GOLDEN = {
     "myohand_keyturn": "myosuite/envs/myo/assets/hand/myohand_keyturn.xml",   # KeyTurnEnvV0: a box bit and joint friction loss (TrackEnv class)
+    "myohand_pen": "myosuite/envs/myo/assets/hand/myohand_pen.xml",           # PenTwirl*EnvV0: condim-4 pen pairs (TrackEnv class), plane - cylinder
 }
 
 if __name__ == "__main__":

@@ -161,6 +161,18 @@ typedef enum myo_task { MYO_TASK_NONE = 0, MYO_TASK_POSE = 1, MYO_TASK_REACH = 2
                                              pos_align + w_reach rot_align - w_act_reg |act|/na - w_penalty [pos_align > far_th] + w_bonus
                                              ([rot_align > 0.9] + 5 [rot_align > 0.95]) [pos_align < far_th]; done = pos_align > far_th;
                                              solved = rot_align > pose_thd and not done.  ntarget = 0 */
+                        MYO_TASK_BAODING = 9, /* BaodingEnvV1 (envs/myo/myochallenge/baoding_v1.py), models of the TrackEnv class whose
+                                                 last two joints are free joints of root bodies (the balls; nq = nv + 2).  ntip = 4 sites:
+                                                 ball1, ball2, target1, target2 (both targets on one body).  ntarget = 5: the per-env goal
+                                                 row of MYO_F_TARGET = start angle, direction sign (0 hold, -1 CW, +1 CCW), x radius, y radius,
+                                                 period; drawn at every reset as U(target_lo, target_hi) (target_generate = 1), the sign
+                                                 rounded down to an integer.  After env step k the targets sit at angle theta = sign 2 pi
+                                                 (k - 1) dt / period + start (ball 2: theta - pi) on the ellipse (x_r cos, y_r sin) + (-0.0125,
+                                                 -0.07) in their body's frame, the compiled z kept; after a reset, at k = 1.  obs = hand qpos
+                                                 (nq - 14), ball1 position, ball1 linear qvel*dt, ball2 position, ball2 linear qvel*dt, target1,
+                                                 target2, target1 - ball1, target2 - ball2 (no act); MYO_F_SITEXPOS: the four sites (12
+                                                 floats).  reward = -w_pose d1 - w_reach d2; done = a ball site below far_th (drop_th);
+                                                 solved = d1 < pose_thd and d2 < pose_thd (proximity_th) and not done */
                         MYO_TASK_HOLD = 4 /* ObjHoldFixedEnvV0 (envs/myo/myobase/obj_hold_v0.py:13-118): the model's LAST joint is the free
                                              object; obs = hand qpos, hand qvel*dt, object position, goal - object, act; target = goal (3) */
 } myo_task;

@@ -176,6 +176,7 @@ struct TaskDev {
   const float* fatigue_vec;
   int terrain, hf_n;        // terrain walk: myo_terrain kind and cells of the elevation grid re-drawn at reset (0: none)
   float terrain_lo, terrain_hi;
+  float bd_frame[12];       // baoding task, link frame of the targets' body: its x axis (3), y axis (3), origin + z_site axis per target (3 + 3)
 };
 
 // walk task (walk_v0.py:WalkEnvV0): its observation needs a forward pass at the post-step state, which the wave kernel

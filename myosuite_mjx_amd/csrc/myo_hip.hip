@@ -25,6 +25,7 @@
 #include "myo_kernels_aux.h"
 #include "myo_task_keyturn.h"
 #include "myo_task_pen.h"
+#include "myo_task_baoding.h"
 
 // ================================================================================================
 // host side
@@ -72,6 +73,7 @@ struct myo_model {
   // per-env orientation of one world-welded body (MYO_F_BODYQUAT): compiled body tree, poses and the bodies of the collision geoms / sites
   std::vector<int> body_parent, body_jntnum, cg_body, site_body;
   std::vector<double> body_pos0, body_quat0;
+  std::vector<double> site_pos0;   // compiled site_pos (site in its body's frame): the baoding task's moving targets keep its z
 };
 
 struct myo_batch {
@@ -309,7 +311,7 @@ int myo_model_load(const void* blobv, size_t nbytes, int device, myo_model** out
         auto BD = [&](const char* n) { std::vector<double> v; const BlobRec* r = blob_find(blob, n); if (r && r->dtype == 0) { v.resize(r->nbytes / 8); memcpy(v.data(), blob + r->offset, r->nbytes); } return v; };
         const std::vector<int> gb = BI("geom_bodyid");
         m->body_parent = BI("body_parentid"); m->body_jntnum = BI("body_jntnum"); m->site_body = BI("site_bodyid");
-        m->body_pos0 = BD("body_pos"); m->body_quat0 = BD("body_quat");
+        m->body_pos0 = BD("body_pos"); m->body_quat0 = BD("body_quat"); m->site_pos0 = BD("site_pos");
         for (int g : m->cg_geom) m->cg_body.push_back(g >= 0 && g < (int)gb.size() ? gb[g] : -1);
       }
       if (m->trk) {   // the root body of MYO_F_BODYPOS: the body of the last joint, a child of the world at the origin of its own root link
@@ -325,12 +327,15 @@ int myo_model_load(const void* blobv, size_t nbytes, int device, myo_model** out
         }
       }
     }
-    {  // plane - cylinder pairs (lowering.py pair types 6 / 7) have a narrow phase in the TRK instantiation only: never dropped silently
+    {  // plane - cylinder and plane - sphere pairs (lowering.py pair types 6 / 7 and 8) have a narrow phase in the TRK instantiation only: never
+       // dropped silently
       std::vector<int> pi2;
       const int* t3;
       if ((rc = load_i(m, blob, "hip_pair_i", &t3, &pi2))) { myo_model_free(m); return rc; }
-      for (int p = 0; p < d.npair; p++)
+      for (int p = 0; p < d.npair; p++) {
         if ((pi2[6 * p + 4] == 6 || pi2[6 * p + 4] == 7) && !m->trk) { myo_model_free(m); return fail(MYO_E_UNSUPPORTED, "plane - cylinder pairs need a model of the TrackEnv class"); }
+        if (pi2[6 * p + 4] == 8 && !m->trk) { myo_model_free(m); return fail(MYO_E_UNSUPPORTED, "plane - sphere pairs need a model of the TrackEnv class"); }
+      }
     }
     {  // self-contained per-lane records (DevModelW::seg_rec, dl_pk, ...): denormalised copies of the tables loaded above
       auto BI = [&](const char* n) { std::vector<int> v; const BlobRec* r = blob_find(blob, n); if (r && r->dtype == 1) { v.resize(r->nbytes / 4); memcpy(v.data(), blob + r->offset, r->nbytes); } return v; };
@@ -637,6 +642,7 @@ void myo_batch_free(myo_batch* b) {
 int myo_batch_size(const myo_batch* b) { return b ? b->db.B : 0; }
 
 static int set_quat_body(myo_batch* b, int body);   // (below, with the rest of MYO_F_BODYQUAT)
+static void quat2mat_d(double* R, const double* q);
 
 int myo_batch_configure(myo_batch* b, const myo_task_config* c) {
   if (!b || !c) return fail(MYO_E_ARG, "myo_batch_configure: null");
@@ -701,6 +707,40 @@ int myo_batch_configure(myo_batch* b, const myo_task_config* c) {
     for (int k = 0; k < 3; k++) if (!std::isfinite(c->tip_lpos[k])) return fail(MYO_E_ARG, "pen task: tip_lpos must be finite");
     if (!(c->far_th > 0.f) || !(c->pose_thd == c->pose_thd)) return fail(MYO_E_ARG, "pen task: far_th > 0, pose_thd a number");
     T.obs_dim = (nv - 6) + 21 + dm.na_obs;
+  }
+  else if (c->task == MYO_TASK_BAODING) {
+    // baoding_v1.py: the balls are the model's last two joints, free joints of root bodies (qpos[-14:-7], qpos[-7:]); sites = ball1, ball2,
+    // target1, target2.  The targets move in the frame of their body (baoding_v1.py:147-181: site_pos), which lowering folds into its link:
+    // T.bd_frame carries that body's x and y axes and, per target, the body origin lifted by the site's compiled z, in the link frame
+    const myo_model* m = b->model;
+    if (!(m->wave_ok && m->trk) || m->nq != nv + 2 || nv < 13) return fail(MYO_E_UNSUPPORTED, "baoding task: a TrackEnv-class model whose last two joints are free joints (the balls)");
+    std::vector<int> dlink(12), lpar(2), ldn(2);
+    HIPCHK(hipMemcpy(dlink.data(), dm.dof_link + (nv - 12), 48, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 2; k++) {
+      HIPCHK(hipMemcpy(lpar.data() + k, dm.link_parent + dlink[6 * k], 4, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(ldn.data() + k, dm.link_dofnum + dlink[6 * k], 4, hipMemcpyDeviceToHost));
+    }
+    bool ok = dlink[0] != dlink[6] && lpar[0] < 0 && lpar[1] < 0 && ldn[0] == 6 && ldn[1] == 6;
+    for (int k = 0; k < 12; k++) ok = ok && dlink[k] == dlink[k < 6 ? 0 : 6];
+    if (!ok) return fail(MYO_E_UNSUPPORTED, "baoding task: the last twelve dofs must be two free joints of root bodies");
+    if (c->ntip != 4 || c->ntarget != 5) return fail(MYO_E_ARG, "baoding task: ntip = 4 (ball1, ball2, target1, target2) and ntarget = 5 (goal parameters)");
+    for (int k = 0; k < 4; k++) if (c->tip_site[k] < 0 || c->tip_site[k] >= m->dims.nsite) return fail(MYO_E_ARG, "baoding task: site id out of range");
+    std::vector<int> slink(4);
+    for (int k = 0; k < 4; k++) HIPCHK(hipMemcpy(slink.data() + k, dm.site_link + c->tip_site[k], 4, hipMemcpyDeviceToHost));
+    const int tb = m->site_body[c->tip_site[2]];
+    if (slink[0] != dlink[0] || slink[1] != dlink[6] || tb != m->site_body[c->tip_site[3]] || slink[2] < 0 || m->body_link[tb] != slink[2])
+      return fail(MYO_E_UNSUPPORTED, "baoding task: the ball sites must be on the balls, both target sites on one moving body");
+    if (!(c->far_th == c->far_th) || !(c->pose_thd == c->pose_thd)) return fail(MYO_E_ARG, "baoding task: far_th (drop_th) and pose_thd (proximity_th) numbers");
+    const float* bq = &m->body_lquat[4 * (size_t)tb];
+    const double qd[4] = {bq[0], bq[1], bq[2], bq[3]};
+    double R[9];
+    quat2mat_d(R, qd);
+    for (int k = 0; k < 3; k++) { T.bd_frame[k] = (float)R[3 * k]; T.bd_frame[3 + k] = (float)R[3 * k + 1]; }
+    for (int t = 0; t < 2; t++) {
+      const double z = m->site_pos0[3 * (size_t)c->tip_site[2 + t] + 2];
+      for (int k = 0; k < 3; k++) T.bd_frame[6 + 3 * t + k] = (float)(m->body_lpos[3 * (size_t)tb + k] + R[3 * k + 2] * z);
+    }
+    T.obs_dim = (nv - 12) + 24;
   }
   else if (c->task == MYO_TASK_HOLD) {
     if (c->ntarget != 3) return fail(MYO_E_ARG, "hold task: ntarget must be 3 (goal position)");
@@ -1306,6 +1346,8 @@ static int launch_obs(myo_batch* b, hipStream_t s, int obs_only = 0, int reset_o
     hipLaunchKernelGGL(keyturn_obs_kernel, dim3(B), dim3(64), 0, s, m->dm, b->db, b->task, obs_only, reset_only);
   } else if (b->task.task == MYO_TASK_PEN) {
     hipLaunchKernelGGL(pen_obs_kernel, dim3(B), dim3(64), 0, s, m->dm, b->db, b->task, obs_only, reset_only);
+  } else if (b->task.task == MYO_TASK_BAODING) {
+    hipLaunchKernelGGL(baoding_obs_kernel, dim3(B), dim3(64), 0, s, m->dm, b->db, b->task, obs_only, reset_only);
   } else if (b->task.task == MYO_TASK_REACH) {
     const int EPW = 4;
     hipLaunchKernelGGL(reach_obs_kernel<16>, dim3((B + EPW - 1) / EPW), dim3(64), (size_t)EPW * m->env_lds_bytes, s, m->dm, b->db, b->task, obs_only);
@@ -1426,6 +1468,11 @@ int myo_bench_rollout(myo_batch* b, int steps, int nsubsteps, uint64_t seed, int
     }
     if ((mode & MYO_BENCH_OBS) && (mode & MYO_BENCH_AUTORESET) && max_episode_steps > 0 && tk == MYO_TASK_PEN) {       // ... and the pen task
       hipLaunchKernelGGL(pen_post_kernel, dim3(b->db.B), dim3(64), 0, s, b->model->dm, b->db, b->task, b->model->nq, b->model->dm.qpos0, seed, b->env_offset, max_episode_steps);
+      HIPCHK(hipGetLastError());
+      continue;
+    }
+    if ((mode & MYO_BENCH_OBS) && (mode & MYO_BENCH_AUTORESET) && max_episode_steps > 0 && tk == MYO_TASK_BAODING) {   // ... and the baoding task
+      hipLaunchKernelGGL(baoding_post_kernel, dim3(b->db.B), dim3(64), 0, s, b->model->dm, b->db, b->task, b->model->nq, b->model->dm.qpos0, seed, b->env_offset, max_episode_steps);
       HIPCHK(hipGetLastError());
       continue;
     }

@@ -1396,6 +1396,18 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
                 }
               }
             }
+          } else if (FULL && TRK && P[4] == 8) {   // plane - sphere (mjc_PlaneSphere): the sphere's lowest point along -normal (one contact)
+            const float* n = E + Y.gax + 3 * g1;
+            const float r = sz2[0];
+            const float rel[3] = {x2[0] - x1[0], x2[1] - x1[1], x2[2] - x1[2]};
+            const float d = dot3(rel, n) - r;
+#pragma unroll
+            for (int k = 0; k < 3; k++) nrm[k] = n[k];
+            if (d <= margin) {
+              hit = true; dist = d;
+#pragma unroll
+              for (int k = 0; k < 3; k++) cpos[k] = x2[k] - n[k] * (r + 0.5f * d);
+            }
           } else if (FULL && P[4] == 3) {   // plane - ellipsoid (mjc_PlaneConvex): deepest support point along -normal
             const float* n = E + Y.gax + 3 * g1;
             float R2[9], nl[3], sp[3], pw[3];

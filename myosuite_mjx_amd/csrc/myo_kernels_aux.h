@@ -155,7 +155,9 @@ __device__ __forceinline__ bool reset_body(const DevBatch& Bt, const TaskDev& T,
   }
   for (int i = lane; i < T.ntarget; i += 64) {
     float lo = T.target_lo[i], hi = T.target_hi[i];
-    Bt.target[(size_t)e * T.ntarget + i] = T.target_generate ? lo + (hi - lo) * u01(seed, ge * 4096 + 2048 + i, 2) : lo;
+    float t = T.target_generate ? lo + (hi - lo) * u01(seed, ge * 4096 + 2048 + i, 2) : lo;
+    if (T.task == MYO_TASK_BAODING && i == 1) t = fminf(floorf(t), hi);   // the direction sign: U(-1, 2) rounded down, one of -1, 0, +1
+    Bt.target[(size_t)e * T.ntarget + i] = t;
   }
   if (T.gsize_type && Bt.gsize && lane == 0) {
     // ObjHoldRandomEnvV0.reset (obj_hold_v0.py:133-139): a fresh size for the object's geom per episode (its mass and inertia stay)

@@ -1,0 +1,98 @@
+// myo_task_baoding.h -- BaodingEnvV1 (envs/myo/myochallenge/baoding_v1.py) observation / reward / done / solved, MYO_TASK_BAODING.
+//
+// The model (myohand_baoding) is of the TrackEnv class (the balls' condim-4 pairs), so, as for the key turn and the pen, this kernel runs
+// its own forward kinematics of what the task reads, from the post-step qpos: the two ball sites (free joints: pose straight from qpos)
+// and the two moving targets, one lane each.  The targets follow the reference's goal trajectory analytically: env step k (MYO_F_ELAPSED)
+// uses goal[k - 1], so no per-step host work is needed.  One 64-lane workgroup per env.
+#ifndef MYO_TASK_BAODING_H
+#define MYO_TASK_BAODING_H
+
+// baoding_v1.py:147-246.  Row: hand qpos (nq - 14), ball1 position, ball1 linear qvel * dt, ball2 position, ball2 linear qvel * dt, target1,
+// target2, target1 - ball1, target2 - ball2 (47 floats for myohand_baoding; act is not observed).  T.tip_site = ball1, ball2, target1,
+// target2; Bt.target row = start angle, sign, x radius, y radius, period.
+__device__ __forceinline__ void baoding_obs_body(const DevModel& M, const DevBatch& Bt, const TaskDev& T, int obs_only, const int e, const int lane) {
+  const int nv = M.nv, nq = nv + 2, nh = nv - 12;
+  const float dt = (float)T.frame_skip * M.timestep;
+  float* o = Bt.obs + (size_t)e * T.obs_dim;
+  const float* q = Bt.qpos + (size_t)e * nq;
+  const float* v = Bt.qvel + (size_t)e * nv;
+  float p[3] = {0.f, 0.f, 0.f};
+  if (lane < 4) {
+    const int s = T.tip_site[lane];
+    if (lane < 2) {   // ball site: its free joint's position + R(quat) site_lpos
+      const float* qb = q + nh + 7 * lane;
+      float qq[4] = {qb[3], qb[4], qb[5], qb[6]}, R[9], w[3];
+      const float qn = 1.0f / sqrtf(qq[0] * qq[0] + qq[1] * qq[1] + qq[2] * qq[2] + qq[3] * qq[3]);
+      qq[0] *= qn; qq[1] *= qn; qq[2] *= qn; qq[3] *= qn;
+      quat2mat(R, qq);
+      matvec(w, R, M.site_lpos + 3 * s);
+      p[0] = qb[0] + w[0]; p[1] = qb[1] + w[1]; p[2] = qb[2] + w[2];
+    } else {          // target: the goal point goal[k - 1] on its ellipse, in the targets' body frame, carried to the world
+      const float* g = Bt.target + (size_t)e * 5;
+      const int k = max(Bt.elapsed[e] - 1, 0);
+      const float ang = g[1] * 6.283185307179586f * ((float)k * dt / g[4]) + g[0] - (lane == 3 ? 3.141592653589793f : 0.f);
+      float sn, cs;
+      sincosf(ang, &sn, &cs);
+      const float X = g[2] * cs - 0.0125f, Yc = g[3] * sn - 0.07f;
+      const float* F = T.bd_frame;
+      float lp[3];
+#pragma unroll
+      for (int c = 0; c < 3; c++) lp[c] = F[6 + 3 * (lane - 2) + c] + F[c] * X + F[3 + c] * Yc;
+      link_point_pos(M, Bt, q, e, M.site_link[s], lp, p);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) p[c] += M.origin[c];
+#pragma unroll
+    for (int c = 0; c < 3; c++) Bt.sitexpos[(size_t)e * 12 + 3 * lane + c] = p[c];
+  }
+  float x[4][3];
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+#pragma unroll
+    for (int c = 0; c < 3; c++) x[i][c] = __shfl(p[c], i);
+  if (lane < 3) {
+    o[nh + lane] = x[0][lane];
+    o[nh + 3 + lane] = v[nh + lane] * dt;
+    o[nh + 6 + lane] = x[1][lane];
+    o[nh + 9 + lane] = v[nh + 6 + lane] * dt;
+    o[nh + 12 + lane] = x[2][lane];
+    o[nh + 15 + lane] = x[3][lane];
+    o[nh + 18 + lane] = x[2][lane] - x[0][lane];
+    o[nh + 21 + lane] = x[3][lane] - x[1][lane];
+  }
+  for (int i = lane; i < nh; i += 64) o[i] = q[i];
+  if (obs_only) return;
+  if (lane == 0) {
+    float d1[3], d2[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) { d1[c] = x[2][c] - x[0][c]; d2[c] = x[3][c] - x[1][c]; }
+    const float n1 = norm3(d1), n2 = norm3(d2);
+    const bool fall = x[0][2] < T.far_th || x[1][2] < T.far_th;
+    Bt.reward[e] = T.w_pose * (-n1) + T.w_reach * (-n2);
+    Bt.solved[e] = (n1 < T.pose_thd && n2 < T.pose_thd && !fall) ? 1.f : 0.f;
+    Bt.done[e] = fall ? 1.f : 0.f;
+  }
+}
+
+__global__ void __launch_bounds__(64) baoding_obs_kernel(DevModel M, DevBatch Bt, TaskDev T, int obs_only, int reset_only) {
+  const int e = blockIdx.x;
+  if (e >= Bt.B) return;
+  if (reset_only && Bt.elapsed[e] != 0) return;    // refresh only the rows of envs an auto-reset just touched
+  baoding_obs_body(M, Bt, T, obs_only, e, threadIdx.x);
+}
+
+// myo_bench_rollout's fused epilogue (keyturn_post_kernel's pattern): observation / reward / done of the stepped state, auto-reset, and the
+// first observation of the new episodes, in one launch
+__global__ void __launch_bounds__(64) baoding_post_kernel(DevModel M, DevBatch Bt, TaskDev T, int nq, const float* qpos0, uint64_t seed, int env_offset,
+                                                          int auto_max) {
+  const int e = blockIdx.x, lane = threadIdx.x;
+  if (e >= Bt.B) return;
+  baoding_obs_body(M, Bt, T, 0, e, lane);
+  __syncthreads();                       // reward / done of this env written (lane 0) before every lane tests them
+  if (reset_body(Bt, T, nq, M.nv, M.nu, qpos0, nullptr, seed, env_offset, auto_max, e, lane)) {
+    __syncthreads();                     // the new state rows and goal parameters are complete before they are read back
+    baoding_obs_body(M, Bt, T, 1, e, lane);
+  }
+}
+
+#endif  // MYO_TASK_BAODING_H

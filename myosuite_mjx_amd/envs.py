@@ -144,6 +144,13 @@ REGISTRY["myoHandPenTwirlFixed-v0"] = dict(
     model="myohand_pen", task="pen", max_episode_steps=50, frame_skip=5, normalize_act=True, target_euler_range=None,
     weights=dict(pos_align=1.0, rot_align=1.0, act_reg=5.0, drop=5.0, bonus=10.0))
 REGISTRY["myoHandPenTwirlRandom-v0"] = dict(REGISTRY["myoHandPenTwirlFixed-v0"], target_euler_range=((-1.0, -1.0, 0.0), (1.0, 1.0, 0.0)))
+# myoChallengeBaodingP1-v1 (envs/myo/myochallenge/__init__.py:355-370, baoding_v1.py): MyoHand + two free balls (TrackEnv class: the balls'
+# condim-4 pairs).  Palm-up open hand at reset (init_qpos[:-14] = 0, init_qpos[0] = -1.57), balls at qpos0; the two targets circle the palm
+# (goal parameters per env: start angle, direction sign, x / y radius, period, re-drawn at every reset; BatchedMyoEnv.goal_params)
+REGISTRY["myoChallengeBaodingP1-v1"] = dict(
+    model="myohand_baoding", task="baoding", max_episode_steps=200, frame_skip=10, normalize_act=True, task_choice="fixed",
+    goal_time_period=(5, 5), goal_xrange=(0.025, 0.025), goal_yrange=(0.028, 0.028), drop_th=1.25, proximity_th=0.015,
+    weights=dict(pos_dist_1=5.0, pos_dist_2=5.0))
 # muscle-condition variants (register_env_with_variants, envs/myo/myobase/__init__.py:14-48): myoSarc* (sarcopenia), myoFati* (fatigue)
 # for every myo* id, myoReaf* (EIP -> EPL tendon transfer) for the myoHand* ids
 for _id in [k for k in list(REGISTRY) if k.startswith("myo")]:
@@ -185,6 +192,10 @@ UNSUPPORTED = {
     # (nothing of the walk family: the terrain envs run on the height-field instantiation of the leg kernel)
     "myoElbowPose1D6MExoRandom-v0": "re-draws the mass of body carry_weight per episode (a per-env model edit)",
 }
+# myoChallengeBaodingP2-v1 (envs/myo/myochallenge/__init__.py:372-389) and its muscle-condition variants (the challenge registry has no Reaf one)
+for _id in ("myoChallengeBaodingP2-v1", "myoSarcChallengeBaodingP2-v1", "myoFatiChallengeBaodingP2-v1"):
+    UNSUPPORTED[_id] = ("re-draws the balls' size, mass and friction per episode (obj_size_range, obj_mass_range, obj_friction_change): "
+                        "the TrackEnv-class step kernel has no per-env ball size, mass or friction")
 
 
 class Box:
@@ -219,9 +230,12 @@ class BatchedMyoEnv:
 
     # env kwargs of the reference that gym.make forwards to the env class and that are honoured here (others raise)
     ENV_KWARGS = ("reset_type", "fatigue_reset_random", "fatigue_reset_vec", "weight_bodyname", "weight_range", "target_jnt_range",
-                  "goal_th", "key_init_range")
+                  "goal_th", "key_init_range", "task_choice", "goal_time_period", "goal_xrange", "goal_yrange", "drop_th", "proximity_th")
     POSE_KWARGS = ("weight_bodyname", "weight_range", "target_jnt_range")   # PoseEnvV0 kwargs (pose_v0.py:56-75): pose tasks only
     KEYTURN_KWARGS = ("goal_th", "key_init_range")                           # KeyTurnEnvV0._setup kwargs (key_turn_v0.py:54-61): key turn only
+    # BaodingEnvV1._setup kwargs (baoding_v1.py:54-69): baoding only; its per-env ball size / mass / friction kwargs are refused
+    BAODING_KWARGS = ("task_choice", "goal_time_period", "goal_xrange", "goal_yrange", "drop_th", "proximity_th")
+    BAODING_REFUSED = ("obj_size_range", "obj_mass_range", "obj_friction_change")
 
     def __init__(self, env_id, num_envs=1, device=0, seed=0, env_offset=0, autoreset=True, as_torch=True, **env_kwargs):
         if env_id in UNSUPPORTED:
@@ -231,9 +245,15 @@ class BatchedMyoEnv:
         self.id = env_id
         self.spec = spec = dict(REGISTRY[env_id])
         for k, v in env_kwargs.items():
-            if k not in self.ENV_KWARGS or (k in self.POSE_KWARGS and spec.get("task") != "pose") or (k in self.KEYTURN_KWARGS and spec.get("task") != "keyturn"):
+            if k in self.BAODING_REFUSED and spec.get("task") == "baoding" and v is not None:
+                raise NotImplementedError(f"{env_id}: {k} re-draws the balls' size, mass or friction per episode; the TrackEnv-class step "
+                                          "kernel has no per-env ball size, mass or friction")
+            if k in self.BAODING_REFUSED and spec.get("task") == "baoding":
+                continue
+            if k not in self.ENV_KWARGS or (k in self.POSE_KWARGS and spec.get("task") != "pose") or (k in self.KEYTURN_KWARGS and spec.get("task") != "keyturn") or (
+                    k in self.BAODING_KWARGS and spec.get("task") != "baoding"):
                 raise TypeError(f"{env_id}: unsupported env kwarg {k!r} (supported: {self.ENV_KWARGS}; {self.POSE_KWARGS} for pose tasks only, "
-                                f"{self.KEYTURN_KWARGS} for the key-turn task only)")
+                                f"{self.KEYTURN_KWARGS} for the key-turn task only, {self.BAODING_KWARGS} for the baoding task only)")
             spec[k] = v
         self.num_envs = int(num_envs)
         self.device = device
@@ -359,6 +379,25 @@ class BatchedMyoEnv:
             if spec.get("target_euler_range") is not None:
                 lo, hi = spec["target_euler_range"]
                 self.batch.set_body_quat_range(lo, hi)
+        elif spec["task"] == "baoding":
+            # baoding_v1.py:54-145, 325-383: palm-up open hand, balls at qpos0; sites ball1, ball2, target1, target2.  Goal parameters per env
+            # (MYO_F_TARGET row: start angle, sign, x radius, y radius, period) ~ U(lo, hi) at every reset: "fixed" is BAODING_CCW from pi / 4,
+            # "random" draws the direction from HOLD / CW / CCW (the sign U(-1, 2) rounded down) and the start angle from U(0, 2 pi)
+            init = np.array(m.qpos0, float)
+            init[:-14] = 0.0
+            init[0] = -1.57
+            if spec["task_choice"] not in ("fixed", "random"):
+                raise ValueError(f"{env_id}: task_choice must be 'fixed' or 'random'")
+            rnd = spec["task_choice"] == "random"
+            (p0, p1), (x0, x1), (y0, y1) = ((float(a) for a in spec[k]) for k in ("goal_time_period", "goal_xrange", "goal_yrange"))
+            if not (0 < p0 <= p1 and x0 <= x1 and y0 <= y1):
+                raise ValueError(f"{env_id}: goal_time_period, goal_xrange and goal_yrange must be (lo, hi) with lo <= hi (periods > 0)")
+            glo = [0.0 if rnd else np.pi / 4, -1.0 if rnd else 1.0, x0, y0, p0]
+            ghi = [2 * np.pi if rnd else np.pi / 4, 2.0 if rnd else 1.0, x1, y1, p1]
+            self.batch.configure(task=capi.TASK_BAODING, frame_skip=self.frame_skip, reset_random=0, target_generate=1, target_lo=glo, target_hi=ghi,
+                                 init_qpos=init, tip_sites=[m.name2id("site", n) for n in ("ball1_site", "ball2_site", "target1_site", "target2_site")],
+                                 pose_thd=float(spec["proximity_th"]), far_th=float(spec["drop_th"]), w_pose=w["pos_dist_1"], w_reach=w["pos_dist_2"])
+            self.obs_dim = (m.nq - 14) + 24
         else:
             tips = [m.name2id("site", t) for t in spec["tips"]]
             n = len(tips)
@@ -463,6 +502,26 @@ class BatchedMyoEnv:
             self.view(capi.F_BODYQUAT).copy_(self._torch.as_tensor(value, dtype=self._torch.float32).expand(self.num_envs, -1))
         else:
             self.batch.write(capi.F_BODYQUAT, np.broadcast_to(np.asarray(value, np.float32), (self.num_envs, 4)))
+
+    # -- per-env goal parameters of the baoding task (MYO_F_TARGET) ------------------------------------------
+    @property
+    def goal_params(self):
+        """[num_envs, 5] goal parameters of the baoding task in every env: start angle, direction sign (0 hold, -1 CW, +1 CCW), x radius, y
+        radius, period (BaodingEnvV1's ball_1_starting_angle, which_task, x_radius, y_radius, time_period).  A torch view of the library's
+        buffer (no copy; writes move the targets from the next observation on, until the env's next reset re-draws them).  With
+        as_torch=False: a numpy copy (assign the property to write it)."""
+        if self.spec["task"] != "baoding":
+            raise AttributeError("goal_params: baoding task only")
+        return self.view(capi.F_TARGET)
+
+    @goal_params.setter
+    def goal_params(self, value):
+        if self.spec["task"] != "baoding":
+            raise AttributeError("goal_params: baoding task only")
+        if self.as_torch:
+            self.view(capi.F_TARGET).copy_(self._torch.as_tensor(value, dtype=self._torch.float32).expand(self.num_envs, -1))
+        else:
+            self.batch.write(capi.F_TARGET, np.broadcast_to(np.asarray(value, np.float32), (self.num_envs, 5)))
 
     # -- zero-copy views ---------------------------------------------------------------------------------
     def view(self, field):

@@ -76,8 +76,8 @@ def lower(cm):
     for j in range(len(m.jnt_type)):
         if m.jnt_type[j] == JNT_FREE:
             b = m.jnt_bodyid[j]
-            if m.body_parentid[b] != 0 or m.body_jntnum[b] != 1 or has_free:
-                raise NotImplementedError("HIP path: a free joint must be the only joint of a single root body")
+            if m.body_parentid[b] != 0 or m.body_jntnum[b] != 1:
+                raise NotImplementedError("HIP path: a free joint must be the only joint of a root body")
             has_free = True
         elif m.jnt_type[j] not in (JNT_HINGE, JNT_SLIDE):
             raise NotImplementedError("HIP path: ball joints")
@@ -414,7 +414,8 @@ def lower(cm):
             # not provably out of reach (e.g. a free object over the scene's floor / pedestal): a plane goes to the analytic plane
             # narrow phases (a moving cylinder: TrackEnv-class models only, checked below), a static cylinder to the generic convex one
             # (the kernel's geom frames accept world-fixed geoms)
-            plane_ok = m.geom_type[stat] == GEOM_PLANE and stat == g1 and m.geom_type[mov] in (GEOM_CAPSULE, GEOM_ELLIPSOID, GEOM_MESH, GEOM_CYLINDER)
+            plane_ok = m.geom_type[stat] == GEOM_PLANE and stat == g1 and m.geom_type[mov] in (GEOM_CAPSULE, GEOM_ELLIPSOID, GEOM_MESH, GEOM_CYLINDER,
+                                                                                          GEOM_SPHERE)
             cyl_ok = m.geom_type[stat] == GEOM_CYLINDER and m.geom_type[mov] in (GEOM_CAPSULE, GEOM_ELLIPSOID, GEOM_SPHERE, GEOM_CYLINDER)
             if not (plane_ok or cyl_ok):
                 raise NotImplementedError(f"HIP path: cannot prune static geom {stat} against moving geom {mov}")
@@ -445,16 +446,18 @@ def lower(cm):
             condim = int(A["pair_condim"][pidx])
         if condim not in (1, 3, 4):
             raise NotImplementedError("HIP path: condim must be 1, 3 or 4")
-        if plane_pair and t2 in (GEOM_BOX, GEOM_SPHERE):
-            raise NotImplementedError("HIP path: plane against a moving box / sphere")
+        if plane_pair and t2 == GEOM_BOX:
+            raise NotImplementedError("HIP path: plane against a moving box")
         b1, b2 = m.geom_bodyid[g1], m.geom_bodyid[g2]
         invw = m.body_invweight0[b1, 0] + m.body_invweight0[b2, 0]
         # narrow-phase type: 1 capsule-capsule (analytic), 2 plane-capsule, 3 plane-ellipsoid, 0 generic convex (MPR)
         # 5 plane - convex hull (deepest vertex); 6 and 7 plane - cylinder (mjc_PlaneCylinder, up to four contacts): the pair is lowered as
         # two records, 6 giving contacts 1-2 (deepest rim point, opposite cap) and 7 contacts 3-4 (the two triangle points), since one
-        # narrow-phase lane produces at most two contacts (TrackEnv-class models only)
+        # narrow-phase lane produces at most two contacts (TrackEnv-class models only); 8 plane - sphere (mjc_PlaneSphere, one contact; the
+        # sphere's geom_size is [r, 0, 0], so it cannot go to the plane - ellipsoid type; TrackEnv-class models only)
         ptype = 1 if (t1 == GEOM_CAPSULE and t2 == GEOM_CAPSULE) else (2 if (plane_pair and t2 == GEOM_CAPSULE) else (
-            5 if (plane_pair and t2 == GEOM_MESH) else (6 if (plane_pair and t2 == GEOM_CYLINDER) else (3 if plane_pair else (4 if hfield_pair else 0)))))
+            5 if (plane_pair and t2 == GEOM_MESH) else (6 if (plane_pair and t2 == GEOM_CYLINDER) else (8 if (plane_pair and t2 == GEOM_SPHERE) else (
+                3 if plane_pair else (4 if hfield_pair else 0))))))
         for pt in ((6, 7) if ptype == 6 else (ptype,)):
             pairs_i.append([cg_index(g1), cg_index(g2), len(pair_dl), len(lst), pt, condim])
             pairs_f.append([margin, max(m.geom_gap[g1], m.geom_gap[g2]), fric[0], invw, solref[0], solref[1],
@@ -713,6 +716,8 @@ def lower(cm):
                              int(any(m.geom_type[g] in (GEOM_BOX, GEOM_MESH) for g in cgs))], np.int32)
     if not A["hip_trk"].any() and any(p[4] in (6, 7) for p in pairs_i):
         raise NotImplementedError("HIP path: plane against a moving cylinder outside the TrackEnv model class")
+    if not A["hip_trk"].any() and any(p[4] == 8 for p in pairs_i):
+        raise NotImplementedError("HIP path: plane against a moving sphere outside the TrackEnv model class")
     A["hip_cg_rbound"] = m.geom_rbound[cgs] if cgs else np.zeros(0)
     A["hip_cg_geom"] = np.array(cgs, np.int32)
     # pair order = candidate order = lane order of the narrow phase, whose 64-lane rounds each cost their slowest lane: the pairs that go

@@ -37,6 +37,7 @@ for _obj in ("alarmclock", "banana", "binoculars", "camera", "coffeemug", "cubel
 GOLDEN = {
     "myohand_keyturn": "myosuite/envs/myo/assets/hand/myohand_keyturn.xml",   # KeyTurnEnvV0: a box bit and joint friction loss (TrackEnv class)
     "myohand_pen": "myosuite/envs/myo/assets/hand/myohand_pen.xml",           # PenTwirl*EnvV0: condim-4 pen pairs (TrackEnv class), plane - cylinder
+    "myohand_baoding": "myosuite/envs/myo/assets/hand/myohand_baoding.xml",   # BaodingEnvV1: two free balls (TrackEnv class), plane - sphere
 }
 
 if __name__ == "__main__":

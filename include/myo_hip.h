@@ -253,6 +253,18 @@ typedef struct myo_track_config {
   int max_episode_steps;                   /* gym TimeLimit of the registered MyoDM ids (envs/myo/myodm/__init__.py:571,649; 0: none): MYO_F_SOLVED = 1 when the
                                               episode is truncated by it (and not done); with `autoreset` such envs are reset as well */
   uint64_t seed;                           /* RANDOM references: draws keyed by (seed, global env id, env step) */
+  int flavour;                             /* 0: the MJX TrackEnv above (default).  1: the classic gym TrackEnv (envs/myo/myodm/myodm_v0.py), the
+                                              entry point of the registered MyoDM ids: an env step is myo_step(action, MYO_ACTMAP_MUSCLE_SIGMOID,
+                                              n_frames = 10) then myo_obs (MYO_ACTMAP_CTRLRANGE is refused with MYO_E_ARG).  myo_obs /
+                                              myo_obs_reset_only write qpos, qvel, hand_qpos_err, hand_qvel_err (robot_dim entries, or one 0
+                                              without ref_robot_vel), obj_com_err (3), act (na) -- nq + nv + 2 robot_dim + 3 + na floats, or
+                                              nq + nv + robot_dim + 4 + na -- with the reference looked up at t = elapsed * n_frames * timestep +
+                                              motion_start_time (t = 0 after a reset) and the body frames of the post-step qpos (:189-251);
+                                              MYO_F_REWARD / DONE / METRICS from get_reward_dict (:253-311: object = exp(-obj_err_scale (com_err
+                                              + 0.1 rot_err)) + exp(-base_err_scale base_err)); MYO_F_SOLVED = 0.  myo_reset / myo_autoreset put
+                                              envs at init_qpos.  RANDOM references draw a fresh row at every lookup, keyed by (seed of the last
+                                              myo_reset / myo_autoreset, the env's episode count, global env id, env step); `seed`, `autoreset`
+                                              and `max_episode_steps` above are unused.  Needs robot_dim = nq - 6, object_dim = 7, nq = nv */
 } myo_track_config;
 
 typedef enum myo_terrain { MYO_TERRAIN_NONE = 0, MYO_TERRAIN_ROUGH = 1, MYO_TERRAIN_HILLY = 2, MYO_TERRAIN_STAIRS = 3 } myo_terrain;

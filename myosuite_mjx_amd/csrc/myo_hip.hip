@@ -26,6 +26,7 @@
 #include "myo_task_keyturn.h"
 #include "myo_task_pen.h"
 #include "myo_task_baoding.h"
+#include "myo_task_myodm.h"
 
 // ================================================================================================
 // host side
@@ -90,6 +91,8 @@ struct myo_batch {
   DevTrack* d_track = nullptr;    // MYO_TASK_TRACK: device copy of the task record (tables hang off it)
   float* d_metrics = nullptr;     // [B][4]
   int track_frames = 0;
+  int track_flavour = 0;          // myo_track_config.flavour: 0 MJX (fused into the step kernel), 1 classic gym TrackEnv (myodm_obs_kernel)
+  uint64_t reset_seed = 0;        // seed of the last myo_reset / myo_autoreset (classic flavour: keys the RANDOM reference draws)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   uint64_t bench_step = 0;
   long long* d_stamps = nullptr;
@@ -843,7 +846,13 @@ int myo_batch_configure_track(myo_batch* b, const myo_track_config* c) {
     return fail(MYO_E_ARG, "myo_batch_configure_track: reference rows missing");
   if (c->ref_type == 1 && ((c->robot_dim > 0 && c->robot_horizon < 2) || (c->object_dim > 0 && c->object_horizon < 2))) return fail(MYO_E_ARG, "RANDOM reference needs two rows");
   if (c->object_link < 0 || c->object_link >= m->dm.nl || c->wrist_link < 0 || c->wrist_link >= m->dm.nl) return fail(MYO_E_ARG, "myo_batch_configure_track: link out of range");
-  if (nq + nv > b->obs_alloc) return fail(MYO_E_ARG, "obs_dim too large");
+  if (c->flavour != 0 && c->flavour != 1) return fail(MYO_E_ARG, "myo_batch_configure_track: flavour must be 0 (MJX) or 1 (classic)");
+  // classic flavour (envs/myo/myodm/myodm_v0.py): hand_qpos_err = qpos[:-6] - robot, the object pose is 7 wide, and its own kinematics walk
+  // takes hinge / slide joints only
+  if (c->flavour == 1 && (nq != nv || c->robot_dim != nq - 6 || c->object_dim != 7))
+    return fail(MYO_E_ARG, "myo_batch_configure_track: the classic flavour needs nq == nv, robot_dim == nq - 6 and object_dim == 7");
+  const int obs_dim = c->flavour == 1 ? nq + nv + c->robot_dim + (c->ref_robot_vel ? c->robot_dim : 1) + 3 + m->dm.na_obs : nq + nv;
+  if (obs_dim > b->obs_alloc) return fail(MYO_E_ARG, "obs_dim too large");
   HIPCHK(hipSetDevice(m->device));
   HIPCHK(hipDeviceSynchronize());
   const int B = b->db.B;
@@ -882,10 +891,11 @@ int myo_batch_configure_track(myo_batch* b, const myo_track_config* c) {
   HIPCHK(hipMemcpy(b->d_track, &K, sizeof(DevTrack), hipMemcpyHostToDevice));
   b->db.track = b->d_track;
   b->track_frames = c->n_frames;
+  b->track_flavour = c->flavour;
   // the generic reset / observation plumbing: TrackEnv.reset puts every env at init_qpos with zero velocity, activation, control and time
   TaskDev& T = b->task;
   T = TaskDev{};
-  T.task = MYO_TASK_TRACK; T.frame_skip = c->n_frames; T.nq = nq; T.obs_dim = nq + nv;
+  T.task = MYO_TASK_TRACK; T.frame_skip = c->n_frames; T.nq = nq; T.obs_dim = obs_dim;
   HIPCHK(hipMemcpy(b->d_init, c->init_qpos, (size_t)nq * 4, hipMemcpyHostToDevice));
   T.init_qpos = b->d_init; T.jnt_lo = b->d_jlo; T.jnt_hi = b->d_jhi; T.target_lo = b->d_tlo; T.target_hi = b->d_thi;
   return MYO_OK;
@@ -1150,6 +1160,7 @@ int myo_batch_write(myo_batch* b, int field, const void* host, size_t nbytes) {
 
 int myo_reset(myo_batch* b, const uint8_t* mask_dev, uint64_t seed, void* stream) {
   if (!b) return fail(MYO_E_ARG, "myo_reset: null");
+  b->reset_seed = seed;
   const DevModel& dm = b->model->dm;
   HIPCHK(hipSetDevice(b->model->device));
   int B = b->db.B;
@@ -1161,6 +1172,7 @@ int myo_reset(myo_batch* b, const uint8_t* mask_dev, uint64_t seed, void* stream
 
 int myo_autoreset(myo_batch* b, int max_episode_steps, uint64_t seed, void* stream) {
   if (!b || max_episode_steps <= 0) return fail(MYO_E_ARG, "myo_autoreset: bad arguments");
+  b->reset_seed = seed;
   const DevModel& dm = b->model->dm;
   HIPCHK(hipSetDevice(b->model->device));
   int B = b->db.B;
@@ -1330,6 +1342,8 @@ static int launch_step(myo_batch* b, const float* action, int actmap, int nsub, 
 
 int myo_step(myo_batch* b, const float* action_dev, int actmap, int nsubsteps, void* stream) {
   if (!b || nsubsteps < 0) return fail(MYO_E_ARG, "myo_step: bad arguments");
+  if (b->task.task == MYO_TASK_TRACK && b->track_flavour == 1 && actmap == MYO_ACTMAP_CTRLRANGE)
+    return fail(MYO_E_ARG, "myo_step: MYO_ACTMAP_CTRLRANGE is the MJX TrackEnv's action map; a batch of the classic flavour steps with MYO_ACTMAP_MUSCLE_SIGMOID");
   HIPCHK(hipSetDevice(b->model->device));
   return launch_step(b, action_dev, actmap, nsubsteps, (hipStream_t)stream);
 }
@@ -1340,6 +1354,8 @@ static int launch_obs(myo_batch* b, hipStream_t s, int obs_only = 0, int reset_o
   if (b->task.task == MYO_TASK_WALK) {
     // the walk observation lives in the step kernel: run it with zero substeps as an observation-only pass
     return launch_step(b, nullptr, MYO_ACTMAP_NONE, 0, s, KF_AUX | (obs_only ? KF_OBS_ONLY : 0) | (reset_only ? KF_RESET_ONLY : 0));
+  } else if (b->task.task == MYO_TASK_TRACK && b->track_flavour == 1) {
+    hipLaunchKernelGGL(myodm_obs_kernel, dim3(B), dim3(64), 0, s, m->dm, b->db, b->task, (const DevTrack*)b->d_track, b->reset_seed, obs_only, reset_only);
   } else if (b->task.task == MYO_TASK_POSE || b->task.task == MYO_TASK_HOLD || b->task.task == MYO_TASK_STAND || b->task.task == MYO_TASK_TRACK) {
     hipLaunchKernelGGL(obs_kernel, dim3(B), dim3(64), 0, s, m->dm, b->db, b->task, obs_only, reset_only);
   } else if (b->task.task == MYO_TASK_KEYTURN) {
@@ -1450,11 +1466,19 @@ int myo_bench_rollout(myo_batch* b, int steps, int nsubsteps, uint64_t seed, int
   for (int i = 0; i < steps; i++) {
     if (mode & MYO_BENCH_FRESH_ACTIONS) { rc = myo_random_action(b, b->d_action, seed, b->bench_step++, b->env_offset, stream); if (rc) return rc; }
     HIPCHK(hipEventRecord(b->kev[2 * (base + i)], s));       // brackets the dominant kernel (+ its tiny placement kernel) on its own stream
-    rc = launch_step(b, b->d_action, b->task.task == MYO_TASK_TRACK ? MYO_ACTMAP_CTRLRANGE : MYO_ACTMAP_MUSCLE_SIGMOID, nsubsteps, s);
+    const bool mjx_track = b->task.task == MYO_TASK_TRACK && b->track_flavour == 0;
+    rc = launch_step(b, b->d_action, mjx_track ? MYO_ACTMAP_CTRLRANGE : MYO_ACTMAP_MUSCLE_SIGMOID, nsubsteps, s);
     if (rc) return rc;
     HIPCHK(hipEventRecord(b->kev[2 * (base + i) + 1], s));
     const int tk = b->task.task;
-    if (tk == MYO_TASK_TRACK) continue;   // observation, reward, done and the masked reset are the step kernel's own epilogue
+    if (mjx_track) continue;   // observation, reward, done and the masked reset are the step kernel's own epilogue
+    if ((mode & MYO_BENCH_OBS) && (mode & MYO_BENCH_AUTORESET) && max_episode_steps > 0 && tk == MYO_TASK_TRACK) {     // ... the classic MyoDM flavour
+      b->reset_seed = seed;
+      hipLaunchKernelGGL(myodm_post_kernel, dim3(b->db.B), dim3(64), 0, s, b->model->dm, b->db, b->task, (const DevTrack*)b->d_track, b->model->nq,
+                         b->model->dm.qpos0, seed, b->env_offset, max_episode_steps);
+      HIPCHK(hipGetLastError());
+      continue;
+    }
     if ((mode & MYO_BENCH_OBS) && (mode & MYO_BENCH_AUTORESET) && max_episode_steps > 0 && (tk == MYO_TASK_POSE || tk == MYO_TASK_HOLD || tk == MYO_TASK_STAND)) {
       // state-only observations: observation + auto-reset + first observation of the new episodes in ONE launch (post_kernel)
       hipLaunchKernelGGL(post_kernel, dim3(b->db.B), dim3(64), 0, s, b->model->dm, b->db, b->task, b->model->nq, b->model->dm.qpos0, seed, b->env_offset, max_episode_steps);

@@ -1,0 +1,147 @@
+// myo_task_myodm.h -- the classic gym flavour of the MyoDM TrackEnv (envs/myo/myodm/myodm_v0.py, the entry point of the registered MyoDM
+// ids): observation / reward / done / metrics of MYO_TASK_TRACK batches configured with myo_track_config.flavour = 1.
+//
+// The env step itself is BaseV0.step on the TRK step kernel, unchanged: the muscle sigmoid on the muscles, the raw action on the position
+// actuators (clamped to ctrlrange where the actuator force reads it, as MuJoCo clamps ctrl), frame_skip = 10 substeps.  get_obs_dict then
+// reads the reference at the POST-step time and the object / wrist body frames of the post-step state (update_reference_insim's
+// sim.forward()), so this kernel runs its own forward kinematics of the two links it reads, from the post-step qpos, one lane each.
+// One 64-lane workgroup per env.
+#ifndef MYO_TASK_MYODM_H
+#define MYO_TASK_MYODM_H
+
+// world frame (relative to the lowered origin) of a frame fixed in link `link`: point lp -> p, rotation Rl -> R, at the joint positions q of
+// env e.  The walk of link_point_pos (myo_task_keyturn.h) with the rotation carried along.  Hinge / slide joints only (nq == nv, checked at
+// configure).
+__device__ __forceinline__ void myodm_link_frame(const DevModel& M, const DevBatch& Bt, const float* q, int e, int link, const float* lp, const float* Rl,
+                                                 float* p, float* R) {
+  p[0] = lp[0]; p[1] = lp[1]; p[2] = lp[2];
+#pragma unroll
+  for (int k = 0; k < 9; k++) R[k] = Rl[k];
+  for (int l = link; l >= 0; l = M.link_parent[l]) {
+    float A[9], c[3] = {M.link_pos[3 * l], M.link_pos[3 * l + 1], M.link_pos[3 * l + 2]};
+    const float lq[4] = {M.link_quat[4 * l], M.link_quat[4 * l + 1], M.link_quat[4 * l + 2], M.link_quat[4 * l + 3]};
+    quat2mat(A, lq);
+    if (Bt.bpos && l == Bt.bpos_link) {
+      const float* o = Bt.bpos + 3 * (size_t)e;
+      c[0] += o[0]; c[1] += o[1]; c[2] += o[2];
+    }
+    const int da = M.link_dofadr[l], dn = M.link_dofnum[l];
+    for (int k = 0; k < dn; k++) {
+      const int d = da + k;
+      const float al[3] = {M.dof_axis[3 * d], M.dof_axis[3 * d + 1], M.dof_axis[3 * d + 2]};
+      const float dp[3] = {M.dof_pos[3 * d], M.dof_pos[3 * d + 1], M.dof_pos[3 * d + 2]};
+      const float ang = q[d] - M.qpos0[d];
+      float ax[3], an[3];
+      matvec(ax, A, al);
+      matvec(an, A, dp);
+      an[0] += c[0]; an[1] += c[1]; an[2] += c[2];
+      if (M.dof_type[d] == 3) {   // hinge: rotate about the axis through the anchor
+        float sn, cs;
+        sincosf(ang, &sn, &cs);
+        const float oc = 1 - cs, x = al[0], y = al[1], z = al[2];
+        const float Rj[9] = {cs + oc * x * x, oc * x * y - sn * z, oc * x * z + sn * y, oc * x * y + sn * z, cs + oc * y * y, oc * y * z - sn * x,
+                             oc * x * z - sn * y, oc * y * z + sn * x, cs + oc * z * z};
+        float v[3];
+        matmul3(A, A, Rj);
+        matvec(v, A, dp);
+        c[0] = an[0] - v[0]; c[1] = an[1] - v[1]; c[2] = an[2] - v[2];
+      } else {                    // slide
+        c[0] += ax[0] * ang; c[1] += ax[1] * ang; c[2] += ax[2] * ang;
+      }
+    }
+    float w[3];
+    matvec(w, A, p);
+    p[0] = w[0] + c[0]; p[1] = w[1] + c[1]; p[2] = w[2] + c[2];
+    matmul3(R, A, R);
+  }
+}
+
+// get_obs_dict (:189-251, + act, base_v0.py:34-38) and get_reward_dict / check_termination (:253-311, :336-362) of env e.  Row: qpos (nq),
+// qvel (nv), hand_qpos_err (nr), hand_qvel_err (nr, or the single 0 of a reference without robot_vel), obj_com_err (3), act (na).
+// The reference row is looked up at t = elapsed * frame_skip * timestep + motion_start_time in double (the post-step sim.data.time, which
+// the reference rounds to 4 decimals before comparing it with the frame times); RANDOM draws are keyed by (seed, the env's episode count,
+// global env id, env step).  `seed` is the seed of the last reset.
+__device__ __forceinline__ void myodm_obs_body(const DevModel& M, const DevBatch& Bt, const TaskDev& T, const DevTrack& K, uint64_t seed, int obs_only,
+                                               const int e, const int lane) {
+  const int nv = M.nv, nu = M.nu, nr = K.robot_dim;
+  const int vdim = K.has_vel ? nr : 1, oe = 2 * nv + nr + vdim;   // offset of obj_com_err
+  const float* q = Bt.qpos + (size_t)e * nv;
+  const float* v = Bt.qvel + (size_t)e * nv;
+  const float* a = Bt.act + (size_t)e * nu;
+  float* o = Bt.obs + (size_t)e * T.obs_dim;
+  const int elapsed = Bt.elapsed[e];
+  track_lookup<true>(K, e, e + Bt.env_offset, 0.f, elapsed, lane, (double)elapsed * (double)T.frame_skip * (double)M.timestep,
+                     seed + 0x632BE59BD9B4E019ull * (uint64_t)Bt.episode[e]);
+  __syncthreads();                       // the reference row (written by lanes < nr + 7) is complete before every lane reads it
+  const float* R = K.ref + (size_t)e * K.ref_pitch;
+  const float* tc = R + 2 * nr;          // target object pose: com (3) | quaternion (4)
+  // xipos / ximat of the object body (lane 0) and xipos of the wrist (lunate) body (lane 1) of the post-step state
+  float p[3] = {0.f, 0.f, 0.f}, Rb[9];
+  if (lane < 2) {
+    myodm_link_frame(M, Bt, q, e, lane == 0 ? K.obj_link : K.wrist_link, lane == 0 ? K.obj_p : K.wrist_p, K.obj_R, p, Rb);
+#pragma unroll
+    for (int k = 0; k < 3; k++) p[k] += M.origin[k];
+  }
+  float com[3], wr[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) { com[k] = __shfl(p[k], 0); wr[k] = __shfl(p[k], 1); }
+  for (int i = lane; i < nv; i += 64) { o[i] = q[i]; o[nv + i] = v[i]; }
+  float qe = 0.f, ve = 0.f;
+  if (lane < nr) {
+    qe = q[lane] - R[lane];
+    o[2 * nv + lane] = qe;
+    if (K.has_vel) { ve = v[lane] - R[nr + lane]; o[2 * nv + nr + lane] = ve; }
+  }
+  if (!K.has_vel && lane == 0) o[2 * nv + nr] = 0.f;
+  if (lane < 3) o[oe + lane] = com[lane] - tc[lane];
+  for (int i = lane; i < nu; i += 64) { const int sl = M.act_obs[i]; if (sl >= 0) o[oe + 3 + sl] = a[i]; }
+  if (obs_only) return;
+  const float q2 = wave_sum(qe * qe), v2 = wave_sum(ve * ve);
+  if (lane == 0) {
+    float cq[4];
+    track_mat2quat(Rb, cq);
+    const float e0 = tc[0] - com[0], e1 = tc[1] - com[1], e2 = tc[2] - com[2];
+    const float obj_com_err = sqrtf(e0 * e0 + e1 * e1 + e2 * e2);
+    const float obj_rot_err = track_rot_err(cq, tc + 3);
+    const float obj_reward = expf(-K.obj_err_scale * (obj_com_err + 0.1f * obj_rot_err));            // :262-265
+    const float lift_bonus = (tc[2] >= K.lift_z && com[2] >= K.lift_z) ? 1.f : 0.f;                 // :268
+    const float qpos_reward = expf(-K.qpos_err_scale * q2);
+    const float qvel_reward = expf(-K.qvel_err_scale * v2);             // hand_qvel_err = [0] without robot_vel: exp(0) = 1 (:276-280)
+    const float b0 = com[0] - wr[0], b1 = com[1] - wr[1], b2 = com[2] - wr[2];
+    const float base_error = sqrtf(b0 * b0 + b1 * b1 + b2 * b2);
+    const float base_reward = expf(-K.base_err_scale * base_error);
+    bool term = false;
+    if (K.term_obj) term = term || (obj_com_err * obj_com_err >= K.obj_fail2) || (base_error * base_error >= K.base_fail2);
+    if (K.term_pose) term = term || (q2 >= K.qpos_fail);
+    const float done = term ? 1.f : 0.f;
+    const float m_pose = K.qpos_w * qpos_reward + K.qvel_w * qvel_reward, m_obj = obj_reward + base_reward, m_bonus = K.lift_bonus_mag * lift_bonus;
+    Bt.reward[e] = K.w_pose * m_pose + K.w_object * m_obj + K.w_bonus * m_bonus + K.w_penalty * done;
+    Bt.done[e] = done;
+    Bt.solved[e] = 0.f;
+    float* mt = K.metrics + 4 * (size_t)e;
+    mt[0] = m_pose; mt[1] = m_obj; mt[2] = m_bonus; mt[3] = done;
+  }
+}
+
+__global__ void __launch_bounds__(64) myodm_obs_kernel(DevModel M, DevBatch Bt, TaskDev T, const DevTrack* K, uint64_t seed, int obs_only, int reset_only) {
+  const int e = blockIdx.x;
+  if (e >= Bt.B) return;
+  if (reset_only && Bt.elapsed[e] != 0) return;    // refresh only the rows of envs an auto-reset just touched
+  myodm_obs_body(M, Bt, T, *K, seed, obs_only, e, threadIdx.x);
+}
+
+// myo_bench_rollout's fused epilogue (pen_post_kernel's pattern): observation / reward / done of the stepped state, auto-reset, and the
+// first observation of the new episodes, in one launch
+__global__ void __launch_bounds__(64) myodm_post_kernel(DevModel M, DevBatch Bt, TaskDev T, const DevTrack* K, int nq, const float* qpos0, uint64_t seed,
+                                                        int env_offset, int auto_max) {
+  const int e = blockIdx.x, lane = threadIdx.x;
+  if (e >= Bt.B) return;
+  myodm_obs_body(M, Bt, T, *K, seed, 0, e, lane);
+  __syncthreads();                       // reward / done of this env written (lane 0) before every lane tests them
+  if (reset_body(Bt, T, nq, M.nv, M.nu, qpos0, nullptr, seed, env_offset, auto_max, e, lane)) {
+    __syncthreads();                     // the new state rows are complete before they are read back
+    myodm_obs_body(M, Bt, T, *K, seed, 1, e, lane);
+  }
+}
+
+#endif  // MYO_TASK_MYODM_H

@@ -13,7 +13,11 @@
 #define MYO_TASK_TRACK_H
 
 // lane i < robot_dim: robot[i] (and robot_vel[i]); lane robot_dim + j: object[j].  Written to this env's row of K.ref (robot | robot_vel | object).
-__device__ __forceinline__ void track_lookup(const DevTrack& K, int env, int genv, float time, int elapsed, int lane) {
+// MJX flavour (CLASSIC = false): `time` is the pre-step time, RANDOM draws keyed by (K.seed, global env id, env step).  Classic flavour
+// (myo_task_myodm.h): the lookup time is t_classic (double) and RANDOM draws take seed_classic instead of K.seed.
+template <bool CLASSIC = false>
+__device__ __forceinline__ void track_lookup(const DevTrack& K, int env, int genv, float time, int elapsed, int lane, double t_classic = 0.0,
+                                             uint64_t seed_classic = 0) {
   const int nr = K.robot_dim, no = K.object_dim;
   float* out = K.ref + (size_t)env * K.ref_pitch;
   const bool isr = lane < nr, iso = lane >= nr && lane < nr + no;
@@ -26,16 +30,16 @@ __device__ __forceinline__ void track_lookup(const DevTrack& K, int env, int gen
   if (K.ref_type == 1) {                                               // RANDOM: uniform between the two rows, a fresh draw per env step
     const uint64_t key = (uint64_t)genv * 4096 + (uint64_t)lane;
     if (isr) {
-      const double u = (double)u01(K.seed, key, (uint64_t)elapsed * 4 + 0), a = K.robot[j], b = K.robot[nr + j];
+      const double u = (double)u01(CLASSIC ? seed_classic : K.seed, key, (uint64_t)elapsed * 4 + 0), a = K.robot[j], b = K.robot[nr + j];
       out[j] = (float)(a + (b - a) * u);
-      if (K.has_vel) { const double u2 = (double)u01(K.seed, key, (uint64_t)elapsed * 4 + 1), c = K.robot_vel[j], d = K.robot_vel[nr + j]; out[nr + j] = (float)(c + (d - c) * u2); }
+      if (K.has_vel) { const double u2 = (double)u01(CLASSIC ? seed_classic : K.seed, key, (uint64_t)elapsed * 4 + 1), c = K.robot_vel[j], d = K.robot_vel[nr + j]; out[nr + j] = (float)(c + (d - c) * u2); }
     }
-    if (iso) { const double u = (double)u01(K.seed, key, (uint64_t)elapsed * 4 + 2), a = K.object[j], b = K.object[no + j]; out[2 * nr + j] = (float)(a + (b - a) * u); }
+    if (iso) { const double u = (double)u01(CLASSIC ? seed_classic : K.seed, key, (uint64_t)elapsed * 4 + 2), a = K.object[j], b = K.object[no + j]; out[2 * nr + j] = (float)(a + (b - a) * u); }
     return;
   }
   // TRACK
   const int H = K.horizon;
-  const double t = rint(((double)time + K.start_time) * 1e4) / 1e4;
+  const double t = rint(((CLASSIC ? t_classic : (double)time) + K.start_time) * 1e4) / 1e4;
   int lo = 0, hi = H;                                                  // number of frame times <= t (searchsorted side = "right")
   while (lo < hi) { const int mid = (lo + hi) >> 1; if (K.T[mid] <= t) lo = mid + 1; else hi = mid; }
   int idx = min(max(lo - 1, 0), H - 1);
@@ -81,6 +85,15 @@ __device__ __forceinline__ void track_mat2quat(const float* M, float* q) {
   q[0] = sg * w; q[1] = sg * x; q[2] = sg * y; q[3] = sg * z;
 }
 
+// rotation_distance(curr, targ, euler = False) / pi = |quatDiff2Vel(targ, curr, 1)[0]| / pi (:180-183): diff = curr * conj(targ), the
+// speed 2 atan2(|diff.xyz|, diff.w).  a: current quaternion, tq: target quaternion (as the reference gives it, not normalised)
+__device__ __forceinline__ float track_rot_err(const float* a, const float* tq) {
+  const float b[4] = {tq[0], -tq[1], -tq[2], -tq[3]};
+  const float d0 = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3], d1 = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
+              d2 = a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1], d3 = a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0];
+  return fabsf(2.f * atan2f(sqrtf(d1 * d1 + d2 * d2 + d3 * d3), d0)) / 3.14159265358979323846f;
+}
+
 // compute_reward (:185-267) on the stepped state: qpos / qvel are the post-step rows (LDS), the body frames those of the last substep's
 // position stage (what an MJX pipeline_state holds after mjx.step).  lpos / lmat: link frames in LDS (origin-shifted), org = model origin.
 // Every lane computes the (uniform) scalars; lane 0 writes.  Returns done.
@@ -113,11 +126,7 @@ __device__ __forceinline__ float track_reward(const DevTrack& K, const DevBatch&
   track_mat2quat(Rm, a);
   const float e0 = tc[0] - com[0], e1 = tc[1] - com[1], e2 = tc[2] - com[2];
   const float obj_com_err = sqrtf(e0 * e0 + e1 * e1 + e2 * e2);
-  // rotation_distance(curr, targ, euler = False) = |quatDiff2Vel(targ, curr, 1)[0]| (:180-183): diff = curr * conj(targ)
-  const float b[4] = {tc[3], -tc[4], -tc[5], -tc[6]};
-  const float d0 = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3], d1 = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
-              d2 = a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1], d3 = a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0];
-  const float obj_rot_err = fabsf(2.f * atan2f(sqrtf(d1 * d1 + d2 * d2 + d3 * d3), d0)) / 3.14159265358979323846f;
+  const float obj_rot_err = track_rot_err(a, tc + 3);
   const float obj_reward = expf(-K.obj_err_scale * obj_com_err) * expf(-K.obj_err_scale * obj_rot_err);
   const float lift_bonus = (tc[2] >= K.lift_z && com[2] >= K.lift_z) ? 1.f : 0.f;
   const float qpos_reward = expf(-K.qpos_err_scale * q2);

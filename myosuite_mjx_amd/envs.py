@@ -594,9 +594,23 @@ class BatchedMyoEnv:
         return self.batch.status()
 
 
-def _make_track(env_id, num_envs, reference=None, **kw):
+def _make_track(env_id, num_envs, reference=None, flavour="mjx", **kw):
+    from .track import ClassicTrackEnv, TrackEnv
+    if flavour not in ("mjx", "classic"):
+        raise ValueError(f"{env_id}: flavour must be 'mjx' (mjx/myodm_v0.py, the default) or 'classic' (envs/myo/myodm/myodm_v0.py), got {flavour!r}")
+    reference = _myodm_reference(env_id, reference)
+    kw.setdefault("max_episode_steps", REGISTRY[env_id]["max_episode_steps"])
+    if flavour == "classic":
+        env = ClassicTrackEnv(num_envs=num_envs, object_name=REGISTRY[env_id]["object"], reference=reference, **kw)
+    else:
+        env = TrackEnv(num_envs=num_envs, object_name=REGISTRY[env_id]["object"], reference=reference, gym_api=True, **kw)
+    env.id = env_id
+    return env
+
+
+def _myodm_reference(env_id, reference=None):
+    """The reference of a MyoDM id: `reference` if given, the registered one of the Fixed / Random ids, else the id's motion file."""
     import os
-    from .track import TrackEnv
     spec = REGISTRY[env_id]
     if reference is None:
         reference = spec.get("reference")
@@ -607,14 +621,41 @@ def _make_track(env_id, num_envs, reference=None, **kw):
             raise FileNotFoundError(f"{env_id}: motion file {spec['motion']} not found; pass reference=<path or dict> or set MYODM_DATA to the "
                                     "directory of the reference's envs/myo/myodm/data")
         reference = hits[0]
-    kw.setdefault("max_episode_steps", spec["max_episode_steps"])
-    env = TrackEnv(num_envs=num_envs, object_name=spec["object"], reference=reference, gym_api=True, **kw)
-    env.id = env_id
-    return env
+    return reference
+
+
+def myodm_spec(env_id, flavour="mjx", reference=None):
+    """What make(env_id, flavour=...) builds for a MyoDM id, worked out on the host (no GPU): frame_skip, obs_dim, act_dim, init_qpos,
+    max_episode_steps (the TimeLimit) and the reference type.  init_qpos = qpos0 with [:robot_dim] = robot_init, the object position from
+    object_init[:3] and its three hinges from quat2euler(object_init[3:]) (envs/myo/myodm/myodm_v0.py:168-179, mjx/myodm_v0.py:144-150)."""
+    from .track import ReferenceMotion, quat2euler
+    if flavour not in ("mjx", "classic"):
+        raise ValueError(f"{env_id}: flavour must be 'mjx' or 'classic', got {flavour!r}")
+    spec = REGISTRY[env_id]
+    if spec.get("task") != "track":
+        raise KeyError(f"{env_id} is not a MyoDM id")
+    m = _model.load_asset(f"myohand_object_{spec['object']}")
+    ref = ReferenceMotion(_myodm_reference(env_id, reference))
+    init = np.array(m.qpos0, float)
+    ri, oi = ref.get_init()
+    if ri is not None:
+        init[: ref.robot_dim] = ri
+    if oi is not None:
+        init[ref.robot_dim: ref.robot_dim + 3] = oi[:3]
+        init[-3:] = quat2euler(oi[3:])
+    nr = ref.robot_dim
+    if flavour == "classic":     # qp, qv, hand_qpos_err, hand_qvel_err ([0] without robot_vel), obj_com_err, act (base_v0.py:34-38)
+        obs_dim = m.nq + m.nv + nr + (nr if ref.reference["robot_vel"] is not None else 1) + 3 + m.n_muscle
+    else:
+        obs_dim = m.nq + m.nv
+    return dict(frame_skip=10 if flavour == "classic" else 5, obs_dim=obs_dim, act_dim=m.nu, init_qpos=init.astype(np.float32),
+                max_episode_steps=spec["max_episode_steps"], ref_type=ref.type)
 
 
 def make(env_id, num_envs=1, **kw):
-    """gym.make counterpart for the batched envs (envs/myo/myobase/__init__.py and envs/myo/myodm/__init__.py register the same ids)."""
+    """gym.make counterpart for the batched envs (envs/myo/myobase/__init__.py and envs/myo/myodm/__init__.py register the same ids).
+    The MyoDM ids take `flavour`: "mjx" (default, mjx/myodm_v0.py TrackEnv -> track.TrackEnv) or "classic" (the registered entry point,
+    envs/myo/myodm/myodm_v0.py TrackEnv -> track.ClassicTrackEnv)."""
     if env_id in REGISTRY and REGISTRY[env_id].get("task") == "track":
         return _make_track(env_id, num_envs, **kw)
     return BatchedMyoEnv(env_id, num_envs=num_envs, **kw)

@@ -604,7 +604,7 @@ int myo_batch_create(const myo_model* m, int B, myo_batch** out) {
   if (m->dw.hf.on) { BA(d.hfield, (size_t)B * m->dw.hf.nrow * m->dw.hf.ncol) }   // zero-filled: flat terrain at the geom's height
   BA(b->d_initv, nv) BA(b->d_init2, nq) BA(b->d_initv2, nv) BA(b->d_fatvec, nu)
   { void* pw = nullptr; if ((rc = balloc(b, &pw, sizeof(DevWalk)))) { myo_batch_free(b); return rc; } b->d_walk = (DevWalk*)pw; }
-  BA(b->d_stamps, (size_t)B * 12 * 2 * 2)      // 2 x 12 long long per workgroup (diagnostic build)
+  BA(b->d_stamps, (size_t)B * 12 * 3 * 2)      // 3 x 12 long long per workgroup (diagnostic build)
   BA(b->d_order, B)
   b->sched_stride = (B + 7) / 8 + 1;                 // per queue with 8 queues; launch_step widens it when the device shows fewer XCDs
   BA(b->d_sched, 32 + B + 64)

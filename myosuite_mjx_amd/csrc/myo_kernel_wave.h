@@ -145,6 +145,7 @@ template <int NVT> __device__ __forceinline__ float chol_rows(float (&r)[NVT], i
   }
   return invd;
 }
+#include "myo_ldl_mfma.h"
 // Dof trees of the size-specialised instantiations (parent dof of each dof; myo_model_load checks the model's dof_parentid against them
 // before it selects a specialised instantiation).  The mass matrix M and M + h D couple a dof only with its ancestors and descendants:
 // factorised LEAVES FIRST (lane i <-> dof nv - 1 - i) the Cholesky factor keeps exactly that pattern, no fill-in (Featherstone; MuJoCo's
@@ -496,12 +497,19 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
 #if MYO_STAMPS
   long long st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   long long st_t0 = clock64();
-  long long st_sub[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_s0 = 0;   // finer split (second half of the stamps buffer)
+  long long st_sub[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_s0 = 0;   // finer split (second third of the stamps buffer)
+  // last third: [0] cycles of the dense Newton refactors, [1] cycles of the tree-sparse M / M + h D factorisations (both out of sub[2]),
+  // [2] number of dense Newton refactors
+  long long st_x[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #define SUB0() do { st_s0 = clock64(); } while (0)
 #define SUB(k) do { long long t1_ = clock64(); st_sub[k] += t1_ - st_s0; st_s0 = t1_; } while (0)
+#define SUBX(k) do { long long t1_ = clock64(); st_x[k] += t1_ - st_s0; st_s0 = t1_; } while (0)
+#define CNTX(k) do { st_x[k]++; } while (0)
 #else
 #define SUB0() do { } while (0)
 #define SUB(k) do { } while (0)
+#define SUBX(k) do { } while (0)
+#define CNTX(k) do { } while (0)
 #endif
   const int nsubtot = nsub + (walk ? 1 : 0);
   const float h = M.timestep;
@@ -2259,11 +2267,19 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
           E[Y.sq + lane * (NVT + 1) + NVT] = invd;
         }
         SYNC();
-        SUB(2);
+        SUBX(1);
         const float xp = chol_solve_rows<NVT>(r, invd, rhs_p, E + Y.sq, lane);
         x = __shfl(xp, act ? NVS - 1 - lane : lane);
       } else {
-      if (refactor) {
+      // Newton refactor on the matrix cores: L and 1 / D replace the Hessian in the buffer, the rows are then reloaded like a reused factor
+      constexpr bool LDL_MFMA = MYO_LDL_MFMA && NVT <= 32;
+      if constexpr (LDL_MFMA) {
+        if (refactor && phase == 0) {
+          ldl_mfma<NVT>(E + Y.sq, lane);
+          SYNC();
+        }
+      }
+      if (refactor && !(LDL_MFMA && phase == 0)) {
         if (phase == 0) {          // Newton: the buffer already holds M + the diagonal terms + J^T D J (see the assembly above)
           const int ll_ = lane < NVT ? lane : 0;
 #pragma unroll
@@ -2289,13 +2305,13 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
         }
         SYNC();
       } else {
-        // the factor of the previous iteration is still in LDS (row-major L): reload this lane's row
+        // the factor of the previous iteration (or the one ldl_mfma just wrote) is in LDS (row-major L): reload this lane's row
         const int ll = lane < NVT ? lane : 0;
 #pragma unroll
         for (int k = 0; k < NVT; k++) r[k] = E[Y.sq + ll * (NVT + 1) + k];
         invd = E[Y.sq + ll * (NVT + 1) + NVT];
       }
-      SUB(2);
+      if (refactor && phase == 0) { SUBX(0); CNTX(2); } else SUB(2);
       x = chol_solve_rows<NVT>(r, invd, rhs, E + Y.sq, lane);
       }
       SUB(3);
@@ -2575,7 +2591,8 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
 #if MYO_STAMPS
   st_acc[10] = __builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_REG_HW_ID: wave/simd/cu/sh/se ids (placement census)
   st_acc[11] = (__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xFF) | ((long long)(oe >> 28) << 8) | ((long long)last_cost << 16);   // HW_REG_XCC_ID, issue priority, cost estimate
-  if (stamps && lane_id == 0) for (int k = 0; k < 12; k++) { stamps[(size_t)blockIdx.x * 12 + k] = st_acc[k]; stamps[((size_t)gridDim.x + blockIdx.x) * 12 + k] = st_sub[k]; }
+  if (stamps && lane_id == 0) for (int k = 0; k < 12; k++) { stamps[(size_t)blockIdx.x * 12 + k] = st_acc[k]; stamps[((size_t)gridDim.x + blockIdx.x) * 12 + k] = st_sub[k];
+                                                stamps[((size_t)2 * gridDim.x + blockIdx.x) * 12 + k] = st_x[k]; }
 #endif
 }
 

@@ -6,8 +6,12 @@
 //   myo_task_track.h    MyoDM TrackEnv as a fused task of the TRK step kernel: reference lookup, reward / done, masked reset
 //   myo_kernel_lanes.h  step_kernel<G>: the first kernel, G = 16 / 32 / 64 lanes per env, all state in LDS (cross-check / fallback)
 //   myo_kernel_wave.h   step_kernel_w: one env per 64-lane wavefront (default), substep scheduler, size-specialised instantiations
-//   myo_kernels_aux.h   RNG, placement hint, random actions, policy inference, reset, observation kernels
-//   myo_hip.hip         host side: model upload, batches, launches, the extern "C" entry points
+//   myo_ldl_mfma.h      dense LDL^T of the Newton Hessian on the FP32 matrix cores (included by myo_kernel_wave.h)
+//   myo_kernels_aux.h   RNG, placement hint, random actions, policy inference, reset, state-only observations, task_obs_kernel / task_post_kernel
+//   myo_host.h          host records: myo_model, myo_batch, the per-task hook record (TaskHooks) and its generic launchers
+//   myo_task_*.h        key-turn, pen, baoding, classic MyoDM: a task's observation body, its configure checks and its hook record
+//   myo_host_model.h    myo_model_load in pieces: blob view, table upload, packing of the per-lane records, kernel class
+//   myo_hip.hip         host side: batches, the table of step-kernel instantiations, launches, the task table, the extern "C" entry points
 //
 // Execution model: one environment = one wavefront = one workgroup; the whole working set of an env (link
 // frames, sparse tendon Jacobian rows, spatial inertias, mass matrix, contact rows, Newton vectors) lives in that wave's LDS slice
@@ -23,168 +27,12 @@
 #include "myo_kernel_lanes.h"
 #include "myo_kernel_wave.h"
 #include "myo_kernels_aux.h"
+#include "myo_host.h"
 #include "myo_task_keyturn.h"
 #include "myo_task_pen.h"
 #include "myo_task_baoding.h"
 #include "myo_task_myodm.h"
-
-// ================================================================================================
-// host side
-// ================================================================================================
-static int g_lanes = 64;  // lanes per env (16 / 32 / 64); MYO_LANES env var or myo_set_lanes(); 64 = wave-per-env kernel
-static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(MYO_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
-
-struct BlobRec { char name[32]; uint32_t dtype, ndim, shape[4]; uint64_t nbytes, offset; };
-
-struct myo_model {
-  int device = 0;
-  DevModel dm{};
-  DevModelW dw{};
-  DevModel* d_dm = nullptr;     // device copies of the model structs for the wave kernel
-  DevModelW* d_dw = nullptr;
-  int env_lds_bytes_w = 0;
-  bool wave_ok = false, generic_ok = false;
-  int n_cu = 0;                 // compute units of the model's device (scheduler sizing)
-  int kin_floats = 0;           // LDS scratch the two-phase kinematics needs (lowering.py hip_kin_size)
-  bool rk4 = false;             // <option integrator="RK4">: the RK4 instantiations of the wave kernel (generic sizes, no scheduler)
-  bool trk = false;             // TrackEnv model class: step_kernel_w<36,20,32,2,2,false,0,false,true>
-  bool hand_sizes = false, leg_sizes = false, terrain_sizes = false;   // table sizes equal Sizes<1> / Sizes<2>: the size-specialised instantiations may be used
-  int wave_cfg = 0;             // 0: step_kernel_w<24,8,32,1,4> (hand / finger), 1: step_kernel_w<36,20,48,2,2> (legs)
-  int nq = 0;
-  int has_tl = 0;
-  bool has_affine = false;   // some actuator is a stateless affine one (motor / position / velocity): wave kernel only
-  myo_dims dims{};
-  std::vector<void*> dev_allocs;
-  std::vector<float> qpos0, jnt_lo, jnt_hi;
-  std::vector<int> cg_geom, cg_type_h;   // collision geom -> compiled geom id, and its type (host copies)
-  std::vector<int> body_link;                       // body -> link, pose of the body inside the link frame (walk task)
-  std::vector<float> body_lpos, body_lquat, mass;   // mass = [total, static bodies' mass-weighted COM xyz]
-  float* d_qpos0 = nullptr;
-  int env_lds_bytes = 0;
-  // per-env body masses (MYO_F_BODYMASS): the compiled body_mass and, per link, its member bodies (CSR) with their COM (3), inertia
-  // about the COM (6) in the link frame and compiled mass -- the per-body constants of lowering.py's link recomposition (link_compose_kernel)
-  std::vector<float> body_mass0;
-  const int *d_lm_adr = nullptr, *d_lm_body = nullptr;
-  const double* d_lm_tab = nullptr;
-  // per-env translation of one root body (MYO_F_BODYPOS): the link headed by the body that carries the model's last joint, when that body
-  // is a child of the world heading a root link of a TrackEnv-class model; -1 otherwise
-  int bp_link = -1;
-  // per-env orientation of one world-welded body (MYO_F_BODYQUAT): compiled body tree, poses and the bodies of the collision geoms / sites
-  std::vector<int> body_parent, body_jntnum, cg_body, site_body;
-  std::vector<double> body_pos0, body_quat0;
-  std::vector<double> site_pos0;   // compiled site_pos (site in its body's frame): the baoding task's moving targets keep its z
-};
-
-struct myo_batch {
-  const myo_model* model = nullptr;
-  DevBatch db{};
-  TaskDev task{};
-  int ntarget_alloc = 0, obs_alloc = 0, env_offset = 0;
-  std::vector<void*> dev_allocs;
-  float *d_tlo = nullptr, *d_thi = nullptr, *d_init = nullptr, *d_jlo = nullptr, *d_jhi = nullptr, *d_action = nullptr, *d_rnd = nullptr;
-  float* d_initv = nullptr;
-  float *d_init2 = nullptr, *d_initv2 = nullptr, *d_fatvec = nullptr;   // walk reset "random": second keyframe; fatigue reset vector
-  const char* last_kernel = "step_kernel";   // name of the step-kernel instantiation of the last myo_step / bench launch
-  DevWalk* d_walk = nullptr;
-  DevTrack* d_track = nullptr;    // MYO_TASK_TRACK: device copy of the task record (tables hang off it)
-  float* d_metrics = nullptr;     // [B][4]
-  int track_frames = 0;
-  int track_flavour = 0;          // myo_track_config.flavour: 0 MJX (fused into the step kernel), 1 classic gym TrackEnv (myodm_obs_kernel)
-  uint64_t reset_seed = 0;        // seed of the last myo_reset / myo_autoreset (classic flavour: keys the RANDOM reference draws)
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  uint64_t bench_step = 0;
-  long long* d_stamps = nullptr;
-  int* d_order = nullptr;
-  int* d_sched = nullptr;       // substep scheduler: 8 queues x (4 control words + ring)
-  int sched_stride = 0;
-  int balance = 1;
-  bool bm_on = false;            // per-env body-mass override started (DevBatch.bmass / bmass_range / linkc allocated)
-  bool bp_on = false;            // per-env root-body offset started (DevBatch.bpos / bpos_range allocated)
-  int bq_body = -1;              // body of MYO_F_BODYQUAT (myo_task_config.quat_body; -1: none selected)
-  bool bq_on = false;            // per-env body orientation started (DevBatch.bquat / bquat_range / bq_c / bq_flag allocated)
-  std::vector<hipEvent_t> kev;   // per-launch event pairs around the step kernel (bench only)
-  int kev_pending = 0;           // pairs recorded by asynchronous bench calls and not collected yet
-  float last_kernel_ms = 0.f;
-};
-
-static const BlobRec* blob_find(const uint8_t* blob, const char* name) {
-  uint32_t n;
-  memcpy(&n, blob + 8, 4);
-  for (uint32_t i = 0; i < n; i++) {
-    const BlobRec* r = (const BlobRec*)(blob + 16 + (size_t)i * sizeof(BlobRec));
-    if (!strncmp(r->name, name, 32)) return r;
-  }
-  return nullptr;
-}
-
-template <typename T> static int upload(myo_model* m, const std::vector<T>& v, const T** out) {
-  void* p = nullptr;
-  size_t nb = (v.size() + 4) * sizeof(T);
-  HIPCHK(hipMalloc(&p, nb));
-  HIPCHK(hipMemset(p, 0, nb));
-  if (!v.empty()) HIPCHK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  m->dev_allocs.push_back(p);
-  *out = (const T*)p;
-  return 0;
-}
-// (out is a template so that the struct fields' device-side address-space types do not matter to this host code)
-template <class P> static int load_f(myo_model* m, const uint8_t* blob, const char* name, P* out, std::vector<float>* keep = nullptr) {
-  const BlobRec* r = blob_find(blob, name);
-  if (!r || r->dtype != 0) return fail(MYO_E_BLOB, std::string("model blob lacks f64 array ") + name);
-  size_t n = r->nbytes / 8;
-  std::vector<float> v(n);
-  const double* src = (const double*)(blob + r->offset);
-  for (size_t i = 0; i < n; i++) v[i] = (float)src[i];
-  if (keep) *keep = v;
-  const float* tmp = nullptr;
-  int rc = upload<float>(m, v, &tmp);
-  *out = (P)tmp;
-  return rc;
-}
-template <class P> static int load_i(myo_model* m, const uint8_t* blob, const char* name, P* out, std::vector<int>* keep = nullptr) {
-  const BlobRec* r = blob_find(blob, name);
-  if (!r || r->dtype != 1) return fail(MYO_E_BLOB, std::string("model blob lacks i32 array ") + name);
-  size_t n = r->nbytes / 4;
-  std::vector<int> v(n);
-  memcpy(v.data(), blob + r->offset, n * 4);
-  if (keep) *keep = v;
-  const int* tmp = nullptr;
-  int rc = upload<int>(m, v, &tmp);
-  *out = (P)tmp;
-  return rc;
-}
-
-static void build_layout_w(const DevModel& d, DevModelW& w, int nvt, int kc, int nc, int nj = 3) {
-  w.lay = layout_w(w.nq, d.nv, d.nu, d.nl, d.ngt, d.maxnnz, d.ncg, w.has_tl != 0, nvt, kc, nc, nj);   // (myo_kernel_wave.h: shared with the compile-time layouts)
-}
-
-static void build_layout(DevModel& d) {
-  Lay& Y = d.lay;
-  int o = 0;
-  auto take = [&](int n) { int r = o; o += n; return r; };
-  int nv = d.nv, nu = d.nu, nl = d.nl, ntri = nv * (nv + 1) / 2;
-  Y.qpos = take(nv); Y.qvel = take(nv); Y.act = take(nu); Y.ctrl = take(nu); Y.warm = take(nv);
-  Y.lpos = take(3 * nl); Y.lmat = take(9 * nl); Y.lquat = take(4 * nl); Y.axis = take(3 * nv); Y.anchor = take(3 * nv);
-  Y.tJ = take(d.ngt * d.maxnnz); Y.tlen = take(d.ngt); Y.tforce = take(nu); Y.actdot = take(nu);
-  Y.qfa = take(nv); Y.smooth = take(nv); Y.qas = take(nv); Y.qacc = take(nv); Y.Ma = take(nv); Y.grad = take(nv);
-  Y.search = take(nv); Y.Mv = take(nv); Y.qfc = take(nv);
-  Y.Mp = take(ntri); Y.Hp = take(ntri);
-  Y.lsign = take(nv); Y.laref = take(nv); Y.lD = take(nv); Y.ljar = take(nv); Y.ljv = take(nv);
-  // region A (spatial dynamics) is dead once Mp / smooth exist; region B (collision + contact rows) aliases it
-  int regA = o;
-  Y.cdof = take(6 * nv); Y.cinert = take(10 * nl); Y.crb = take(10 * nl); Y.cvel = take(6 * nl); Y.cacc = take(6 * nl); Y.cfrc = take(6 * nl);
-  int endA = o;
-  o = regA;
-  Y.gpos = take(3 * d.ncg); Y.gmat = take(9 * d.ncg); Y.cand = take(NCAND);
-  Y.cdist = take(NCON); Y.cpos = take(3 * NCON); Y.cnrm = take(3 * NCON); Y.cpair = take(NCON); Y.cJ = take(NCON * 3 * KCMAX);
-  Y.caref = take(4 * NCON); Y.cD = take(NCON); Y.cjar = take(4 * NCON); Y.cjv = take(4 * NCON); Y.cimp = take(NCON);
-  if (o < endA) o = endA;
-  // pad so that the 64/G env slices start on different LDS banks
-  o = (o + 31) / 32 * 32 + 8;
-  Y.total = o;
-}
+#include "myo_host_model.h"
 
 extern "C" {
 
@@ -193,358 +41,20 @@ int myo_version(void) { return 1; }
 
 int myo_model_load(const void* blobv, size_t nbytes, int device, myo_model** out) {
   if (!blobv || !out || nbytes < 16) return fail(MYO_E_ARG, "myo_model_load: bad arguments");
-  const uint8_t* blob = (const uint8_t*)blobv;
+  const Blob B{(const uint8_t*)blobv};
   uint32_t ver;
-  memcpy(&ver, blob + 4, 4);
-  if (memcmp(blob, "MYOB", 4) || ver != 3) return fail(MYO_E_BLOB, "myo_model_load: not a MYOB v3 blob");
+  memcpy(&ver, B.p + 4, 4);
+  if (memcmp(B.p, "MYOB", 4) || ver != 3) return fail(MYO_E_BLOB, "myo_model_load: not a MYOB v3 blob");
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return fail(MYO_E_HIP, "myo_model_load: no such HIP device (a GPU is required; there is no CPU fallback)");
   HIPCHK(hipSetDevice(device));
-  myo_model* m = new myo_model();
+  std::unique_ptr<myo_model, void (*)(myo_model*)> m(new myo_model(), myo_model_free);   // a failed load frees what it had uploaded
   m->device = device;
   { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device) == hipSuccess) m->n_cu = prop.multiProcessorCount; }
-  DevModel& d = m->dm;
-  const BlobRec* hs = blob_find(blob, "hip_sizes");
-  const BlobRec* sz = blob_find(blob, "sizes");
-  const BlobRec* op = blob_find(blob, "opt");
-  if (!hs || !sz || !op) { delete m; return fail(MYO_E_BLOB, "myo_model_load: blob lacks hip_* tables (run lowering)"); }
-  const int* H = (const int*)(blob + hs->offset);
-  const int* S = (const int*)(blob + sz->offset);
-  const double* O = (const double*)(blob + op->offset);
-  d.nl = H[0]; d.nlevel = H[1]; d.nv = H[2]; d.nu = H[3]; d.ngt = H[4]; d.nseg = H[5]; d.maxnnz = H[7]; d.nwg = H[8];
-  d.ncg = H[9]; d.npair = H[10]; d.maxkc = H[11]; d.ns = H[12]; d.nM = S[11];
-  m->nq = S[0];
-  if (d.ngt != d.nu) { delete m; return fail(MYO_E_UNSUPPORTED, "limited-only tendons are not supported by the HIP path yet"); }
-  d.timestep = (float)O[0]; d.grav[0] = (float)O[1]; d.grav[1] = (float)O[2]; d.grav[2] = (float)O[3];
-  d.tolerance = (float)O[4]; d.iterations = (int)O[5]; d.ls_iterations = (int)O[6]; d.ls_tolerance = (float)O[7];
-  d.meaninertia = (float)O[9];
-  d.newton_scale = 1.0f / (d.meaninertia * (float)(d.nv > 1 ? d.nv : 1));
-  int rc = 0;
-  std::vector<float> c0, jl;
-  const float* tmp;
-#define LF(field, name) if ((rc = load_f(m, blob, name, &d.field))) { myo_model_free(m); return rc; }
-#define LI(field, name) if ((rc = load_i(m, blob, name, &d.field))) { myo_model_free(m); return rc; }
-  LI(level_adr, "hip_level_adr") LI(link_parent, "hip_link_parent") LI(link_dofadr, "hip_link_dofadr") LI(link_dofnum, "hip_link_dofnum")
-  LI(child_adr, "hip_child_adr") LI(child, "hip_child") LI(dof_link, "hip_dof_link") LI(dof_type, "hip_dof_type")
-  LI(dof_parent, "dof_parentid") LI(site_link, "hip_site_link") LI(wg_link, "hip_wg_link") LI(gt_seg_adr, "hip_gt_seg_adr")
-  LI(gt_seg_num, "hip_gt_seg_num") LI(gt_dofs, "hip_gt_dofs") LI(seg, "hip_seg") LI(dl, "hip_dl") LI(col_adr, "hip_col_adr")
-  LI(col, "hip_col") LI(cg_link, "hip_cg_link") LI(cg_type, "hip_cg_type") LI(pair_i, "hip_pair_i") LI(pair_dl, "hip_pair_dl")
-  LF(link_pos, "hip_link_pos") LF(link_quat, "hip_link_quat") LF(link_mass, "hip_link_mass") LF(link_com, "hip_link_com")
-  LF(link_inertia, "hip_link_inertia") LF(dof_pos, "hip_dof_pos") LF(dof_axis, "hip_dof_axis") LF(dof_damping, "dof_damping")
-  LF(dof_armature, "dof_armature") LF(site_lpos, "hip_site_lpos") LF(wg_lpos, "hip_wg_lpos") LF(wg_lmat, "hip_wg_lmat")
-  LF(wg_radius, "hip_wg_radius") LF(seg_div, "hip_seg_div") LF(gt_len0, "hip_gt_len0") LF(act, "hip_act") LF(cg_lpos, "hip_cg_lpos") LF(cg_lmat, "hip_cg_lmat")
-  LF(cg_size, "hip_cg_size") LF(cg_rbound, "hip_cg_rbound") LF(pair_f, "hip_pair_f")
-#undef LF
-#undef LI
-  if ((rc = load_f(m, blob, "qpos0", &d.qpos0, &m->qpos0))) { myo_model_free(m); return rc; }
-  if ((rc = load_f(m, blob, "hip_jl", &d.jl, &jl))) { myo_model_free(m); return rc; }
-  if ((rc = load_f(m, blob, "hip_c0", &tmp, &c0))) { myo_model_free(m); return rc; }
-  d.c0[0] = c0[0]; d.c0[1] = c0[1]; d.c0[2] = c0[2];
-  {
-    std::vector<float> org;
-    if ((rc = load_f(m, blob, "hip_origin", &tmp, &org))) { myo_model_free(m); return rc; }
-    d.origin[0] = org[0]; d.origin[1] = org[1]; d.origin[2] = org[2];
-  }
-  m->jnt_lo.resize(d.nv); m->jnt_hi.resize(d.nv);
-  for (int i = 0; i < d.nv; i++) { m->jnt_lo[i] = jl[12 * i + 1]; m->jnt_hi[i] = jl[12 * i + 2]; }
-  build_layout(d);
-  m->env_lds_bytes = d.lay.total * 4;
-  {  // wave-per-env kernel tables (one env per wavefront, nv <= 24)
-    DevModelW& w = m->dw;
-    std::vector<int> nws;
-    const int* tmpi;
-    if ((rc = load_i(m, blob, "hip_seg_order", &w.seg_order)) || (rc = load_i(m, blob, "hip_seg_tendon", &w.seg_tendon)) ||
-        (rc = load_i(m, blob, "hip_gt_dl", &w.gt_dl)) || (rc = load_f(m, blob, "hip_link_mat0", &w.link_mat0)) ||
-        (rc = load_i(m, blob, "hip_nwrapseg", &tmpi, &nws))) { myo_model_free(m); return rc; }
-    w.nwrapseg = nws[0];
-    w.ndl = H[6];
-    {
-      std::vector<float> tlv;
-      if ((rc = load_f(m, blob, "hip_tl", &w.tl, &tlv))) { myo_model_free(m); return rc; }
-      w.has_tl = 0;
-      for (int t = 0; t < d.ngt; t++) if (tlv[12 * t] != 0) w.has_tl = 1;
-      m->has_tl = w.has_tl;
-    }
-    bool plane_pairs = false, condim1 = false;
-    {
-      std::vector<int> fl, pi;
-      if ((rc = load_i(m, blob, "hip_flags", &tmpi, &fl)) || (rc = load_i(m, blob, "hip_link_free", &w.link_free)) ||
-          (rc = load_i(m, blob, "hip_dof_qposadr", &w.dof_qposadr)) || (rc = load_i(m, blob, "hip_link_chain_adr", &w.link_chain_adr)) ||
-          (rc = load_i(m, blob, "hip_link_chain", &w.link_chain)) || (rc = load_i(m, blob, "hip_eq_i", &w.eq_i)) ||
-          (rc = load_i(m, blob, "hip_kin_base", &w.kin_base)) || (rc = load_i(m, blob, "hip_kin_adr", &w.kin_adr)) || (rc = load_i(m, blob, "hip_kin_vec", &w.kin_vec)) ||
-          (rc = load_f(m, blob, "hip_eq_f", &w.eq_f)) || (rc = load_i(m, blob, "hip_pair_i", &tmpi, &pi))) { myo_model_free(m); return rc; }
-      {
-        std::vector<int> ks;
-        if ((rc = load_i(m, blob, "hip_kin_size", &tmpi, &ks))) { myo_model_free(m); return rc; }
-        m->kin_floats = ks[0];   // checked against the Hessian scratch (nvt x (nvt + 1)) once the kernel class is known
-        w.kin_dnmax = ks.size() > 1 ? ks[1] : 6;
-      }
-      w.has_free = fl[0]; w.nq = fl[1]; w.neq = fl[2];
-      if (fl.size() < 6) { myo_model_free(m); return fail(MYO_E_BLOB, "hip_flags: blob predates the actuator-kind tables; recompile the model"); }
-      w.has_j0 = fl[3]; d.na_obs = fl[4]; m->has_affine = fl[5] != 0;
-      { const int* t2; if ((rc = load_i(m, blob, "hip_cg_geom", &t2, &m->cg_geom)) || (rc = load_i(m, blob, "hip_cg_type", &t2, &m->cg_type_h))) { myo_model_free(m); return rc; } }
-      {
-        std::vector<int> hi; std::vector<float> hf; const float* tf2;
-        if ((rc = load_i(m, blob, "hip_hf_i", &tmpi, &hi)) || (rc = load_f(m, blob, "hip_hf_f", &tf2, &hf))) { myo_model_free(m); return rc; }
-        w.hf.on = hi[0]; w.hf.nrow = hi[1]; w.hf.ncol = hi[2]; w.hf.cg = hi[3];
-        for (int k = 0; k < 4; k++) w.hf.size[k] = hf[k];
-        for (int k = 0; k < 3; k++) w.hf.pos[k] = hf[4 + k];
-        if (w.hf.on && (w.hf.nrow > 128 || w.hf.ncol > 100 || d.npair > 1023)) { myo_model_free(m); return fail(MYO_E_UNSUPPORTED, "height field: at most 128 x 100 cells and 1023 pairs"); }
-      }
-      if ((rc = load_f(m, blob, "hip_gt_j0", &w.gt_j0)) || (rc = load_i(m, blob, "hip_act_obs", &d.act_obs))) { myo_model_free(m); return rc; }
-      const float* tf;
-      if ((rc = load_i(m, blob, "hip_body_link", &tmpi, &m->body_link)) || (rc = load_f(m, blob, "hip_body_lpos", &tf, &m->body_lpos)) ||
-          (rc = load_f(m, blob, "hip_body_lquat", &tf, &m->body_lquat)) || (rc = load_f(m, blob, "hip_mass", &tf, &m->mass))) { myo_model_free(m); return rc; }
-      if (w.nq != m->nq) { myo_model_free(m); return fail(MYO_E_BLOB, "hip_flags disagrees with sizes"); }
-      for (int p = 0; p < d.npair; p++) { if (pi[6 * p + 4] >= 2) plane_pairs = true; if (pi[6 * p + 5] == 1) condim1 = true; }
-      // the 16/32-lane generic kernel covers fixed-base models with hinge / slide joints and capsule / convex pairs only
-      m->generic_ok = !w.has_free && w.neq == 0 && !plane_pairs && !condim1 && w.nq == d.nv && d.maxkc <= KCMAX && !w.has_tl && !m->has_affine;
-    }
-    // TrackEnv model class (lowering: hip_trk = condim-4 pairs | friction loss | box / hull geoms): tables of the TRK instantiation
-    w.fl = nullptr; w.mesh_vert = nullptr; w.mesh_rec = nullptr; w.mesh_startrec = nullptr; w.mesh_aabb = nullptr;
-    m->trk = false;
-    if (blob_find(blob, "hip_trk")) {
-      std::vector<int> tk;
-      if ((rc = load_i(m, blob, "hip_trk", &tmpi, &tk)) || (rc = load_f(m, blob, "hip_fl", &w.fl)) || (rc = load_f(m, blob, "hip_mesh_vert", &w.mesh_vert)) ||
-          (rc = load_f(m, blob, "hip_mesh_rec", &w.mesh_rec)) || (rc = load_f(m, blob, "hip_mesh_startrec", &w.mesh_startrec)) || (rc = load_f(m, blob, "hip_mesh_aabb", &w.mesh_aabb))) { myo_model_free(m); return rc; }
-      m->trk = tk[0] || tk[1] || tk[2];
-      if (m->trk) {   // bodies of MYO_F_BODYQUAT: the tree, compiled poses, and the body of every collision geom and site
-        auto BI = [&](const char* n) { std::vector<int> v; const BlobRec* r = blob_find(blob, n); if (r && r->dtype == 1) { v.resize(r->nbytes / 4); memcpy(v.data(), blob + r->offset, r->nbytes); } return v; };
-        auto BD = [&](const char* n) { std::vector<double> v; const BlobRec* r = blob_find(blob, n); if (r && r->dtype == 0) { v.resize(r->nbytes / 8); memcpy(v.data(), blob + r->offset, r->nbytes); } return v; };
-        const std::vector<int> gb = BI("geom_bodyid");
-        m->body_parent = BI("body_parentid"); m->body_jntnum = BI("body_jntnum"); m->site_body = BI("site_bodyid");
-        m->body_pos0 = BD("body_pos"); m->body_quat0 = BD("body_quat"); m->site_pos0 = BD("site_pos");
-        for (int g : m->cg_geom) m->cg_body.push_back(g >= 0 && g < (int)gb.size() ? gb[g] : -1);
-      }
-      if (m->trk) {   // the root body of MYO_F_BODYPOS: the body of the last joint, a child of the world at the origin of its own root link
-        auto BI = [&](const char* n) { std::vector<int> v; const BlobRec* r = blob_find(blob, n); if (r && r->dtype == 1) { v.resize(r->nbytes / 4); memcpy(v.data(), blob + r->offset, r->nbytes); } return v; };
-        const std::vector<int> jb = BI("jnt_bodyid"), jt = BI("jnt_type"), bp = BI("body_parentid"), bl = BI("hip_body_link"), lpar = BI("hip_link_parent");
-        const int bb = jb.empty() ? -1 : jb.back();
-        if (bb > 0 && jt.size() == jb.size() && (jt.back() == 2 || jt.back() == 3)   // a slide / hinge (a free root takes its pose from qpos)
-            && bb < (int)bp.size() && bb < (int)bl.size() && bp[bb] == 0) {
-          const int l = bl[bb];
-          bool head = l >= 0 && l < (int)lpar.size() && lpar[l] < 0;
-          for (int k = 1; head && k < bb; k++) if (bl[k] == l) head = false;   // the body heads its link (no earlier body welded into it)
-          if (head) m->bp_link = l;
-        }
-      }
-    }
-    {  // plane - cylinder and plane - sphere pairs (lowering.py pair types 6 / 7 and 8) have a narrow phase in the TRK instantiation only: never
-       // dropped silently
-      std::vector<int> pi2;
-      const int* t3;
-      if ((rc = load_i(m, blob, "hip_pair_i", &t3, &pi2))) { myo_model_free(m); return rc; }
-      for (int p = 0; p < d.npair; p++) {
-        if ((pi2[6 * p + 4] == 6 || pi2[6 * p + 4] == 7) && !m->trk) { myo_model_free(m); return fail(MYO_E_UNSUPPORTED, "plane - cylinder pairs need a model of the TrackEnv class"); }
-        if (pi2[6 * p + 4] == 8 && !m->trk) { myo_model_free(m); return fail(MYO_E_UNSUPPORTED, "plane - sphere pairs need a model of the TrackEnv class"); }
-      }
-    }
-    {  // self-contained per-lane records (DevModelW::seg_rec, dl_pk, ...): denormalised copies of the tables loaded above
-      auto BI = [&](const char* n) { std::vector<int> v; const BlobRec* r = blob_find(blob, n); if (r && r->dtype == 1) { v.resize(r->nbytes / 4); memcpy(v.data(), blob + r->offset, r->nbytes); } return v; };
-      auto BF = [&](const char* n) { std::vector<float> v; const BlobRec* r = blob_find(blob, n); if (r && r->dtype == 0) { v.resize(r->nbytes / 8); const double* sp = (const double*)(blob + r->offset); for (size_t i = 0; i < v.size(); i++) v[i] = (float)sp[i]; } return v; };
-      const std::vector<int> seg = BI("hip_seg"), seg_order = BI("hip_seg_order"), seg_tendon = BI("hip_seg_tendon"), site_link = BI("hip_site_link"), wg_link = BI("hip_wg_link"),
-                             dl = BI("hip_dl"), dof_type = BI("hip_dof_type");
-      const std::vector<float> seg_div = BF("hip_seg_div"), site_lpos = BF("hip_site_lpos"), wg_lpos = BF("hip_wg_lpos"), wg_lmat = BF("hip_wg_lmat"), wg_radius = BF("hip_wg_radius");
-      auto fi = [](int v) { float f; memcpy(&f, &v, 4); return f; };
-      std::vector<int> dlp(std::max<size_t>(dl.size() / 3, 1), 0);
-      for (size_t i = 0; i < dl.size() / 3; i++) {
-        const int dd = dl[3 * i], sg = dl[3 * i + 1], slot = dl[3 * i + 2];
-        if (dd < 0 || dd > 127 || slot < 0 || slot > 255 || sg < -32768 || sg > 32767) { myo_model_free(m); return fail(MYO_E_UNSUPPORTED, "moment-arm list entry does not fit the packed word"); }
-        dlp[i] = dd | ((dof_type[dd] == 3 ? 1 : 0) << 7) | (slot << 8) | (int)((unsigned)sg << 16);
-      }
-      // (each segment's three lists are copied to 16-byte rows of their own: a lane reads a list four entries per load, the first row ahead of its use)
-      std::vector<int> dl4;
-      std::vector<float> rec((size_t)std::max(d.nseg, 1) * SEGR * 4, 0.f);
-      for (int idx = 0; idx < d.nseg; idx++) {
-        const int si = seg_order[idx];
-        const int* S = &seg[12 * (size_t)si];
-        float* R = &rec[(size_t)idx * SEGR * 4];
-        for (int k = 0; k < 2; k++) { R[4 * k] = fi(site_link[S[k]]); for (int c = 0; c < 3; c++) R[4 * k + 1 + c] = site_lpos[3 * (size_t)S[k] + c]; }
-        R[8] = fi(S[2]); R[9] = fi(S[3] >= 0 ? site_link[S[3]] : -2); R[10] = 1.0f / seg_div[si]; R[11] = fi(seg_tendon[si]);
-        for (int k = 0; k < 3; k++) {
-          const int a0 = S[4 + 2 * k], n = S[5 + 2 * k], adr4 = (int)(dl4.size() / 4);
-          if (adr4 >= (1 << 20) || n < 0 || n >= (1 << 11) || (n > 0 && (a0 < 0 || (size_t)(a0 + n) > dl.size() / 3))) { myo_model_free(m); return fail(MYO_E_UNSUPPORTED, "tendon moment-arm lists too long for the packed segment record"); }
-          for (int i = 0; i < n; i++) dl4.push_back(dlp[a0 + i]);
-          while (dl4.size() % 4 || dl4.size() == (size_t)adr4 * 4) dl4.push_back(0);     // whole rows; an empty list still owns one (the lane loads it unconditionally)
-          R[12 + k] = fi(adr4 | (n << 20));
-        }
-        R[15] = fi(S[10]);
-        if (S[2] >= 0) {
-          const int g = S[2];
-          if (S[3] >= 0) for (int c = 0; c < 3; c++) R[16 + c] = site_lpos[3 * (size_t)S[3] + c];
-          R[19] = wg_radius[g];
-          R[20] = fi(wg_link[g]); for (int c = 0; c < 3; c++) R[21 + c] = wg_lpos[3 * (size_t)g + c];
-          for (int c = 0; c < 9; c++) R[24 + c] = wg_lmat[9 * (size_t)g + c];
-        }
-      }
-      const float* tf4 = nullptr; const int* ti4 = nullptr;
-      if (dl4.empty()) dl4.resize(4, 0);
-      if ((rc = upload<float>(m, rec, &tf4)) || (rc = upload<int>(m, dl4, &ti4))) { myo_model_free(m); return rc; }
-      w.seg_rec = (decltype(w.seg_rec))tf4; w.dl_pk = (decltype(w.dl_pk))ti4;
-      // collision geoms, pairs and the pairs' dof lists
-      const std::vector<int> cg_link = BI("hip_cg_link"), cg_type = BI("hip_cg_type"), pair_i = BI("hip_pair_i"), pair_dl = BI("hip_pair_dl");
-      const std::vector<float> cg_lpos = BF("hip_cg_lpos"), cg_lmat = BF("hip_cg_lmat"), cg_size = BF("hip_cg_size"), cg_rb = BF("hip_cg_rbound"), pair_f = BF("hip_pair_f");
-      std::vector<float> grec((size_t)std::max(d.ncg, 1) * 16, 0.f), prec((size_t)std::max(d.npair, 1) * 16, 0.f);
-      for (int g = 0; g < d.ncg; g++) {
-        float* R = &grec[(size_t)g * 16];
-        R[0] = fi(cg_link[g]); for (int c = 0; c < 3; c++) R[1 + c] = cg_lpos[3 * (size_t)g + c];
-        for (int c = 0; c < 9; c++) R[4 + c] = cg_lmat[9 * (size_t)g + c];
-        R[13] = fi(cg_type[g]); R[14] = cg_rb[g];
-      }
-      for (int q = 0; q < d.npair; q++) {
-        const int* P = &pair_i[6 * (size_t)q];
-        const float* F = &pair_f[12 * (size_t)q];
-        if (P[0] > 255 || P[1] > 255 || P[3] > 255 || P[4] > 15 || P[5] > 15) { myo_model_free(m); return fail(MYO_E_UNSUPPORTED, "collision pair does not fit the packed pair record"); }
-        float* R = &prec[(size_t)q * 16];
-        R[0] = fi(P[0] | (P[1] << 8) | (P[4] << 16) | (P[5] << 20) | (P[3] << 24)); R[1] = F[0]; R[2] = F[1]; R[3] = fi(P[2]);
-        for (int c = 0; c < 3; c++) { R[4 + c] = cg_size[3 * (size_t)P[0] + c]; R[8 + c] = cg_size[3 * (size_t)P[1] + c]; }
-        R[7] = cg_rb[P[0]]; R[11] = cg_rb[P[1]];
-        R[12] = fi(cg_type[P[0]] | (cg_type[P[1]] << 8));
-      }
-      // (a contact carries pair | dofs << 11 | dof-list start << 16 in one word: step kernel, narrow phase -> row stage)
-      if (d.npair > 2048 || pair_dl.size() / 2 >= (1u << 16) || d.maxkc > 31) { myo_model_free(m); return fail(MYO_E_UNSUPPORTED, "more than 2048 collision pairs, 65535 contact dof-list entries or 31 dofs per contact"); }
-      std::vector<int> pdl(std::max<size_t>(pair_dl.size() / 2, 1), 0);
-      for (size_t i = 0; i < pair_dl.size() / 2; i++) {
-        const int dd = pair_dl[2 * i], sg = pair_dl[2 * i + 1];
-        if (dd < 0 || dd > 127 || sg < -(1 << 22) || sg > (1 << 22)) { myo_model_free(m); return fail(MYO_E_UNSUPPORTED, "contact dof-list entry does not fit the packed word"); }
-        pdl[i] = dd | ((dof_type[dd] == 3 ? 1 : 0) << 7) | (int)((unsigned)sg << 8);
-      }
-      const float *tg4 = nullptr, *tp4 = nullptr; const int* tq4 = nullptr;
-      if ((rc = upload<float>(m, grec, &tg4)) || (rc = upload<float>(m, prec, &tp4)) || (rc = upload<int>(m, pdl, &tq4))) { myo_model_free(m); return rc; }
-      w.cg_rec = (decltype(w.cg_rec))tg4; w.pair_rec = (decltype(w.pair_rec))tp4; w.pair_dl_pk = (decltype(w.pair_dl_pk))tq4;
-      // tree words: one packed word per lane and round for the sweeps over the kinematic tree (DevModelW::kin_pk, link_desc, link_adof, dof_anc)
-      {
-        const std::vector<int> lpar = BI("hip_link_parent"), dlink = BI("hip_dof_link"), dpar = BI("dof_parentid"), kadr = BI("hip_kin_adr"), kvec = BI("hip_kin_vec"),
-                               chadr = BI("hip_link_chain_adr"), chain = BI("hip_link_chain");
-        if (d.nl > 64 || d.nv > 64) { myo_model_free(m); return fail(MYO_E_UNSUPPORTED, "more than 64 links or dofs"); }
-        std::vector<int> kpk;
-        for (size_t L = 0; L + 1 < kadr.size(); L++) {
-          for (int e0 = kadr[L]; e0 < kadr[L + 1]; e0 += 64) {
-            for (int i = 0; i < 64; i++) {
-              const int e = e0 + i;
-              if (e >= kadr[L + 1]) { kpk.push_back(-1); continue; }
-              const int w0 = kvec[2 * (size_t)e], src = kvec[2 * (size_t)e + 1], l = w0 & 255, kind = (w0 >> 8) & 3, ix = w0 >> 16, par1 = lpar[l] + 1;
-              if (src < 0 || src >= 2048 || l >= 64 || ix < 0 || ix >= 64 || par1 < 0 || par1 > 64) { myo_model_free(m); return fail(MYO_E_UNSUPPORTED, "kinematics entry does not fit the packed word"); }
-              kpk.push_back((int)((unsigned)src | ((unsigned)l << 11) | ((unsigned)kind << 17) | ((unsigned)ix << 19) | ((unsigned)par1 << 25)));
-            }
-          }
-        }
-        w.kin_nround = (int)(kpk.size() / 64);
-        kpk.resize(kpk.size() + 64, -1);                       // padding round: the loop prefetches one round ahead
-        std::vector<unsigned long long> desc(d.nl, 0), adof(d.nl, 0), anc(d.nv, 0);
-        for (int l = d.nl - 1; l >= 0; l--) { desc[l] |= 1ull << l; if (lpar[l] >= 0) { if (lpar[l] >= l) { myo_model_free(m); return fail(MYO_E_BLOB, "links are not in tree order"); } desc[lpar[l]] |= desc[l]; } }
-        for (int q = 0; q < d.nv; q++) { if (dpar[q] >= q) { myo_model_free(m); return fail(MYO_E_BLOB, "dofs are not in tree order"); } anc[q] = (1ull << q) | (dpar[q] >= 0 ? anc[dpar[q]] : 0ull); }
-        unsigned long long frot = 0, fj3 = 0;
-        for (int l = 0; l < d.nl; l++) {
-          int prev = -1;
-          for (int c = chadr[l]; c < chadr[l + 1]; c++) {
-            const int e = chain[c], q = e & 255, j = (e >> 8) & 7, fr = e >> 12;
-            if (q <= prev || q >= d.nv) { myo_model_free(m); return fail(MYO_E_BLOB, "link dof chain is not root-first"); }
-            prev = q;
-            adof[l] |= 1ull << q;
-            if (fr && j >= 3) frot |= 1ull << q;
-            if (fr && j == 3) fj3 |= 1ull << q;
-          }
-        }
-        w.free_rot[0] = (unsigned)frot; w.free_rot[1] = (unsigned)(frot >> 32); w.free_j3[0] = (unsigned)fj3; w.free_j3[1] = (unsigned)(fj3 >> 32);
-        auto split = [](const std::vector<unsigned long long>& v) { std::vector<int> o(std::max<size_t>(2 * v.size(), 2), 0); for (size_t i = 0; i < v.size(); i++) { o[2 * i] = (int)(unsigned)v[i]; o[2 * i + 1] = (int)(unsigned)(v[i] >> 32); } return o; };
-        const int *t0 = nullptr, *t1 = nullptr, *t2 = nullptr, *t3 = nullptr;
-        if ((rc = upload<int>(m, kpk, &t0)) || (rc = upload<int>(m, split(desc), &t1)) || (rc = upload<int>(m, split(adof), &t2)) || (rc = upload<int>(m, split(anc), &t3))) { myo_model_free(m); return rc; }
-        w.kin_pk = (decltype(w.kin_pk))t0; w.link_desc = (decltype(w.link_desc))t1; w.link_adof = (decltype(w.link_adof))t2; w.dof_anc = (decltype(w.dof_anc))t3;
-      }
-    }
-    const bool common = d.nl <= 64 && d.ncg <= (m->trk ? 128 : 64) && w.nq <= 64 && w.neq <= 64 && d.maxnnz <= 20;   // (geom ids are bytes in the pair record; the TRK kernel loops over geoms)
-    const bool needs_full = w.has_free || w.neq > 0 || plane_pairs || condim1 || m->trk;
-    if (m->trk) {
-      if (!(common && d.nv <= 36 && d.nu <= 128 && d.ngt <= 128 && d.maxkc <= 20 && !w.hf.on && !w.has_tl)) { myo_model_free(m); return fail(MYO_E_UNSUPPORTED, "condim-4 / friction-loss / box / mesh model exceeds the limits of the TRK step kernel"); }
-      m->wave_ok = true; m->wave_cfg = 2; m->generic_ok = false;
-      build_layout_w(d, w, 36, 20, 32, 4);
-    }
-    else if (common && !needs_full && d.nv <= 24 && d.nu <= 64 && d.ngt <= 64 && d.maxkc <= 8) {
-      m->wave_ok = true; m->wave_cfg = 0;
-      build_layout_w(d, w, 24, 8, 32);
-    }
-    else if (common && d.nv <= 36 && d.nu <= 128 && d.ngt <= 128 && d.maxkc <= 20) { m->wave_ok = true; m->wave_cfg = 1; build_layout_w(d, w, 36, 20, 32); }
-    else { m->wave_ok = false; build_layout_w(d, w, 24, 8, 32); }
-    m->hand_sizes = m->wave_ok && m->wave_cfg == 0 && sizes_match<1>(w.nq, d.nv, d.nu, d.nl, d.nlevel, d.maxnnz, d.ngt, d.nseg, d.ncg, d.npair);
-    if (m->trk) m->generic_ok = false;
-    if (blob_find(blob, "integrator")) { std::vector<int> ig; if ((rc = load_i(m, blob, "integrator", &tmpi, &ig))) { myo_model_free(m); return rc; } m->rk4 = !ig.empty() && ig[0] == 1; }
-    if (m->rk4) {
-      if (!m->wave_ok || m->trk || w.hf.on) { myo_model_free(m); return fail(MYO_E_UNSUPPORTED, "RK4: wave kernel models without height field / TrackEnv features only"); }
-      m->generic_ok = false;
-    }
-    m->leg_sizes = m->wave_ok && m->wave_cfg == 1 && sizes_match<2>(w.nq, d.nv, d.nu, d.nl, d.nlevel, d.maxnnz, d.ngt, d.nseg, d.ncg, d.npair);
-    m->terrain_sizes = m->wave_ok && m->wave_cfg == 1 && w.hf.on && sizes_match<3>(w.nq, d.nv, d.nu, d.nl, d.nlevel, d.maxnnz, d.ngt, d.nseg, d.ncg, d.npair);
-    {  // the specialised instantiations also build in the dof tree (tree-sparse factorisation): it must be the model's
-      std::vector<int> dpar;
-      if ((rc = load_i(m, blob, "dof_parentid", &tmpi, &dpar))) { myo_model_free(m); return rc; }
-      auto same_tree = [&](const int* ref, int n) { if ((int)dpar.size() != n) return false; for (int i = 0; i < n; i++) if (dpar[i] != ref[i]) return false; return true; };
-      if (m->hand_sizes && !same_tree(SpecTree<1>::parent, SpecTree<1>::nv)) m->hand_sizes = false;
-      if ((m->leg_sizes || m->terrain_sizes) && !same_tree(SpecTree<2>::parent, SpecTree<2>::nv)) m->leg_sizes = m->terrain_sizes = false;
-    }
-    if (m->rk4) m->hand_sizes = m->leg_sizes = m->terrain_sizes = false;
-    if (w.has_tl) m->hand_sizes = m->leg_sizes = m->terrain_sizes = false;   // the specialised instantiations compile the tendon-limit rows out
-    // ... and their LDS layout in: it must be the one this model was given
-    if (m->hand_sizes && !layout_match<1, 24, 8, 32, 3>(w.lay)) m->hand_sizes = false;
-    if (m->leg_sizes && !layout_match<2, 36, 20, 32, 3>(w.lay)) m->leg_sizes = false;
-    if (m->terrain_sizes && !layout_match<3, 36, 20, 32, 3>(w.lay)) m->terrain_sizes = false;
-    if (const char* e = getenv("MYO_NO_SPEC")) if (atoi(e) == 1) m->hand_sizes = m->leg_sizes = m->terrain_sizes = false;   // tests: force the run-time-sized instantiations
-    if (!m->wave_ok && !m->generic_ok) { myo_model_free(m); return fail(MYO_E_UNSUPPORTED, "model exceeds the limits of both step kernels (nv <= 36, nu <= 128, pair dofs <= 20)"); }
-    { const int nvt = m->wave_cfg == 0 ? 24 : 36;
-      if (m->wave_ok && m->kin_floats > nvt * (nvt + 1)) { myo_model_free(m); return fail(MYO_E_UNSUPPORTED, "kinematics scratch exceeds the Hessian scratch it borrows"); } }
-    m->env_lds_bytes_w = w.lay.total * 4;
-    if (m->wave_ok && m->env_lds_bytes_w > 64 * 1024) { myo_model_free(m); return fail(MYO_E_UNSUPPORTED, "wave kernel working set exceeds 64 KB of LDS"); }
-    void* p1 = nullptr; void* p2 = nullptr;
-    if (hipMalloc(&p1, sizeof(DevModel)) != hipSuccess || hipMalloc(&p2, sizeof(DevModelW)) != hipSuccess) { myo_model_free(m); return fail(MYO_E_NOMEM, "hipMalloc model structs"); }
-    m->dev_allocs.push_back(p1); m->dev_allocs.push_back(p2);
-    m->d_dm = (DevModel*)p1; m->d_dw = (DevModelW*)p2;
-    if (hipMemcpy(p1, &d, sizeof(DevModel), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(p2, &w, sizeof(DevModelW), hipMemcpyHostToDevice) != hipSuccess) { myo_model_free(m); return fail(MYO_E_HIP, "upload model structs"); }
-  }
-  m->dims = myo_dims{S[0], S[1], S[2], d.na_obs, S[4], S[8], S[7], d.nl, 0, m->wave_ok ? m->env_lds_bytes_w : m->env_lds_bytes, 64,
-                     m->wave_ok ? (m->wave_cfg >= 1 ? 32 : NCONW) : NCON, d.timestep};
-  if (4 * m->env_lds_bytes > 160 * 1024) {
-    if (!m->wave_ok) { myo_model_free(m); return fail(MYO_E_UNSUPPORTED, "model working set exceeds 160 KB of LDS per workgroup"); }
-    m->generic_ok = false;
-  }
-  if (m->wave_ok && !m->body_link.empty()) {   // member tables of the per-env body-mass override (lowering.py's link recomposition, per body)
-    auto f64 = [&](const char* n) { std::vector<double> v; const BlobRec* r = blob_find(blob, n); if (r && r->dtype == 0) { v.resize(r->nbytes / 8); memcpy(v.data(), blob + r->offset, r->nbytes); } return v; };
-    const std::vector<double> bmass = f64("body_mass"), ipos = f64("body_ipos"), iquat = f64("body_iquat"), inert = f64("body_inertia"),
-                              lpos = f64("hip_body_lpos"), lquat = f64("hip_body_lquat");
-    const int nb = (int)m->body_link.size();
-    if ((int)bmass.size() == nb && (int)ipos.size() == 3 * nb && (int)iquat.size() == 4 * nb && (int)inert.size() == 3 * nb &&
-        (int)lpos.size() == 3 * nb && (int)lquat.size() == 4 * nb) {
-      auto qmat = [](const double* q, double* R) {
-        const double w = q[0], x = q[1], y = q[2], z = q[3];
-        R[0] = w * w + x * x - y * y - z * z; R[1] = 2 * (x * y - w * z); R[2] = 2 * (x * z + w * y);
-        R[3] = 2 * (x * y + w * z); R[4] = w * w - x * x + y * y - z * z; R[5] = 2 * (y * z - w * x);
-        R[6] = 2 * (x * z - w * y); R[7] = 2 * (y * z + w * x); R[8] = w * w - x * x - y * y + z * z;
-      };
-      std::vector<int> adr(d.nl + 1, 0), body;
-      std::vector<double> tab;
-      for (int l = 0; l < d.nl; l++) {
-        adr[l] = (int)body.size();
-        for (int b = 1; b < nb; b++) {
-          if (m->body_link[b] != l) continue;
-          double Rl[9], Rq[9], Ri[9], c[3], I[9];
-          qmat(&lquat[4 * b], Rl); qmat(&iquat[4 * b], Rq);
-          for (int i = 0; i < 3; i++) {
-            c[i] = lpos[3 * b + i];
-            for (int j = 0; j < 3; j++) { c[i] += Rl[3 * i + j] * ipos[3 * b + j]; Ri[3 * i + j] = Rl[3 * i] * Rq[j] + Rl[3 * i + 1] * Rq[3 + j] + Rl[3 * i + 2] * Rq[6 + j]; }
-          }
-          for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) I[3 * i + j] = Ri[3 * i] * inert[3 * b] * Ri[3 * j] + Ri[3 * i + 1] * inert[3 * b + 1] * Ri[3 * j + 1] + Ri[3 * i + 2] * inert[3 * b + 2] * Ri[3 * j + 2];
-          body.push_back(b);
-          for (double v : {c[0], c[1], c[2], I[0], I[4], I[8], I[1], I[2], I[5], bmass[b]}) tab.push_back(v);
-        }
-      }
-      adr[d.nl] = (int)body.size();
-      int rc2;
-      if ((rc2 = upload<int>(m, adr, &m->d_lm_adr)) || (rc2 = upload<int>(m, body, &m->d_lm_body)) || (rc2 = upload<double>(m, tab, &m->d_lm_tab))) { myo_model_free(m); return rc2; }
-      m->body_mass0.assign(bmass.begin(), bmass.end());
-    }
-  }
-  *out = m;
+  const int rc = load_model(m.get(), B);
+  if (rc) return rc;
+  *out = m.release();
   return MYO_OK;
 }
 
@@ -645,7 +155,7 @@ void myo_batch_free(myo_batch* b) {
 int myo_batch_size(const myo_batch* b) { return b ? b->db.B : 0; }
 
 static int set_quat_body(myo_batch* b, int body);   // (below, with the rest of MYO_F_BODYQUAT)
-static void quat2mat_d(double* R, const double* q);
+static const TaskHooks* task_hooks(int task);       // (below, after the launches the hooks make)
 
 int myo_batch_configure(myo_batch* b, const myo_task_config* c) {
   if (!b || !c) return fail(MYO_E_ARG, "myo_batch_configure: null");
@@ -671,87 +181,10 @@ int myo_batch_configure(myo_batch* b, const myo_task_config* c) {
   for (int i = 0; i < 8; i++) T.tip_site[i] = c->tip_site[i];
   T.pose_thd = c->pose_thd; T.far_th = c->far_th; T.near_th = c->near_th;
   T.w_pose = c->w_pose; T.w_bonus = c->w_bonus; T.w_act_reg = c->w_act_reg; T.w_penalty = c->w_penalty; T.w_reach = c->w_reach;
-  if (c->task == MYO_TASK_POSE) { if (c->ntarget != nv) return fail(MYO_E_ARG, "pose task: ntarget must equal nq"); T.obs_dim = 3 * nv + b->model->dm.na_obs; }
-  else if (c->task == MYO_TASK_REACH) { if (c->ntarget != 3 * c->ntip) return fail(MYO_E_ARG, "reach task: ntarget must be 3*ntip"); T.obs_dim = 2 * nv + 6 * c->ntip + b->model->dm.na_obs; }
-  else if (c->task == MYO_TASK_STAND) {
-    if (c->ntarget != 3) return fail(MYO_E_ARG, "stand task: ntarget must be 3 (target position)");
-    if (!(b->model->wave_ok && b->model->dw.has_free && b->model->nq == nv + 1)) return fail(MYO_E_UNSUPPORTED, "stand task needs a model with a free root joint");
-    T.obs_dim = b->model->nq + nv + 6 + b->model->dm.na_obs;
-  }
-  else if (c->task == MYO_TASK_KEYTURN) {
-    // key_turn_v0.py: the key is the model's last joint, one hinge of a root body; sites = key head, index tip, thumb tip
-    const myo_model* m = b->model;
-    if (!(m->wave_ok && m->trk) || m->bp_link < 0 || m->nq != nv) return fail(MYO_E_UNSUPPORTED, "key-turn task: a TrackEnv-class model without free / ball joints whose last joint is the hinge of a root body");
-    std::vector<int> ltype(1), ldn(1), ldof(1);
-    HIPCHK(hipMemcpy(ltype.data(), dm.dof_type + (nv - 1), 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(ldn.data(), dm.link_dofnum + m->bp_link, 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(ldof.data(), dm.dof_link + (nv - 1), 4, hipMemcpyDeviceToHost));
-    if (ltype[0] != 3 || ldn[0] != 1 || ldof[0] != m->bp_link) return fail(MYO_E_UNSUPPORTED, "key-turn task: the last joint must be the one hinge of its root body");
-    if (c->ntip != 3 || c->ntarget != 0) return fail(MYO_E_ARG, "key-turn task: ntip = 3 (key head, index tip, thumb tip) and ntarget = 0");
-    for (int k = 0; k < 3; k++) if (c->tip_site[k] < 0 || c->tip_site[k] >= m->dims.nsite) return fail(MYO_E_ARG, "key-turn task: site id out of range");
-    if (!(c->near_th >= 0.f) || !(c->far_th > 0.f) || !(c->pose_thd == c->pose_thd)) return fail(MYO_E_ARG, "key-turn task: near_th >= 0, far_th > 0, goal_th (pose_thd) a number");
-    T.obs_dim = 2 * nv + 6 + dm.na_obs;
-  }
-  else if (c->task == MYO_TASK_PEN) {
-    // pen_v0.py: the pen is the model's last six joints, 3 slides + 3 hinges of one root body; sites = object top / bottom, target top /
-    // bottom, eps_ball
-    const myo_model* m = b->model;
-    if (!(m->wave_ok && m->trk) || m->nq != nv || nv < 7) return fail(MYO_E_UNSUPPORTED, "pen task: a TrackEnv-class model without free / ball joints whose last six joints are the pen's");
-    std::vector<int> dtype(6), dlink(6), lpar(1), ldn(1);
-    HIPCHK(hipMemcpy(dtype.data(), dm.dof_type + (nv - 6), 24, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(dlink.data(), dm.dof_link + (nv - 6), 24, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(lpar.data(), dm.link_parent + dlink[5], 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(ldn.data(), dm.link_dofnum + dlink[5], 4, hipMemcpyDeviceToHost));
-    bool ok = lpar[0] < 0 && ldn[0] == 6;
-    for (int k = 0; k < 6; k++) ok = ok && dlink[k] == dlink[5] && dtype[k] == (k < 3 ? 2 : 3);
-    if (!ok) return fail(MYO_E_UNSUPPORTED, "pen task: the last six joints must be 3 slides + 3 hinges of one root body");
-    if (c->ntip != 5 || c->ntarget != 0) return fail(MYO_E_ARG, "pen task: ntip = 5 (object top, object bottom, target top, target bottom, eps_ball) and ntarget = 0");
-    for (int k = 0; k < 5; k++) if (c->tip_site[k] < 0 || c->tip_site[k] >= m->dims.nsite) return fail(MYO_E_ARG, "pen task: site id out of range");
-    for (int k = 0; k < 3; k++) if (!std::isfinite(c->tip_lpos[k])) return fail(MYO_E_ARG, "pen task: tip_lpos must be finite");
-    if (!(c->far_th > 0.f) || !(c->pose_thd == c->pose_thd)) return fail(MYO_E_ARG, "pen task: far_th > 0, pose_thd a number");
-    T.obs_dim = (nv - 6) + 21 + dm.na_obs;
-  }
-  else if (c->task == MYO_TASK_BAODING) {
-    // baoding_v1.py: the balls are the model's last two joints, free joints of root bodies (qpos[-14:-7], qpos[-7:]); sites = ball1, ball2,
-    // target1, target2.  The targets move in the frame of their body (baoding_v1.py:147-181: site_pos), which lowering folds into its link:
-    // T.bd_frame carries that body's x and y axes and, per target, the body origin lifted by the site's compiled z, in the link frame
-    const myo_model* m = b->model;
-    if (!(m->wave_ok && m->trk) || m->nq != nv + 2 || nv < 13) return fail(MYO_E_UNSUPPORTED, "baoding task: a TrackEnv-class model whose last two joints are free joints (the balls)");
-    std::vector<int> dlink(12), lpar(2), ldn(2);
-    HIPCHK(hipMemcpy(dlink.data(), dm.dof_link + (nv - 12), 48, hipMemcpyDeviceToHost));
-    for (int k = 0; k < 2; k++) {
-      HIPCHK(hipMemcpy(lpar.data() + k, dm.link_parent + dlink[6 * k], 4, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(ldn.data() + k, dm.link_dofnum + dlink[6 * k], 4, hipMemcpyDeviceToHost));
-    }
-    bool ok = dlink[0] != dlink[6] && lpar[0] < 0 && lpar[1] < 0 && ldn[0] == 6 && ldn[1] == 6;
-    for (int k = 0; k < 12; k++) ok = ok && dlink[k] == dlink[k < 6 ? 0 : 6];
-    if (!ok) return fail(MYO_E_UNSUPPORTED, "baoding task: the last twelve dofs must be two free joints of root bodies");
-    if (c->ntip != 4 || c->ntarget != 5) return fail(MYO_E_ARG, "baoding task: ntip = 4 (ball1, ball2, target1, target2) and ntarget = 5 (goal parameters)");
-    for (int k = 0; k < 4; k++) if (c->tip_site[k] < 0 || c->tip_site[k] >= m->dims.nsite) return fail(MYO_E_ARG, "baoding task: site id out of range");
-    std::vector<int> slink(4);
-    for (int k = 0; k < 4; k++) HIPCHK(hipMemcpy(slink.data() + k, dm.site_link + c->tip_site[k], 4, hipMemcpyDeviceToHost));
-    const int tb = m->site_body[c->tip_site[2]];
-    if (slink[0] != dlink[0] || slink[1] != dlink[6] || tb != m->site_body[c->tip_site[3]] || slink[2] < 0 || m->body_link[tb] != slink[2])
-      return fail(MYO_E_UNSUPPORTED, "baoding task: the ball sites must be on the balls, both target sites on one moving body");
-    if (!(c->far_th == c->far_th) || !(c->pose_thd == c->pose_thd)) return fail(MYO_E_ARG, "baoding task: far_th (drop_th) and pose_thd (proximity_th) numbers");
-    const float* bq = &m->body_lquat[4 * (size_t)tb];
-    const double qd[4] = {bq[0], bq[1], bq[2], bq[3]};
-    double R[9];
-    quat2mat_d(R, qd);
-    for (int k = 0; k < 3; k++) { T.bd_frame[k] = (float)R[3 * k]; T.bd_frame[3 + k] = (float)R[3 * k + 1]; }
-    for (int t = 0; t < 2; t++) {
-      const double z = m->site_pos0[3 * (size_t)c->tip_site[2 + t] + 2];
-      for (int k = 0; k < 3; k++) T.bd_frame[6 + 3 * t + k] = (float)(m->body_lpos[3 * (size_t)tb + k] + R[3 * k + 2] * z);
-    }
-    T.obs_dim = (nv - 12) + 24;
-  }
-  else if (c->task == MYO_TASK_HOLD) {
-    if (c->ntarget != 3) return fail(MYO_E_ARG, "hold task: ntarget must be 3 (goal position)");
-    if (!(b->model->wave_ok && b->model->dw.has_free && b->model->nq == nv + 1 && nv > 6)) return fail(MYO_E_UNSUPPORTED, "hold task needs a model whose last joint is one free object");
-    T.obs_dim = (b->model->nq - 7) + (nv - 6) + 6 + b->model->dm.na_obs;
-  }
-  else T.obs_dim = 0;
   T.nq = b->model->nq;
+  const TaskHooks* hooks = task_hooks(c->task);
+  if (hooks && hooks->configure) { int rc = hooks->configure(b, c); if (rc) return rc; }
+  else T.obs_dim = 0;
   if (T.obs_dim > b->obs_alloc) return fail(MYO_E_ARG, "obs_dim too large");
   if (c->ntarget > 0) {
     if (!c->target_lo) return fail(MYO_E_ARG, "target_lo required");
@@ -974,13 +407,6 @@ static int bq_check(const myo_batch* b) {
   return MYO_OK;
 }
 
-static void quat2mat_d(double* R, const double* q) {
-  const double w = q[0], x = q[1], y = q[2], z = q[3];
-  R[0] = w * w + x * x - y * y - z * z; R[1] = 2 * (x * y - w * z); R[2] = 2 * (x * z + w * y);
-  R[3] = 2 * (x * y + w * z); R[4] = w * w - x * x + y * y - z * z; R[5] = 2 * (y * z - w * x);
-  R[6] = 2 * (x * z - w * y); R[7] = 2 * (y * z + w * x); R[8] = w * w - x * x - y * y + z * z;
-}
-
 static int bq_start(myo_batch* b) {
   if (b->bq_on) return MYO_OK;
   int rc = bq_check(b);
@@ -1158,28 +584,24 @@ int myo_batch_write(myo_batch* b, int field, const void* host, size_t nbytes) {
   return MYO_OK;
 }
 
-int myo_reset(myo_batch* b, const uint8_t* mask_dev, uint64_t seed, void* stream) {
-  if (!b) return fail(MYO_E_ARG, "myo_reset: null");
+static int launch_reset(myo_batch* b, const uint8_t* mask_dev, uint64_t seed, void* stream, int max_episode_steps) {
   b->reset_seed = seed;
   const DevModel& dm = b->model->dm;
   HIPCHK(hipSetDevice(b->model->device));
-  int B = b->db.B;
-  hipLaunchKernelGGL(reset_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, b->db, b->task, b->model->nq, dm.nv, dm.nu, dm.qpos0, mask_dev, seed,
-                     b->env_offset, 0);
+  hipLaunchKernelGGL(reset_kernel, dim3(b->db.B), dim3(64), 0, (hipStream_t)stream, b->db, b->task, b->model->nq, dm.nv, dm.nu, dm.qpos0, mask_dev, seed,
+                     b->env_offset, max_episode_steps);
   HIPCHK(hipGetLastError());
   return MYO_OK;
 }
 
+int myo_reset(myo_batch* b, const uint8_t* mask_dev, uint64_t seed, void* stream) {
+  if (!b) return fail(MYO_E_ARG, "myo_reset: null");
+  return launch_reset(b, mask_dev, seed, stream, 0);
+}
+
 int myo_autoreset(myo_batch* b, int max_episode_steps, uint64_t seed, void* stream) {
   if (!b || max_episode_steps <= 0) return fail(MYO_E_ARG, "myo_autoreset: bad arguments");
-  b->reset_seed = seed;
-  const DevModel& dm = b->model->dm;
-  HIPCHK(hipSetDevice(b->model->device));
-  int B = b->db.B;
-  hipLaunchKernelGGL(reset_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, b->db, b->task, b->model->nq, dm.nv, dm.nu, dm.qpos0,
-                     (const uint8_t*)nullptr, seed, b->env_offset, max_episode_steps);
-  HIPCHK(hipGetLastError());
-  return MYO_OK;
+  return launch_reset(b, nullptr, seed, stream, max_episode_steps);
 }
 
 int myo_set_env_offset(myo_batch* b, int env_offset) {
@@ -1201,6 +623,49 @@ int myo_set_state(myo_batch* b, const float* qpos, const float* qvel, const floa
   return MYO_OK;
 }
 
+// The instantiations of step_kernel_w<NVT, KC, NC, NTR, WPE, SCHED, SPEC, HF, TRK, RK4>, each with its template arguments and the name
+// rocprofv3 prints for it (myo_bench_last_kernel_name; bench.py reports it next to the kernel time).  The per-device attribute pass, the
+// name and the launch all come from this one list.
+#define MYO_WAVE_KERNELS(X)                                                                                             \
+  X(WK_HAND, "step_kernel_w<24,8,32,1,3,false,0,false>", 24, 8, 32, 1, 3, false, 0)                                      \
+  X(WK_HAND_SPEC, "step_kernel_w<24,8,32,1,4,false,1,false>", 24, 8, 32, 1, 4, false, 1)                                 \
+  X(WK_LEG, "step_kernel_w<36,20,32,2,2,false,0,false>", 36, 20, 32, 2, 2, false, 0)                                     \
+  X(WK_LEG_SCHED, "step_kernel_w<36,20,32,2,2,true,0,false>", 36, 20, 32, 2, 2, true, 0)                                 \
+  X(WK_LEG_SPEC_SCHED, "step_kernel_w<36,20,32,2,2,true,2,false>", 36, 20, 32, 2, 2, true, 2)                            \
+  X(WK_LEG_SPEC, "step_kernel_w<36,20,32,2,2,false,2,false>", 36, 20, 32, 2, 2, false, 2)                                \
+  X(WK_TERRAIN, "step_kernel_w<36,20,32,2,2,false,0,true>", 36, 20, 32, 2, 2, false, 0, true)                            \
+  X(WK_TERRAIN_SPEC_SCHED, "step_kernel_w<36,20,32,2,2,true,3,true>", 36, 20, 32, 2, 2, true, 3, true)                   \
+  X(WK_TERRAIN_SPEC, "step_kernel_w<36,20,32,2,2,false,3,true>", 36, 20, 32, 2, 2, false, 3, true)                       \
+  X(WK_TRK, "step_kernel_w<36,20,32,2,2,false,0,false,true>", 36, 20, 32, 2, 2, false, 0, false, true)                   \
+  X(WK_HAND_RK4, "step_kernel_w<24,8,32,1,3,false,0,false,false,true>", 24, 8, 32, 1, 3, false, 0, false, false, true)   \
+  X(WK_LEG_RK4, "step_kernel_w<36,20,32,2,2,false,0,false,false,true>", 36, 20, 32, 2, 2, false, 0, false, false, true)
+struct WaveKernel {
+  const char* name;
+  void (*fn)(const DevModel*, const DevModelW*, DevBatch, const float*, int, int, long long*, const int*, const DevWalk*, int, SchedDev);
+};
+enum WaveKernelId {
+#define X(id, name, ...) id,
+  MYO_WAVE_KERNELS(X)
+#undef X
+};
+static const WaveKernel wave_kernels[] = {
+#define X(id, name, ...) {name, step_kernel_w<__VA_ARGS__>},
+  MYO_WAVE_KERNELS(X)
+#undef X
+};
+
+// the instantiation a launch of model m runs: bm = the per-env body-mass override is on (only the run-time-sized instantiations read its
+// link tables), sched = the substep scheduler is on (large-kernel models without RK4; terrain models only with their specialised sizes)
+static WaveKernelId select_wave_kernel(const myo_model* m, bool bm, bool sched) {
+  const bool hand_sizes = m->hand_sizes && !bm, leg_sizes = m->leg_sizes && !bm;
+  if (sched) return m->dw.hf.on ? WK_TERRAIN_SPEC_SCHED : (leg_sizes ? WK_LEG_SPEC_SCHED : WK_LEG_SCHED);
+  if (m->rk4) return m->wave_cfg == 0 ? WK_HAND_RK4 : WK_LEG_RK4;
+  if (m->wave_cfg == 2) return WK_TRK;   // TrackEnv model class
+  if (m->wave_cfg == 0) return hand_sizes ? WK_HAND_SPEC : WK_HAND;
+  if (m->dw.hf.on) return m->terrain_sizes ? WK_TERRAIN_SPEC : WK_TERRAIN;   // terrain models: the instantiations with the height-field narrow phase
+  return leg_sizes ? WK_LEG_SPEC : WK_LEG;
+}
+
 static int launch_step(myo_batch* b, const float* action, int actmap, int nsub, hipStream_t s, int kflags = 0) {
   const myo_model* m = b->model;
   const DevWalk* wk = b->task.task == MYO_TASK_WALK ? b->d_walk : nullptr;
@@ -1215,10 +680,8 @@ static int launch_step(myo_batch* b, const float* action, int actmap, int nsub, 
     std::lock_guard<std::mutex> attr_g_lock(attr_g_mu);
     bool& attr_set = attr_g_dev[m->device & 63];
     if (!attr_set) {
-      HIPCHK(hipFuncSetAttribute((const void*)step_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)step_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)step_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)reach_obs_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      for (const void* k : {(const void*)step_kernel<16>, (const void*)step_kernel<32>, (const void*)step_kernel<64>, (const void*)reach_obs_kernel<16>})
+        HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       attr_set = true;
     }
   }
@@ -1242,7 +705,6 @@ static int launch_step(myo_batch* b, const float* action, int actmap, int nsub, 
     const int n = b->db.B * m->dm.nl;
     hipLaunchKernelGGL(link_compose_kernel, dim3((n + 255) / 256), dim3(256), 0, s, b->db, m->dm.nl, m->d_lm_adr, m->d_lm_body, m->d_lm_tab);
   }
-  const bool hand_sizes = m->hand_sizes && !bm, leg_sizes = m->leg_sizes && !bm;
   if (G == 64 && m->wave_ok) {
     // kernel attributes are per device: one flag per device ordinal (a process that opens models on two GPUs)
     static std::mutex attr_mu;
@@ -1250,18 +712,7 @@ static int launch_step(myo_batch* b, const float* action, int actmap, int nsub, 
     std::lock_guard<std::mutex> attr_lock(attr_mu);
     bool& attr_w = attr_w_dev[m->device & 63];
     if (!attr_w) {
-      HIPCHK(hipFuncSetAttribute((const void*)step_kernel_w<24, 8, 32, 1, 3, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)step_kernel_w<24, 8, 32, 1, 4, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)step_kernel_w<36, 20, 32, 2, 2, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)step_kernel_w<36, 20, 32, 2, 2, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)step_kernel_w<36, 20, 32, 2, 2, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)step_kernel_w<36, 20, 32, 2, 2, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)step_kernel_w<36, 20, 32, 2, 2, false, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)step_kernel_w<36, 20, 32, 2, 2, true, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)step_kernel_w<36, 20, 32, 2, 2, false, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)step_kernel_w<36, 20, 32, 2, 2, false, 0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)step_kernel_w<24, 8, 32, 1, 3, false, 0, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)step_kernel_w<36, 20, 32, 2, 2, false, 0, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+      for (const WaveKernel& k : wave_kernels) HIPCHK(hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
       attr_w = true;
     }
     const int* order = nullptr;
@@ -1283,53 +734,18 @@ static int launch_step(myo_batch* b, const float* action, int actmap, int nsub, 
     // XCC_ID & 7 would never be drained on a DPX / QPX / CPX partition)
     const int nqueue = std::max(1, std::min(8, n_cu / 32));
     SchedDev S{b->d_sched, b->d_sched + 32, nqueue == 8 ? b->sched_stride : (Bn + nqueue - 1) / nqueue + 1, nsub + (wk ? 1 : 0), nqueue};
-    if (!kflags)   // instantiation chosen below, as rocprofv3 prints it (bench.py reports it next to the kernel time)
-      b->last_kernel = m->rk4 ? (m->wave_cfg == 0 ? "step_kernel_w<24,8,32,1,3,false,0,false,false,true>" : "step_kernel_w<36,20,32,2,2,false,0,false,false,true>") :
-                       m->wave_cfg == 2 ? "step_kernel_w<36,20,32,2,2,false,0,false,true>" :
-                       sched ? (m->dw.hf.on ? "step_kernel_w<36,20,32,2,2,true,3,true>" : (leg_sizes ? "step_kernel_w<36,20,32,2,2,true,2,false>" : "step_kernel_w<36,20,32,2,2,true,0,false>"))
-                             : (m->wave_cfg == 0 ? (hand_sizes ? "step_kernel_w<24,8,32,1,4,false,1,false>" : "step_kernel_w<24,8,32,1,3,false,0,false>")
-                                                 : (m->dw.hf.on ? (m->terrain_sizes ? "step_kernel_w<36,20,32,2,2,false,3,true>" : "step_kernel_w<36,20,32,2,2,false,0,true>") : (leg_sizes ? "step_kernel_w<36,20,32,2,2,false,2,false>" : "step_kernel_w<36,20,32,2,2,false,0,false>")));
+    const WaveKernel& k = wave_kernels[select_wave_kernel(m, bm, sched)];
+    if (!kflags) b->last_kernel = k.name;
+    int wgrid = Bn;
     if (sched) {
       hipLaunchKernelGGL(sched_init_kernel, dim3(1), dim3(1024), 0, s, (const int*)b->db.diag, Bn, S);
-      int grid = Bn < resident ? Bn : resident;    // persistent waves: no more workgroups than the chip holds at once
+      wgrid = Bn < resident ? Bn : resident;    // persistent waves: no more workgroups than the chip holds at once
       static const int grid_override = [] { const char* e = getenv("MYO_SCHED_GRID"); return e ? atoi(e) : 0; }();
-      if (grid_override > 0 && grid_override < grid) grid = grid_override;
-      if (m->dw.hf.on)
-        hipLaunchKernelGGL((step_kernel_w<36, 20, 32, 2, 2, true, 3, true>), dim3(grid), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm,
-                           (const DevModelW*)m->d_dw, b->db, action, actmap, nsub, st, (const int*)nullptr, wk, 0, S);
-      else if (leg_sizes)
-        hipLaunchKernelGGL((step_kernel_w<36, 20, 32, 2, 2, true, 2>), dim3(grid), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm,
-                           (const DevModelW*)m->d_dw, b->db, action, actmap, nsub, st, (const int*)nullptr, wk, 0, S);
-      else
-        hipLaunchKernelGGL((step_kernel_w<36, 20, 32, 2, 2, true, 0>), dim3(grid), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm,
-                           (const DevModelW*)m->d_dw, b->db, action, actmap, nsub, st, (const int*)nullptr, wk, 0, S);
-    } else if (m->rk4 && m->wave_cfg == 0)
-      hipLaunchKernelGGL((step_kernel_w<24, 8, 32, 1, 3, false, 0, false, false, true>), dim3(Bn), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm,
-                         (const DevModelW*)m->d_dw, b->db, action, actmap, nsub, st, order, (const DevWalk*)nullptr, 0, S);
-    else if (m->rk4)
-      hipLaunchKernelGGL((step_kernel_w<36, 20, 32, 2, 2, false, 0, false, false, true>), dim3(Bn), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm,
-                         (const DevModelW*)m->d_dw, b->db, action, actmap, nsub, st, order, wk, kflags, S);
-    else if (m->wave_cfg == 2)   // TrackEnv model class
-      hipLaunchKernelGGL((step_kernel_w<36, 20, 32, 2, 2, false, 0, false, true>), dim3(Bn), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm,
-                         (const DevModelW*)m->d_dw, b->db, action, actmap, nsub, st, order, wk, kflags, S);
-    else if (m->wave_cfg == 0 && hand_sizes)
-      hipLaunchKernelGGL((step_kernel_w<24, 8, 32, 1, 4, false, 1>), dim3(Bn), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm,
-                         (const DevModelW*)m->d_dw, b->db, action, actmap, nsub, st, order, (const DevWalk*)nullptr, 0, S);
-    else if (m->wave_cfg == 0)
-      hipLaunchKernelGGL((step_kernel_w<24, 8, 32, 1, 3, false, 0>), dim3(Bn), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm,
-                         (const DevModelW*)m->d_dw, b->db, action, actmap, nsub, st, order, (const DevWalk*)nullptr, 0, S);
-    else if (m->dw.hf.on && m->terrain_sizes)     // terrain models: the instantiations with the height-field narrow phase
-      hipLaunchKernelGGL((step_kernel_w<36, 20, 32, 2, 2, false, 3, true>), dim3(Bn), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm,
-                         (const DevModelW*)m->d_dw, b->db, action, actmap, nsub, st, order, wk, kflags, S);
-    else if (m->dw.hf.on)
-      hipLaunchKernelGGL((step_kernel_w<36, 20, 32, 2, 2, false, 0, true>), dim3(Bn), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm,
-                         (const DevModelW*)m->d_dw, b->db, action, actmap, nsub, st, order, wk, kflags, S);
-    else if (leg_sizes)
-      hipLaunchKernelGGL((step_kernel_w<36, 20, 32, 2, 2, false, 2>), dim3(Bn), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm,
-                         (const DevModelW*)m->d_dw, b->db, action, actmap, nsub, st, order, wk, kflags, S);
-    else
-      hipLaunchKernelGGL((step_kernel_w<36, 20, 32, 2, 2, false, 0>), dim3(Bn), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm,
-                         (const DevModelW*)m->d_dw, b->db, action, actmap, nsub, st, order, wk, kflags, S);
+      if (grid_override > 0 && grid_override < wgrid) wgrid = grid_override;
+    }
+    // (order is set only without the scheduler; wk and kflags are null / 0 for every model outside the large-kernel class: the walk task needs wave_cfg == 1)
+    hipLaunchKernelGGL(k.fn, dim3(wgrid), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm, (const DevModelW*)m->d_dw, b->db, action, actmap,
+                       nsub, st, order, wk, kflags, S);
     HIPCHK(hipGetLastError());
     return MYO_OK;
   }
@@ -1348,31 +764,68 @@ int myo_step(myo_batch* b, const float* action_dev, int actmap, int nsubsteps, v
   return launch_step(b, action_dev, actmap, nsubsteps, (hipStream_t)stream);
 }
 
-static int launch_obs(myo_batch* b, hipStream_t s, int obs_only = 0, int reset_only = 0) {
+// the hooks of the tasks that live in myo_kernels_aux.h / this file, and the table of all tasks
+static int state_configure(myo_batch* b, const myo_task_config* c) {   // pose / stand / hold
   const myo_model* m = b->model;
-  int B = b->db.B;
-  if (b->task.task == MYO_TASK_WALK) {
-    // the walk observation lives in the step kernel: run it with zero substeps as an observation-only pass
-    return launch_step(b, nullptr, MYO_ACTMAP_NONE, 0, s, KF_AUX | (obs_only ? KF_OBS_ONLY : 0) | (reset_only ? KF_RESET_ONLY : 0));
-  } else if (b->task.task == MYO_TASK_TRACK && b->track_flavour == 1) {
-    hipLaunchKernelGGL(myodm_obs_kernel, dim3(B), dim3(64), 0, s, m->dm, b->db, b->task, (const DevTrack*)b->d_track, b->reset_seed, obs_only, reset_only);
-  } else if (b->task.task == MYO_TASK_POSE || b->task.task == MYO_TASK_HOLD || b->task.task == MYO_TASK_STAND || b->task.task == MYO_TASK_TRACK) {
-    hipLaunchKernelGGL(obs_kernel, dim3(B), dim3(64), 0, s, m->dm, b->db, b->task, obs_only, reset_only);
-  } else if (b->task.task == MYO_TASK_KEYTURN) {
-    hipLaunchKernelGGL(keyturn_obs_kernel, dim3(B), dim3(64), 0, s, m->dm, b->db, b->task, obs_only, reset_only);
-  } else if (b->task.task == MYO_TASK_PEN) {
-    hipLaunchKernelGGL(pen_obs_kernel, dim3(B), dim3(64), 0, s, m->dm, b->db, b->task, obs_only, reset_only);
-  } else if (b->task.task == MYO_TASK_BAODING) {
-    hipLaunchKernelGGL(baoding_obs_kernel, dim3(B), dim3(64), 0, s, m->dm, b->db, b->task, obs_only, reset_only);
-  } else if (b->task.task == MYO_TASK_REACH) {
-    const int EPW = 4;
-    hipLaunchKernelGGL(reach_obs_kernel<16>, dim3((B + EPW - 1) / EPW), dim3(64), (size_t)EPW * m->env_lds_bytes, s, m->dm, b->db, b->task, obs_only);
+  const int nv = m->dm.nv, nq = m->nq, na = m->dm.na_obs;
+  if (c->task == MYO_TASK_POSE) {
+    if (c->ntarget != nv) return fail(MYO_E_ARG, "pose task: ntarget must equal nq");
+    b->task.obs_dim = 3 * nv + na;
+  } else if (c->task == MYO_TASK_STAND) {
+    if (c->ntarget != 3) return fail(MYO_E_ARG, "stand task: ntarget must be 3 (target position)");
+    if (!(m->wave_ok && m->dw.has_free && nq == nv + 1)) return fail(MYO_E_UNSUPPORTED, "stand task needs a model with a free root joint");
+    b->task.obs_dim = nq + nv + 6 + na;
   } else {
-    return fail(MYO_E_ARG, "myo_obs: no task configured");
+    if (c->ntarget != 3) return fail(MYO_E_ARG, "hold task: ntarget must be 3 (goal position)");
+    if (!(m->wave_ok && m->dw.has_free && nq == nv + 1 && nv > 6)) return fail(MYO_E_UNSUPPORTED, "hold task needs a model whose last joint is one free object");
+    b->task.obs_dim = (nq - 7) + (nv - 6) + 6 + na;
   }
+  return MYO_OK;
+}
+static const TaskHooks state_hooks = {state_configure, launch_task_obs<StateTask>, launch_task_post<StateTask>};
+
+// reach needs tip positions: its observation reuses the lanes kernel's kinematics stage and has no fused epilogue
+static int reach_configure(myo_batch* b, const myo_task_config* c) {
+  if (c->ntarget != 3 * c->ntip) return fail(MYO_E_ARG, "reach task: ntarget must be 3*ntip");
+  b->task.obs_dim = 2 * b->model->dm.nv + 6 * c->ntip + b->model->dm.na_obs;
+  return MYO_OK;
+}
+static int reach_obs(myo_batch* b, hipStream_t s, int obs_only, int) {
+  const int EPW = 4;
+  hipLaunchKernelGGL(reach_obs_kernel<16>, dim3((b->db.B + EPW - 1) / EPW), dim3(64), (size_t)EPW * b->model->env_lds_bytes, s, b->model->dm, b->db, b->task, obs_only);
+  return MYO_OK;
+}
+static const TaskHooks reach_hooks = {reach_configure, reach_obs, nullptr};
+
+// the walk observation lives in the step kernel: run it with zero substeps as an observation-only pass (configured by myo_batch_configure_walk;
+// in myo_bench_rollout the step launch itself observes)
+static int walk_obs(myo_batch* b, hipStream_t s, int obs_only, int reset_only) {
+  return launch_step(b, nullptr, MYO_ACTMAP_NONE, 0, s, KF_AUX | (obs_only ? KF_OBS_ONLY : 0) | (reset_only ? KF_RESET_ONLY : 0));
+}
+static const TaskHooks walk_hooks = {nullptr, walk_obs, nullptr};
+
+static const TaskHooks* task_hooks(int task) {
+  switch (task) {
+    case MYO_TASK_POSE: case MYO_TASK_STAND: case MYO_TASK_HOLD: return &state_hooks;
+    case MYO_TASK_REACH: return &reach_hooks;
+    case MYO_TASK_WALK: return &walk_hooks;
+    case MYO_TASK_TRACK: return &track_hooks;
+    case MYO_TASK_KEYTURN: return &keyturn_hooks;
+    case MYO_TASK_PEN: return &pen_hooks;
+    case MYO_TASK_BAODING: return &baoding_hooks;
+    default: return nullptr;   // MYO_TASK_NONE
+  }
+}
+
+static int launch_obs(myo_batch* b, hipStream_t s, int obs_only = 0, int reset_only = 0) {
+  const TaskHooks* hooks = task_hooks(b->task.task);
+  if (!hooks) return fail(MYO_E_ARG, "myo_obs: no task configured");
+  const int rc = hooks->obs(b, s, obs_only, reset_only);
+  if (rc) return rc;
   HIPCHK(hipGetLastError());
   return MYO_OK;
 }
+
 
 int myo_obs(myo_batch* b, void* stream) {
   if (!b) return fail(MYO_E_ARG, "myo_obs: null");
@@ -1470,33 +923,11 @@ int myo_bench_rollout(myo_batch* b, int steps, int nsubsteps, uint64_t seed, int
     rc = launch_step(b, b->d_action, mjx_track ? MYO_ACTMAP_CTRLRANGE : MYO_ACTMAP_MUSCLE_SIGMOID, nsubsteps, s);
     if (rc) return rc;
     HIPCHK(hipEventRecord(b->kev[2 * (base + i) + 1], s));
-    const int tk = b->task.task;
+    const TaskHooks* hooks = task_hooks(b->task.task);
     if (mjx_track) continue;   // observation, reward, done and the masked reset are the step kernel's own epilogue
-    if ((mode & MYO_BENCH_OBS) && (mode & MYO_BENCH_AUTORESET) && max_episode_steps > 0 && tk == MYO_TASK_TRACK) {     // ... the classic MyoDM flavour
-      b->reset_seed = seed;
-      hipLaunchKernelGGL(myodm_post_kernel, dim3(b->db.B), dim3(64), 0, s, b->model->dm, b->db, b->task, (const DevTrack*)b->d_track, b->model->nq,
-                         b->model->dm.qpos0, seed, b->env_offset, max_episode_steps);
-      HIPCHK(hipGetLastError());
-      continue;
-    }
-    if ((mode & MYO_BENCH_OBS) && (mode & MYO_BENCH_AUTORESET) && max_episode_steps > 0 && (tk == MYO_TASK_POSE || tk == MYO_TASK_HOLD || tk == MYO_TASK_STAND)) {
-      // state-only observations: observation + auto-reset + first observation of the new episodes in ONE launch (post_kernel)
-      hipLaunchKernelGGL(post_kernel, dim3(b->db.B), dim3(64), 0, s, b->model->dm, b->db, b->task, b->model->nq, b->model->dm.qpos0, seed, b->env_offset, max_episode_steps);
-      HIPCHK(hipGetLastError());
-      continue;
-    }
-    if ((mode & MYO_BENCH_OBS) && (mode & MYO_BENCH_AUTORESET) && max_episode_steps > 0 && tk == MYO_TASK_KEYTURN) {   // the same for the key-turn task
-      hipLaunchKernelGGL(keyturn_post_kernel, dim3(b->db.B), dim3(64), 0, s, b->model->dm, b->db, b->task, b->model->nq, b->model->dm.qpos0, seed, b->env_offset, max_episode_steps);
-      HIPCHK(hipGetLastError());
-      continue;
-    }
-    if ((mode & MYO_BENCH_OBS) && (mode & MYO_BENCH_AUTORESET) && max_episode_steps > 0 && tk == MYO_TASK_PEN) {       // ... and the pen task
-      hipLaunchKernelGGL(pen_post_kernel, dim3(b->db.B), dim3(64), 0, s, b->model->dm, b->db, b->task, b->model->nq, b->model->dm.qpos0, seed, b->env_offset, max_episode_steps);
-      HIPCHK(hipGetLastError());
-      continue;
-    }
-    if ((mode & MYO_BENCH_OBS) && (mode & MYO_BENCH_AUTORESET) && max_episode_steps > 0 && tk == MYO_TASK_BAODING) {   // ... and the baoding task
-      hipLaunchKernelGGL(baoding_post_kernel, dim3(b->db.B), dim3(64), 0, s, b->model->dm, b->db, b->task, b->model->nq, b->model->dm.qpos0, seed, b->env_offset, max_episode_steps);
+    if ((mode & MYO_BENCH_OBS) && (mode & MYO_BENCH_AUTORESET) && max_episode_steps > 0 && hooks && hooks->post) {
+      // observation + auto-reset + first observation of the new episodes in ONE launch (task_post_kernel)
+      if ((rc = hooks->post(b, s, seed, max_episode_steps))) return rc;
       HIPCHK(hipGetLastError());
       continue;
     }

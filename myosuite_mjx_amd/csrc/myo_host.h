@@ -1,0 +1,116 @@
+// myo_host.h -- host-side records shared by myo_hip.hip, the model loader and the task headers: error reporting, myo_model, myo_batch, and
+// the per-task hook record with its two generic launchers.
+#ifndef MYO_HOST_H
+#define MYO_HOST_H
+
+#include <memory>
+
+static int g_lanes = 64;  // lanes per env (16 / 32 / 64); MYO_LANES env var or myo_set_lanes(); 64 = wave-per-env kernel
+static thread_local std::string g_err;
+static int fail(int code, const std::string& msg) { g_err = msg; return code; }
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(MYO_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
+
+struct myo_model {
+  int device = 0;
+  DevModel dm{};
+  DevModelW dw{};
+  DevModel* d_dm = nullptr;     // device copies of the model structs for the wave kernel
+  DevModelW* d_dw = nullptr;
+  int env_lds_bytes_w = 0;
+  bool wave_ok = false, generic_ok = false;
+  int n_cu = 0;                 // compute units of the model's device (scheduler sizing)
+  int kin_floats = 0;           // LDS scratch the two-phase kinematics needs (lowering.py hip_kin_size)
+  bool rk4 = false;             // <option integrator="RK4">: the RK4 instantiations of the wave kernel (generic sizes, no scheduler)
+  bool trk = false;             // TrackEnv model class: step_kernel_w<36,20,32,2,2,false,0,false,true>
+  bool hand_sizes = false, leg_sizes = false, terrain_sizes = false;   // table sizes equal Sizes<1> / Sizes<2> / Sizes<3>: the size-specialised instantiations may be used
+  int wave_cfg = 0;             // 0: step_kernel_w<24,8,32,1,...> (hand / finger), 1: step_kernel_w<36,20,32,2,2,...> (legs), 2: the TRK instantiation
+  int nq = 0;
+  int has_tl = 0;
+  bool has_affine = false;   // some actuator is a stateless affine one (motor / position / velocity): wave kernel only
+  myo_dims dims{};
+  std::vector<void*> dev_allocs;
+  std::vector<float> qpos0, jnt_lo, jnt_hi;
+  std::vector<int> dof_type, dof_link, link_parent, link_dofnum, site_link;   // host copies of the uploaded tables the task checks read
+  std::vector<int> cg_geom, cg_type_h;   // collision geom -> compiled geom id, and its type (host copies)
+  std::vector<int> body_link;                       // body -> link, pose of the body inside the link frame (walk task)
+  std::vector<float> body_lpos, body_lquat, mass;   // mass = [total, static bodies' mass-weighted COM xyz]
+  float* d_qpos0 = nullptr;
+  int env_lds_bytes = 0;
+  // per-env body masses (MYO_F_BODYMASS): the compiled body_mass and, per link, its member bodies (CSR) with their COM (3), inertia
+  // about the COM (6) in the link frame and compiled mass -- the per-body constants of lowering.py's link recomposition (link_compose_kernel)
+  std::vector<float> body_mass0;
+  const int *d_lm_adr = nullptr, *d_lm_body = nullptr;
+  const double* d_lm_tab = nullptr;
+  // per-env translation of one root body (MYO_F_BODYPOS): the link headed by the body that carries the model's last joint, when that body
+  // is a child of the world heading a root link of a TrackEnv-class model; -1 otherwise
+  int bp_link = -1;
+  // per-env orientation of one world-welded body (MYO_F_BODYQUAT): compiled body tree, poses and the bodies of the collision geoms / sites
+  std::vector<int> body_parent, body_jntnum, cg_body, site_body;
+  std::vector<double> body_pos0, body_quat0;
+  std::vector<double> site_pos0;   // compiled site_pos (site in its body's frame): the baoding task's moving targets keep its z
+};
+
+struct myo_batch {
+  const myo_model* model = nullptr;
+  DevBatch db{};
+  TaskDev task{};
+  int ntarget_alloc = 0, obs_alloc = 0, env_offset = 0;
+  std::vector<void*> dev_allocs;
+  float *d_tlo = nullptr, *d_thi = nullptr, *d_init = nullptr, *d_jlo = nullptr, *d_jhi = nullptr, *d_action = nullptr, *d_rnd = nullptr;
+  float* d_initv = nullptr;
+  float *d_init2 = nullptr, *d_initv2 = nullptr, *d_fatvec = nullptr;   // walk reset "random": second keyframe; fatigue reset vector
+  const char* last_kernel = "step_kernel";   // name of the step-kernel instantiation of the last myo_step / bench launch
+  DevWalk* d_walk = nullptr;
+  DevTrack* d_track = nullptr;    // MYO_TASK_TRACK: device copy of the task record (tables hang off it)
+  float* d_metrics = nullptr;     // [B][4]
+  int track_frames = 0;
+  int track_flavour = 0;          // myo_track_config.flavour: 0 MJX (fused into the step kernel), 1 classic gym TrackEnv (task_obs_kernel<MyodmTask>)
+  uint64_t reset_seed = 0;        // seed of the last myo_reset / myo_autoreset (classic flavour: keys the RANDOM reference draws)
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  uint64_t bench_step = 0;
+  long long* d_stamps = nullptr;
+  int* d_order = nullptr;
+  int* d_sched = nullptr;       // substep scheduler: 8 queues x (4 control words + ring)
+  int sched_stride = 0;
+  int balance = 1;
+  bool bm_on = false;            // per-env body-mass override started (DevBatch.bmass / bmass_range / linkc allocated)
+  bool bp_on = false;            // per-env root-body offset started (DevBatch.bpos / bpos_range allocated)
+  int bq_body = -1;              // body of MYO_F_BODYQUAT (myo_task_config.quat_body; -1: none selected)
+  bool bq_on = false;            // per-env body orientation started (DevBatch.bquat / bquat_range / bq_c / bq_flag allocated)
+  std::vector<hipEvent_t> kev;   // per-launch event pairs around the step kernel (bench only)
+  int kev_pending = 0;           // pairs recorded by asynchronous bench calls and not collected yet
+  float last_kernel_ms = 0.f;
+};
+
+// What differs per task on the host, indexed by task id (task_hooks in myo_hip.hip); a task's record lives next to its kernel.
+struct TaskHooks {
+  int (*configure)(myo_batch*, const myo_task_config*);                    // argument and model checks, obs_dim, task-specific TaskDev fields; null: no observation row
+  int (*obs)(myo_batch*, hipStream_t, int obs_only, int reset_only);       // observation launch; null: the task has none
+  int (*post)(myo_batch*, hipStream_t, uint64_t seed, int auto_max);       // myo_bench_rollout's fused epilogue; null: observation, auto-reset and re-observation are three launches
+};
+template <class Task> static int launch_task_obs(myo_batch* b, hipStream_t s, int obs_only, int reset_only) {
+  hipLaunchKernelGGL(task_obs_kernel<Task>, dim3(b->db.B), dim3(64), 0, s, b->model->dm, b->db, b->task, (const DevTrack*)b->d_track, b->reset_seed, obs_only, reset_only);
+  return MYO_OK;
+}
+template <class Task> static int launch_task_post(myo_batch* b, hipStream_t s, uint64_t seed, int auto_max) {
+  hipLaunchKernelGGL(task_post_kernel<Task>, dim3(b->db.B), dim3(64), 0, s, b->model->dm, b->db, b->task, (const DevTrack*)b->d_track, b->model->nq,
+                     b->model->dm.qpos0, seed, b->env_offset, auto_max);
+  return MYO_OK;
+}
+
+// the dofs [d0, d0 + n) are all the dofs of one root link: that link, or -1
+static int root_link_of_dofs(const myo_model* m, int d0, int n) {
+  const int l = m->dof_link[d0];
+  if (m->link_parent[l] >= 0 || m->link_dofnum[l] != n) return -1;
+  for (int k = 1; k < n; k++) if (m->dof_link[d0 + k] != l) return -1;
+  return l;
+}
+
+static void quat2mat_d(double* R, const double* q) {
+  const double w = q[0], x = q[1], y = q[2], z = q[3];
+  R[0] = w * w + x * x - y * y - z * z; R[1] = 2 * (x * y - w * z); R[2] = 2 * (x * z + w * y);
+  R[3] = 2 * (x * y + w * z); R[4] = w * w - x * x + y * y - z * z; R[5] = 2 * (y * z - w * x);
+  R[6] = 2 * (x * z - w * y); R[7] = 2 * (y * z + w * x); R[8] = w * w - x * x - y * y + z * z;
+}
+
+#endif  // MYO_HOST_H

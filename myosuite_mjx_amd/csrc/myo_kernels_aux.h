@@ -354,23 +354,42 @@ __device__ __forceinline__ void obs_body(const DevModel& M, const DevBatch& Bt, 
     }
   }
 }
-__global__ void __launch_bounds__(64) obs_kernel(DevModel M, DevBatch Bt, TaskDev T, int obs_only, int reset_only) {
+// A task hands its observation to the two kernels below as a struct with one static function, Task::obs(M, Bt, T, K, seed, obs_only, e, lane),
+// that wraps its *_obs_body (StateObs / TrackObs take the body as a template argument, so a kernel's symbol carries its task's name).  K (the
+// track record) and seed (the seed of the last reset) are read by the classic MyoDM flavour only
+template <void (*Body)(const DevModel&, const DevBatch&, const TaskDev&, int, int, int)>
+struct StateObs {   // a body that reads the batch state alone
+  static __device__ __forceinline__ void obs(const DevModel& M, const DevBatch& Bt, const TaskDev& T, const DevTrack*, uint64_t, int obs_only, int e, int lane) {
+    Body(M, Bt, T, obs_only, e, lane);
+  }
+};
+using StateTask = StateObs<obs_body>;   // pose / hold / stand / MJX track
+template <void (*Body)(const DevModel&, const DevBatch&, const TaskDev&, const DevTrack&, uint64_t, int, int, int)>
+struct TrackObs {   // a body that also reads the track record and the seed of the last reset (classic MyoDM)
+  static __device__ __forceinline__ void obs(const DevModel& M, const DevBatch& Bt, const TaskDev& T, const DevTrack* K, uint64_t seed, int obs_only, int e, int lane) {
+    Body(M, Bt, T, *K, seed, obs_only, e, lane);
+  }
+};
+template <class Task>
+__global__ void __launch_bounds__(64) task_obs_kernel(DevModel M, DevBatch Bt, TaskDev T, const DevTrack* K, uint64_t seed, int obs_only, int reset_only) {
   const int e = blockIdx.x;
   if (e >= Bt.B) return;
   if (reset_only && Bt.elapsed[e] != 0) return;    // refresh only the rows of envs an auto-reset just touched
-  obs_body(M, Bt, T, obs_only, e, threadIdx.x);
+  Task::obs(M, Bt, T, K, seed, obs_only, e, threadIdx.x);
 }
 // observation / reward / done of the stepped state, gym TimeLimit + done auto-reset, and the first observation of the new episode for the
-// envs that were reset: the three launches of the per-step epilogue (obs_kernel, reset_kernel, obs_kernel(reset_only)) in one -- on
-// the critical path between two step kernels every launch costs a few microseconds of dispatch gap
-__global__ void __launch_bounds__(64) post_kernel(DevModel M, DevBatch Bt, TaskDev T, int nq, const float* qpos0, uint64_t seed, int env_offset, int auto_max) {
+// envs that were reset: the three launches of the per-step epilogue (task_obs_kernel, reset_kernel, task_obs_kernel(reset_only)) in one --
+// on the critical path between two step kernels every launch costs a few microseconds of dispatch gap
+template <class Task>
+__global__ void __launch_bounds__(64) task_post_kernel(DevModel M, DevBatch Bt, TaskDev T, const DevTrack* K, int nq, const float* qpos0, uint64_t seed,
+                                                       int env_offset, int auto_max) {
   const int e = blockIdx.x, lane = threadIdx.x;
   if (e >= Bt.B) return;
-  obs_body(M, Bt, T, 0, e, lane);
+  Task::obs(M, Bt, T, K, seed, 0, e, lane);
   __syncthreads();                       // reward / done of this env written (lane 0) before every lane tests them
   if (reset_body(Bt, T, nq, M.nv, M.nu, qpos0, nullptr, seed, env_offset, auto_max, e, lane)) {
-    __syncthreads();                     // the new state rows are complete before they are read back
-    obs_body(M, Bt, T, 1, e, lane);
+    __syncthreads();                     // the new state rows (and what the reset drew for the task) are complete before they are read back
+    Task::obs(M, Bt, T, K, seed, 1, e, lane);
   }
 }
 

@@ -74,25 +74,35 @@ __device__ __forceinline__ void baoding_obs_body(const DevModel& M, const DevBat
   }
 }
 
-__global__ void __launch_bounds__(64) baoding_obs_kernel(DevModel M, DevBatch Bt, TaskDev T, int obs_only, int reset_only) {
-  const int e = blockIdx.x;
-  if (e >= Bt.B) return;
-  if (reset_only && Bt.elapsed[e] != 0) return;    // refresh only the rows of envs an auto-reset just touched
-  baoding_obs_body(M, Bt, T, obs_only, e, threadIdx.x);
-}
-
-// myo_bench_rollout's fused epilogue (keyturn_post_kernel's pattern): observation / reward / done of the stepped state, auto-reset, and the
-// first observation of the new episodes, in one launch
-__global__ void __launch_bounds__(64) baoding_post_kernel(DevModel M, DevBatch Bt, TaskDev T, int nq, const float* qpos0, uint64_t seed, int env_offset,
-                                                          int auto_max) {
-  const int e = blockIdx.x, lane = threadIdx.x;
-  if (e >= Bt.B) return;
-  baoding_obs_body(M, Bt, T, 0, e, lane);
-  __syncthreads();                       // reward / done of this env written (lane 0) before every lane tests them
-  if (reset_body(Bt, T, nq, M.nv, M.nu, qpos0, nullptr, seed, env_offset, auto_max, e, lane)) {
-    __syncthreads();                     // the new state rows and goal parameters are complete before they are read back
-    baoding_obs_body(M, Bt, T, 1, e, lane);
+using BaodingTask = StateObs<baoding_obs_body>;
+// baoding_v1.py: the balls are the model's last two joints, free joints of root bodies (qpos[-14:-7], qpos[-7:]); sites = ball1, ball2,
+// target1, target2.  The targets move in the frame of their body (baoding_v1.py:147-181: site_pos), which lowering folds into its link:
+// T.bd_frame carries that body's x and y axes and, per target, the body origin lifted by the site's compiled z, in the link frame
+static int baoding_configure(myo_batch* b, const myo_task_config* c) {
+  const myo_model* m = b->model;
+  TaskDev& T = b->task;
+  const int nv = m->dm.nv;
+  if (!(m->wave_ok && m->trk) || m->nq != nv + 2 || nv < 13) return fail(MYO_E_UNSUPPORTED, "baoding task: a TrackEnv-class model whose last two joints are free joints (the balls)");
+  const int ball[2] = {root_link_of_dofs(m, nv - 12, 6), root_link_of_dofs(m, nv - 6, 6)};
+  if (ball[0] < 0 || ball[1] < 0 || ball[0] == ball[1]) return fail(MYO_E_UNSUPPORTED, "baoding task: the last twelve dofs must be two free joints of root bodies");
+  if (c->ntip != 4 || c->ntarget != 5) return fail(MYO_E_ARG, "baoding task: ntip = 4 (ball1, ball2, target1, target2) and ntarget = 5 (goal parameters)");
+  for (int k = 0; k < 4; k++) if (c->tip_site[k] < 0 || c->tip_site[k] >= m->dims.nsite) return fail(MYO_E_ARG, "baoding task: site id out of range");
+  const int tb = m->site_body[c->tip_site[2]], tl = m->site_link[c->tip_site[2]];
+  if (m->site_link[c->tip_site[0]] != ball[0] || m->site_link[c->tip_site[1]] != ball[1] || tb != m->site_body[c->tip_site[3]] || tl < 0 || m->body_link[tb] != tl)
+    return fail(MYO_E_UNSUPPORTED, "baoding task: the ball sites must be on the balls, both target sites on one moving body");
+  if (!(c->far_th == c->far_th) || !(c->pose_thd == c->pose_thd)) return fail(MYO_E_ARG, "baoding task: far_th (drop_th) and pose_thd (proximity_th) numbers");
+  const float* bq = &m->body_lquat[4 * (size_t)tb];
+  const double qd[4] = {bq[0], bq[1], bq[2], bq[3]};
+  double R[9];
+  quat2mat_d(R, qd);
+  for (int k = 0; k < 3; k++) { T.bd_frame[k] = (float)R[3 * k]; T.bd_frame[3 + k] = (float)R[3 * k + 1]; }
+  for (int t = 0; t < 2; t++) {
+    const double z = m->site_pos0[3 * (size_t)c->tip_site[2 + t] + 2];
+    for (int k = 0; k < 3; k++) T.bd_frame[6 + 3 * t + k] = (float)(m->body_lpos[3 * (size_t)tb + k] + R[3 * k + 2] * z);
   }
+  T.obs_dim = (nv - 12) + 24;
+  return MYO_OK;
 }
+static const TaskHooks baoding_hooks = {baoding_configure, launch_task_obs<BaodingTask>, launch_task_post<BaodingTask>};
 
 #endif  // MYO_TASK_BAODING_H

@@ -99,25 +99,19 @@ __device__ __forceinline__ void keyturn_obs_body(const DevModel& M, const DevBat
   }
 }
 
-__global__ void __launch_bounds__(64) keyturn_obs_kernel(DevModel M, DevBatch Bt, TaskDev T, int obs_only, int reset_only) {
-  const int e = blockIdx.x;
-  if (e >= Bt.B) return;
-  if (reset_only && Bt.elapsed[e] != 0) return;    // refresh only the rows of envs an auto-reset just touched
-  keyturn_obs_body(M, Bt, T, obs_only, e, threadIdx.x);
+using KeyturnTask = StateObs<keyturn_obs_body>;
+// key_turn_v0.py: the key is the model's last joint, one hinge of a root body; sites = key head, index tip, thumb tip
+static int keyturn_configure(myo_batch* b, const myo_task_config* c) {
+  const myo_model* m = b->model;
+  const int nv = m->dm.nv;
+  if (!(m->wave_ok && m->trk) || m->bp_link < 0 || m->nq != nv) return fail(MYO_E_UNSUPPORTED, "key-turn task: a TrackEnv-class model without free / ball joints whose last joint is the hinge of a root body");
+  if (m->dof_type[nv - 1] != 3 || m->link_dofnum[m->bp_link] != 1 || m->dof_link[nv - 1] != m->bp_link) return fail(MYO_E_UNSUPPORTED, "key-turn task: the last joint must be the one hinge of its root body");
+  if (c->ntip != 3 || c->ntarget != 0) return fail(MYO_E_ARG, "key-turn task: ntip = 3 (key head, index tip, thumb tip) and ntarget = 0");
+  for (int k = 0; k < 3; k++) if (c->tip_site[k] < 0 || c->tip_site[k] >= m->dims.nsite) return fail(MYO_E_ARG, "key-turn task: site id out of range");
+  if (!(c->near_th >= 0.f) || !(c->far_th > 0.f) || !(c->pose_thd == c->pose_thd)) return fail(MYO_E_ARG, "key-turn task: near_th >= 0, far_th > 0, goal_th (pose_thd) a number");
+  b->task.obs_dim = 2 * nv + 6 + m->dm.na_obs;
+  return MYO_OK;
 }
-
-// myo_bench_rollout's fused epilogue (post_kernel's pattern): observation / reward / done of the stepped state, auto-reset, and the first
-// observation of the new episodes, in one launch
-__global__ void __launch_bounds__(64) keyturn_post_kernel(DevModel M, DevBatch Bt, TaskDev T, int nq, const float* qpos0, uint64_t seed, int env_offset,
-                                                          int auto_max) {
-  const int e = blockIdx.x, lane = threadIdx.x;
-  if (e >= Bt.B) return;
-  keyturn_obs_body(M, Bt, T, 0, e, lane);
-  __syncthreads();                       // reward / done of this env written (lane 0) before every lane tests them
-  if (reset_body(Bt, T, nq, M.nv, M.nu, qpos0, nullptr, seed, env_offset, auto_max, e, lane)) {
-    __syncthreads();                     // the new state rows (and the key offset) are complete before they are read back
-    keyturn_obs_body(M, Bt, T, 1, e, lane);
-  }
-}
+static const TaskHooks keyturn_hooks = {keyturn_configure, launch_task_obs<KeyturnTask>, launch_task_post<KeyturnTask>};
 
 #endif  // MYO_TASK_KEYTURN_H

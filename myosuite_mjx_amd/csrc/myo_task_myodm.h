@@ -123,25 +123,17 @@ __device__ __forceinline__ void myodm_obs_body(const DevModel& M, const DevBatch
   }
 }
 
-__global__ void __launch_bounds__(64) myodm_obs_kernel(DevModel M, DevBatch Bt, TaskDev T, const DevTrack* K, uint64_t seed, int obs_only, int reset_only) {
-  const int e = blockIdx.x;
-  if (e >= Bt.B) return;
-  if (reset_only && Bt.elapsed[e] != 0) return;    // refresh only the rows of envs an auto-reset just touched
-  myodm_obs_body(M, Bt, T, *K, seed, obs_only, e, threadIdx.x);
-}
+using MyodmTask = TrackObs<myodm_obs_body>;
 
-// myo_bench_rollout's fused epilogue (pen_post_kernel's pattern): observation / reward / done of the stepped state, auto-reset, and the
-// first observation of the new episodes, in one launch
-__global__ void __launch_bounds__(64) myodm_post_kernel(DevModel M, DevBatch Bt, TaskDev T, const DevTrack* K, int nq, const float* qpos0, uint64_t seed,
-                                                        int env_offset, int auto_max) {
-  const int e = blockIdx.x, lane = threadIdx.x;
-  if (e >= Bt.B) return;
-  myodm_obs_body(M, Bt, T, *K, seed, 0, e, lane);
-  __syncthreads();                       // reward / done of this env written (lane 0) before every lane tests them
-  if (reset_body(Bt, T, nq, M.nv, M.nu, qpos0, nullptr, seed, env_offset, auto_max, e, lane)) {
-    __syncthreads();                     // the new state rows are complete before they are read back
-    myodm_obs_body(M, Bt, T, *K, seed, 1, e, lane);
-  }
+// MYO_TASK_TRACK (configured by myo_batch_configure_track: no configure hook).  The classic flavour observes with MyodmTask, keyed by the seed of the
+// last reset, and has a fused epilogue; the MJX flavour observes the state-only row and myo_bench_rollout skips its epilogue (the step kernel's own)
+static int track_obs(myo_batch* b, hipStream_t s, int obs_only, int reset_only) {
+  return b->track_flavour == 1 ? launch_task_obs<MyodmTask>(b, s, obs_only, reset_only) : launch_task_obs<StateTask>(b, s, obs_only, reset_only);
 }
+static int track_post(myo_batch* b, hipStream_t s, uint64_t seed, int max_episode_steps) {
+  b->reset_seed = seed;
+  return launch_task_post<MyodmTask>(b, s, seed, max_episode_steps);
+}
+static const TaskHooks track_hooks = {nullptr, track_obs, track_post};
 
 #endif  // MYO_TASK_MYODM_H

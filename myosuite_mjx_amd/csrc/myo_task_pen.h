@@ -83,25 +83,23 @@ __device__ __forceinline__ void pen_obs_body(const DevModel& M, const DevBatch& 
   }
 }
 
-__global__ void __launch_bounds__(64) pen_obs_kernel(DevModel M, DevBatch Bt, TaskDev T, int obs_only, int reset_only) {
-  const int e = blockIdx.x;
-  if (e >= Bt.B) return;
-  if (reset_only && Bt.elapsed[e] != 0) return;    // refresh only the rows of envs an auto-reset just touched
-  pen_obs_body(M, Bt, T, obs_only, e, threadIdx.x);
+using PenTask = StateObs<pen_obs_body>;
+// pen_v0.py: the pen is the model's last six joints, 3 slides + 3 hinges of one root body; sites = object top / bottom, target top / bottom,
+// eps_ball
+static int pen_configure(myo_batch* b, const myo_task_config* c) {
+  const myo_model* m = b->model;
+  const int nv = m->dm.nv;
+  if (!(m->wave_ok && m->trk) || m->nq != nv || nv < 7) return fail(MYO_E_UNSUPPORTED, "pen task: a TrackEnv-class model without free / ball joints whose last six joints are the pen's");
+  bool ok = root_link_of_dofs(m, nv - 6, 6) >= 0;
+  for (int k = 0; k < 6; k++) ok = ok && m->dof_type[nv - 6 + k] == (k < 3 ? 2 : 3);
+  if (!ok) return fail(MYO_E_UNSUPPORTED, "pen task: the last six joints must be 3 slides + 3 hinges of one root body");
+  if (c->ntip != 5 || c->ntarget != 0) return fail(MYO_E_ARG, "pen task: ntip = 5 (object top, object bottom, target top, target bottom, eps_ball) and ntarget = 0");
+  for (int k = 0; k < 5; k++) if (c->tip_site[k] < 0 || c->tip_site[k] >= m->dims.nsite) return fail(MYO_E_ARG, "pen task: site id out of range");
+  for (int k = 0; k < 3; k++) if (!std::isfinite(c->tip_lpos[k])) return fail(MYO_E_ARG, "pen task: tip_lpos must be finite");
+  if (!(c->far_th > 0.f) || !(c->pose_thd == c->pose_thd)) return fail(MYO_E_ARG, "pen task: far_th > 0, pose_thd a number");
+  b->task.obs_dim = (nv - 6) + 21 + m->dm.na_obs;
+  return MYO_OK;
 }
-
-// myo_bench_rollout's fused epilogue (keyturn_post_kernel's pattern): observation / reward / done of the stepped state, auto-reset, and the
-// first observation of the new episodes, in one launch
-__global__ void __launch_bounds__(64) pen_post_kernel(DevModel M, DevBatch Bt, TaskDev T, int nq, const float* qpos0, uint64_t seed, int env_offset,
-                                                      int auto_max) {
-  const int e = blockIdx.x, lane = threadIdx.x;
-  if (e >= Bt.B) return;
-  pen_obs_body(M, Bt, T, 0, e, lane);
-  __syncthreads();                       // reward / done of this env written (lane 0) before every lane tests them
-  if (reset_body(Bt, T, nq, M.nv, M.nu, qpos0, nullptr, seed, env_offset, auto_max, e, lane)) {
-    __syncthreads();                     // the new state rows (and the target orientation) are complete before they are read back
-    pen_obs_body(M, Bt, T, 1, e, lane);
-  }
-}
+static const TaskHooks pen_hooks = {pen_configure, launch_task_obs<PenTask>, launch_task_post<PenTask>};
 
 #endif  // MYO_TASK_PEN_H

@@ -173,6 +173,24 @@ typedef enum myo_task { MYO_TASK_NONE = 0, MYO_TASK_POSE = 1, MYO_TASK_REACH = 2
                                                  target2, target1 - ball1, target2 - ball2 (no act); MYO_F_SITEXPOS: the four sites (12
                                                  floats).  reward = -w_pose d1 - w_reach d2; done = a ball site below far_th (drop_th);
                                                  solved = d1 < pose_thd and d2 < pose_thd (proximity_th) and not done */
+                        MYO_TASK_DIE = 10, /* ReorientEnvV0 (envs/myo/myochallenge/reorient_v0.py; myoChallengeDieReorient{Demo,P1}-v0), models
+                                              of the TrackEnv class whose last six joints are the die (3 slides + 3 hinges of one root body, a
+                                              child of the world).  ntip = 8 sites: object_o, object_x, object_y, object_z, target_o, target_x,
+                                              target_y, target_z (origin and axis points of the two frames; column k of a frame = (x_k - x_o) /
+                                              |lpos_k - lpos_o|); quat_body = the target body, which carries the four target sites and no
+                                              colliding geom.  ntarget = 3: the per-env row of MYO_F_TARGET is the goal offset, the target's
+                                              position minus its compiled one, drawn at every reset as U(target_lo, target_hi) (target_generate
+                                              = 1; goal_pos on all three components); MYO_F_BODYQUAT_RANGE = goal_rot on all three Euler
+                                              angles draws the target's orientation.  goal_obj_offset = target_o - object_o at qpos0, a model
+                                              constant worked out at configure time.  obs = qpos[:nq - 7] (the reference's off-by-one is kept),
+                                              qvel[:nv - 6] * dt, obj_pos (3), goal_pos (3), pos_err = goal_pos - obj_pos - goal_obj_offset (3),
+                                              obj_rot = mat2euler(object frame) (3), goal_rot = mat2euler(target frame) (3), rot_err = goal_rot
+                                              - obj_rot (3) (no act; mat2euler: utils/quat_math.py:96-115), with the site positions of the
+                                              post-step state (also MYO_F_SITEXPOS, 24 floats).  pos_dist = |pos_err|, rot_dist = |rot_err|,
+                                              drop = pos_dist > far_th (drop_th); reward = -w_pose pos_dist - w_reach rot_dist + w_bonus
+                                              ([pos_dist < 2 near_th] + [pos_dist < near_th]) - w_act_reg |act|/na - w_penalty drop; done =
+                                              drop; solved = pos_dist < near_th (pos_th; +inf allowed) and rot_dist < pose_thd (rot_th) and not
+                                              drop.  The reset puts envs at init_qpos with zero velocity */
                         MYO_TASK_HOLD = 4 /* ObjHoldFixedEnvV0 (envs/myo/myobase/obj_hold_v0.py:13-118): the model's LAST joint is the free
                                              object; obs = hand qpos, hand qvel*dt, object position, goal - object, act; target = goal (3) */
 } myo_task;
@@ -194,7 +212,8 @@ typedef struct myo_task_config {
    * entry; host pointers, nq floats each (copied), all four or none (NULL) */
   const float *reset_noise_lo, *reset_noise_hi, *reset_clip_lo, *reset_clip_hi;
   const float* init_qvel; /* host pointer, nv floats (copied) or NULL = zero */
-  float tip_lpos[3];      /* stand: the tip site's position in the root link's frame; pen: the object body's origin in its link frame */
+  float tip_lpos[3];      /* stand: the tip site's position in the root link's frame; pen: the object body's origin in its link frame
+                             (die: unused, the library works goal_obj_offset out itself) */
   int quat_body;          /* > 0: selects the body of MYO_F_BODYQUAT / MYO_F_BODYQUAT_RANGE (compiled-model body id; 0: no selection, an
                              earlier one stays).  A batch selects one body once.  MYO_E_UNSUPPORTED for models outside the TrackEnv class
                              and for a body with joints or whose parent is not the world */

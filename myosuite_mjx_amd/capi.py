@@ -27,6 +27,7 @@ TASK_TRACK = 6
 TASK_KEYTURN = 7
 TASK_PEN = 8
 TASK_BAODING = 9
+TASK_DIE = 10
 FLAG_BAD_STATE, FLAG_BAD_QACC, FLAG_CONTACT_OVERFLOW, FLAG_CAND_OVERFLOW = 1, 2, 4, 8
 
 

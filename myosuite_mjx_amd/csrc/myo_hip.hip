@@ -9,7 +9,7 @@
 //   myo_ldl_mfma.h      dense LDL^T of the Newton Hessian on the FP32 matrix cores (included by myo_kernel_wave.h)
 //   myo_kernels_aux.h   RNG, placement hint, random actions, policy inference, reset, state-only observations, task_obs_kernel / task_post_kernel
 //   myo_host.h          host records: myo_model, myo_batch, the per-task hook record (TaskHooks) and its generic launchers
-//   myo_task_*.h        key-turn, pen, baoding, classic MyoDM: a task's observation body, its configure checks and its hook record
+//   myo_task_*.h        key-turn, pen, baoding, die, classic MyoDM: a task's observation body, its configure checks and its hook record
 //   myo_host_model.h    myo_model_load in pieces: blob view, table upload, packing of the per-lane records, kernel class
 //   myo_hip.hip         host side: batches, the table of step-kernel instantiations, launches, the task table, the extern "C" entry points
 //
@@ -31,6 +31,7 @@
 #include "myo_task_keyturn.h"
 #include "myo_task_pen.h"
 #include "myo_task_baoding.h"
+#include "myo_task_die.h"
 #include "myo_task_myodm.h"
 #include "myo_host_model.h"
 
@@ -813,6 +814,7 @@ static const TaskHooks* task_hooks(int task) {
     case MYO_TASK_KEYTURN: return &keyturn_hooks;
     case MYO_TASK_PEN: return &pen_hooks;
     case MYO_TASK_BAODING: return &baoding_hooks;
+    case MYO_TASK_DIE: return &die_hooks;
     default: return nullptr;   // MYO_TASK_NONE
   }
 }

@@ -1,0 +1,148 @@
+// myo_task_die.h -- ReorientEnvV0 (envs/myo/myochallenge/reorient_v0.py; myoChallengeDieReorient{Demo,P1}-v0) observation / reward / done /
+// solved, MYO_TASK_DIE.
+//
+// The model (myohand_die) is of the TrackEnv class (the die's boxes), so, as for the key turn, the pen and the balls, this kernel runs its
+// own forward kinematics of what the task reads, from the post-step qpos: the die's and the target's origin and axis sites (object_o / x /
+// y / z, target_o / x / y / z), one lane each.  Column k of a site frame is (x_k - x_o) / |lpos_k - lpos_o|, the way the pen's axis is
+// built.  The target is world-welded: its sites are static, turn with the per-env orientation of MYO_F_BODYQUAT and shift by the env's
+// MYO_F_TARGET row (the goal offset; the target carries no colliding geom, so the step kernel never reads it).  One 64-lane workgroup per env.
+#ifndef MYO_TASK_DIE_H
+#define MYO_TASK_DIE_H
+
+// utils/quat_math.py:96-115 mat2euler, both branches; cx, cy, cz = the columns of the rotation matrix
+__device__ __forceinline__ void die_mat2euler(float* eu, const float* cx, const float* cy, const float* cz) {
+  const float c = sqrtf(cz[2] * cz[2] + cz[1] * cz[1]);
+  eu[1] = -atan2f(-cz[0], c);
+  if (c > 8.8817841970012523e-16f) {   // _EPS4 = 4 eps(float64)
+    eu[2] = -atan2f(cy[0], cx[0]);
+    eu[0] = -atan2f(cz[1], cz[2]);
+  } else {
+    eu[2] = -atan2f(-cx[1], cy[1]);
+    eu[0] = 0.f;
+  }
+}
+
+// reorient_v0.py:111-176.  Row: qpos[:-7] (nq - 7: the reference's off-by-one is kept), qvel[:-6] * dt (nv - 6), obj_pos (3), goal_pos (3),
+// pos_err = goal_pos - obj_pos - goal_obj_offset (3), obj_rot (3), goal_rot (3), rot_err = goal_rot - obj_rot (3); act is not observed.
+// T.tip_site = object_o, object_x, object_y, object_z, target_o, target_x, target_y, target_z; T.tip_lpos = goal_obj_offset; Bt.target row =
+// the goal offset from the compiled target position.
+__device__ __forceinline__ void die_obs_body(const DevModel& M, const DevBatch& Bt, const TaskDev& T, int obs_only, const int e, const int lane) {
+  const int nv = M.nv, nu = M.nu, nh = nv - 6, b0 = 2 * nh - 1;
+  const float dt = (float)T.frame_skip * M.timestep;
+  float* o = Bt.obs + (size_t)e * T.obs_dim;
+  const float* q = Bt.qpos + (size_t)e * nv;
+  const float* v = Bt.qvel + (size_t)e * nv;
+  const float* a = Bt.act + (size_t)e * nu;
+  float p[3] = {0.f, 0.f, 0.f};
+  if (lane < 8) {   // lanes 0-3: the die's sites, 4-7: the target's
+    const int s = T.tip_site[lane];
+    link_point_pos(M, Bt, q, e, M.site_link[s], M.site_lpos + 3 * s, p);
+    if (lane >= 4) {   // a static site of the per-env oriented body (checked at configure), moved by the env's goal offset
+      if (Bt.bquat) {
+        float D[9], Rq[9], w[3];
+        const float* c = Bt.bq_c;
+        const float* bq = Bt.bquat + 4 * (size_t)e;
+        const float qe[4] = {bq[0], bq[1], bq[2], bq[3]};
+        quat2mat(Rq, qe);
+        matmul3(D, Rq, c);
+        const float d[3] = {p[0] - c[9], p[1] - c[10], p[2] - c[11]};
+        matvec(w, D, d);
+        p[0] = c[9] + w[0]; p[1] = c[10] + w[1]; p[2] = c[11] + w[2];
+      }
+      const float* g = Bt.target + 3 * (size_t)e;
+      p[0] += g[0]; p[1] += g[1]; p[2] += g[2];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) { p[k] += M.origin[k]; Bt.sitexpos[(size_t)e * 24 + 3 * lane + k] = p[k]; }
+  }
+  float x[8][3];
+#pragma unroll
+  for (int i = 0; i < 8; i++)
+#pragma unroll
+    for (int k = 0; k < 3; k++) x[i][k] = __shfl(p[k], i);
+  float col[6][3];   // the columns of the die's frame (0-2) and of the target's (3-5)
+#pragma unroll
+  for (int f = 0; f < 2; f++)
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      const float* l0 = M.site_lpos + 3 * T.tip_site[4 * f];
+      const float* lk = M.site_lpos + 3 * T.tip_site[4 * f + 1 + k];
+      const float d[3] = {lk[0] - l0[0], lk[1] - l0[1], lk[2] - l0[2]};
+      const float inv = 1.0f / norm3(d);   // (rotation invariant: from the model's site positions)
+#pragma unroll
+      for (int c = 0; c < 3; c++) col[3 * f + k][c] = (x[4 * f + 1 + k][c] - x[4 * f][c]) * inv;
+    }
+  float orot[3], grot[3], perr[3], rerr[3];
+  die_mat2euler(orot, col[0], col[1], col[2]);
+  die_mat2euler(grot, col[3], col[4], col[5]);
+#pragma unroll
+  for (int k = 0; k < 3; k++) { perr[k] = x[4][k] - x[0][k] - T.tip_lpos[k]; rerr[k] = grot[k] - orot[k]; }
+  if (lane < 3) {
+    o[b0 + lane] = x[0][lane];
+    o[b0 + 3 + lane] = x[4][lane];
+    o[b0 + 6 + lane] = perr[lane];
+    o[b0 + 9 + lane] = orot[lane];
+    o[b0 + 12 + lane] = grot[lane];
+    o[b0 + 15 + lane] = rerr[lane];
+  }
+  for (int i = lane; i < nh; i += 64) {
+    if (i < nh - 1) o[i] = q[i];
+    o[nh - 1 + i] = v[i] * dt;
+  }
+  if (obs_only) return;
+  float act2 = 0.f;
+  for (int i = lane; i < nu; i += 64) { const float ai = a[i]; if (M.act_obs[i] >= 0) act2 += ai * ai; }
+  const float actn = sqrtf(wave_sum(act2)) / (float)(M.na_obs > 0 ? M.na_obs : 1);
+  if (lane == 0) {
+    const float pos_dist = norm3(perr), rot_dist = norm3(rerr);
+    const bool drop = pos_dist > T.far_th;
+    const float bonus = (pos_dist < 2.f * T.near_th ? 1.f : 0.f) + (pos_dist < T.near_th ? 1.f : 0.f);
+    Bt.reward[e] = T.w_pose * (-pos_dist) + T.w_reach * (-rot_dist) + T.w_bonus * bonus + T.w_act_reg * (-actn) + T.w_penalty * (drop ? -1.f : 0.f);
+    Bt.solved[e] = (pos_dist < T.near_th && rot_dist < T.pose_thd && !drop) ? 1.f : 0.f;
+    Bt.done[e] = drop ? 1.f : 0.f;
+  }
+}
+
+using DieTask = StateObs<die_obs_body>;
+// reorient_v0.py: the die is the model's last six joints, 3 slides + 3 hinges of one root body; the target is the body of MYO_F_BODYQUAT.
+// goal_obj_offset (:68-71) = target_o - object_o at qpos0, from the compiled body and site positions (both bodies are children of the world)
+static int die_configure(myo_batch* b, const myo_task_config* c) {
+  const myo_model* m = b->model;
+  TaskDev& T = b->task;
+  const int nv = m->dm.nv;
+  if (!(m->wave_ok && m->trk) || m->nq != nv || nv < 8) return fail(MYO_E_UNSUPPORTED, "die task: a TrackEnv-class model without free / ball joints whose last six joints are the die's");
+  const int ol = root_link_of_dofs(m, nv - 6, 6);
+  bool ok = ol >= 0;
+  for (int k = 0; k < 6; k++) ok = ok && m->dof_type[nv - 6 + k] == (k < 3 ? 2 : 3);
+  if (!ok) return fail(MYO_E_UNSUPPORTED, "die task: the last six joints must be 3 slides + 3 hinges of one root body");
+  if (c->ntip != 8 || c->ntarget != 3) return fail(MYO_E_ARG, "die task: ntip = 8 (object_o / x / y / z, target_o / x / y / z) and ntarget = 3 (goal offset)");
+  for (int k = 0; k < 8; k++) if (c->tip_site[k] < 0 || c->tip_site[k] >= m->dims.nsite) return fail(MYO_E_ARG, "die task: site id out of range");
+  if (b->bq_body < 0) return fail(MYO_E_ARG, "die task: quat_body (the target body) must be selected");
+  if (m->site_body.empty() || m->site_pos0.empty() || m->body_pos0.empty()) return fail(MYO_E_UNSUPPORTED, "die task: the model blob lacks the body tables");
+  const int ob = m->site_body[c->tip_site[0]], tb = b->bq_body;
+  for (int k = 0; k < 4; k++)
+    if (m->site_link[c->tip_site[k]] != ol || m->site_body[c->tip_site[k]] != ob || m->site_body[c->tip_site[4 + k]] != tb)
+      return fail(MYO_E_UNSUPPORTED, "die task: the object sites must be on the die's body, the target sites on the quat_body");
+  if (m->body_parent[ob] != 0) return fail(MYO_E_UNSUPPORTED, "die task: the die's body must be a child of the world");
+  auto site_world0 = [&](int body, int s, double* w) {
+    double R[9];
+    quat2mat_d(R, &m->body_quat0[4 * (size_t)body]);
+    const double* sp = &m->site_pos0[3 * (size_t)s];
+    for (int k = 0; k < 3; k++) w[k] = m->body_pos0[3 * (size_t)body + k] + R[3 * k] * sp[0] + R[3 * k + 1] * sp[1] + R[3 * k + 2] * sp[2];
+  };
+  for (int f = 0; f < 2; f++)
+    for (int k = 1; k < 4; k++) {
+      const double *s0 = &m->site_pos0[3 * (size_t)c->tip_site[4 * f]], *sk = &m->site_pos0[3 * (size_t)c->tip_site[4 * f + k]];
+      if (!(std::hypot(sk[0] - s0[0], sk[1] - s0[1], sk[2] - s0[2]) > 1e-6)) return fail(MYO_E_ARG, "die task: an axis site coincides with its origin site");
+    }
+  if (!(c->near_th == c->near_th) || !(c->pose_thd == c->pose_thd) || !(c->far_th == c->far_th)) return fail(MYO_E_ARG, "die task: near_th (pos_th), pose_thd (rot_th) and far_th (drop_th) numbers");
+  double wo[3], wt[3];
+  site_world0(ob, c->tip_site[0], wo);
+  site_world0(tb, c->tip_site[4], wt);
+  for (int k = 0; k < 3; k++) T.tip_lpos[k] = (float)(wt[k] - wo[k]);
+  T.obs_dim = (nv - 7) + (nv - 6) + 18;
+  return MYO_OK;
+}
+static const TaskHooks die_hooks = {die_configure, launch_task_obs<DieTask>, launch_task_post<DieTask>};
+
+#endif  // MYO_TASK_DIE_H

@@ -151,6 +151,15 @@ REGISTRY["myoChallengeBaodingP1-v1"] = dict(
     model="myohand_baoding", task="baoding", max_episode_steps=200, frame_skip=10, normalize_act=True, task_choice="fixed",
     goal_time_period=(5, 5), goal_xrange=(0.025, 0.025), goal_yrange=(0.028, 0.028), drop_th=1.25, proximity_th=0.015,
     weights=dict(pos_dist_1=5.0, pos_dist_2=5.0))
+# myoChallengeDieReorient{Demo,P1}-v0 (envs/myo/myochallenge/__init__.py:308-335, reorient_v0.py): MyoHand + a die on 3 slides + 3 hinges
+# (TrackEnv class: the die's boxes alone).  Palm-up open hand at reset (init_qpos[:-7] = 0, init_qpos[0] = -1.5), die at qpos0; the
+# world-welded target is moved by U(goal_pos)^3 from its compiled position and turned to euler2quat(U(goal_rot)^3) at every reset
+# (BatchedMyoEnv.goal_offset / body_quat).  The die's mass "re-draw" U(0.108, 0.108) is the compiled mass
+REGISTRY["myoChallengeDieReorientDemo-v0"] = dict(
+    model="myohand_die", task="die", max_episode_steps=150, frame_skip=5, normalize_act=True, goal_pos=(0.0, 0.0), goal_rot=(-0.785, 0.785),
+    pos_th=np.inf, rot_th=0.262, drop_th=0.200,
+    weights=dict(pos_dist=100.0, rot_dist=1.0, bonus=0.0, act_reg=0.0, penalty=0.0))
+REGISTRY["myoChallengeDieReorientP1-v0"] = dict(REGISTRY["myoChallengeDieReorientDemo-v0"], goal_pos=(-0.010, 0.010), goal_rot=(-1.57, 1.57), pos_th=0.025)
 # muscle-condition variants (register_env_with_variants, envs/myo/myobase/__init__.py:14-48): myoSarc* (sarcopenia), myoFati* (fatigue)
 # for every myo* id, myoReaf* (EIP -> EPL tendon transfer) for the myoHand* ids
 for _id in [k for k in list(REGISTRY) if k.startswith("myo")]:
@@ -196,6 +205,10 @@ UNSUPPORTED = {
 for _id in ("myoChallengeBaodingP2-v1", "myoSarcChallengeBaodingP2-v1", "myoFatiChallengeBaodingP2-v1"):
     UNSUPPORTED[_id] = ("re-draws the balls' size, mass and friction per episode (obj_size_range, obj_mass_range, obj_friction_change): "
                         "the TrackEnv-class step kernel has no per-env ball size, mass or friction")
+# myoChallengeDieReorientP2-v0 (envs/myo/myochallenge/__init__.py:336-353) and its muscle-condition variants
+for _id in ("myoChallengeDieReorientP2-v0", "myoSarcChallengeDieReorientP2-v0", "myoFatiChallengeDieReorientP2-v0"):
+    UNSUPPORTED[_id] = ("re-draws the die's size, mass and friction per episode (obj_size_change, obj_mass_range, obj_friction_change): "
+                        "the TrackEnv-class step kernel has no per-env die size, mass or friction")
 
 
 class Box:
@@ -230,12 +243,17 @@ class BatchedMyoEnv:
 
     # env kwargs of the reference that gym.make forwards to the env class and that are honoured here (others raise)
     ENV_KWARGS = ("reset_type", "fatigue_reset_random", "fatigue_reset_vec", "weight_bodyname", "weight_range", "target_jnt_range",
-                  "goal_th", "key_init_range", "task_choice", "goal_time_period", "goal_xrange", "goal_yrange", "drop_th", "proximity_th")
+                  "goal_th", "key_init_range", "task_choice", "goal_time_period", "goal_xrange", "goal_yrange", "drop_th", "proximity_th",
+                  "goal_pos", "goal_rot", "pos_th", "rot_th")
     POSE_KWARGS = ("weight_bodyname", "weight_range", "target_jnt_range")   # PoseEnvV0 kwargs (pose_v0.py:56-75): pose tasks only
     KEYTURN_KWARGS = ("goal_th", "key_init_range")                           # KeyTurnEnvV0._setup kwargs (key_turn_v0.py:54-61): key turn only
     # BaodingEnvV1._setup kwargs (baoding_v1.py:54-69): baoding only; its per-env ball size / mass / friction kwargs are refused
     BAODING_KWARGS = ("task_choice", "goal_time_period", "goal_xrange", "goal_yrange", "drop_th", "proximity_th")
     BAODING_REFUSED = ("obj_size_range", "obj_mass_range", "obj_friction_change")
+    # ReorientEnvV0._setup kwargs (reorient_v0.py:45-62): die only (drop_th is shared with baoding); its per-env die size / mass / friction
+    # kwargs are refused
+    DIE_KWARGS = ("goal_pos", "goal_rot", "pos_th", "rot_th", "drop_th")
+    DIE_REFUSED = ("obj_size_change", "obj_mass_range", "obj_friction_change")
 
     def __init__(self, env_id, num_envs=1, device=0, seed=0, env_offset=0, autoreset=True, as_torch=True, **env_kwargs):
         if env_id in UNSUPPORTED:
@@ -250,10 +268,17 @@ class BatchedMyoEnv:
                                           "kernel has no per-env ball size, mass or friction")
             if k in self.BAODING_REFUSED and spec.get("task") == "baoding":
                 continue
+            if k in self.DIE_REFUSED and spec.get("task") == "die":
+                if v is not None:
+                    raise NotImplementedError(f"{env_id}: {k} re-draws the die's size, mass or friction per episode; the TrackEnv-class step "
+                                              "kernel has no per-env die size, mass or friction")
+                continue
+            task_kw = [t for t, names in (("baoding", self.BAODING_KWARGS), ("die", self.DIE_KWARGS)) if k in names]
             if k not in self.ENV_KWARGS or (k in self.POSE_KWARGS and spec.get("task") != "pose") or (k in self.KEYTURN_KWARGS and spec.get("task") != "keyturn") or (
-                    k in self.BAODING_KWARGS and spec.get("task") != "baoding"):
+                    task_kw and spec.get("task") not in task_kw):
                 raise TypeError(f"{env_id}: unsupported env kwarg {k!r} (supported: {self.ENV_KWARGS}; {self.POSE_KWARGS} for pose tasks only, "
-                                f"{self.KEYTURN_KWARGS} for the key-turn task only, {self.BAODING_KWARGS} for the baoding task only)")
+                                f"{self.KEYTURN_KWARGS} for the key-turn task only, {self.BAODING_KWARGS} for the baoding task only, "
+                                f"{self.DIE_KWARGS} for the die task only)")
             spec[k] = v
         self.num_envs = int(num_envs)
         self.device = device
@@ -398,6 +423,24 @@ class BatchedMyoEnv:
                                  init_qpos=init, tip_sites=[m.name2id("site", n) for n in ("ball1_site", "ball2_site", "target1_site", "target2_site")],
                                  pose_thd=float(spec["proximity_th"]), far_th=float(spec["drop_th"]), w_pose=w["pos_dist_1"], w_reach=w["pos_dist_2"])
             self.obs_dim = (m.nq - 14) + 24
+        elif spec["task"] == "die":
+            # reorient_v0.py:45-109, 209-250: palm-up open hand (init_qpos[:-7] = 0: the die's first slide is zeroed too, as the reference
+            # does), die at qpos0; sites = the origin and axis points of the die's and the target's frames.  The goal offset (MYO_F_TARGET row)
+            # ~ U(goal_pos)^3 and the target's Euler angles ~ U(goal_rot)^3 are re-drawn per env at every reset
+            init = np.array(m.qpos0, float)
+            init[:-7] = 0.0
+            init[0] = -1.5
+            (p0, p1), (r0, r1) = ((float(a) for a in spec[k]) for k in ("goal_pos", "goal_rot"))
+            if not (p0 <= p1 and r0 <= r1):
+                raise ValueError(f"{env_id}: goal_pos and goal_rot must be (lo, hi) with lo <= hi")
+            self.batch.configure(task=capi.TASK_DIE, frame_skip=self.frame_skip, reset_random=0, target_generate=1, target_lo=[p0] * 3, target_hi=[p1] * 3,
+                                 init_qpos=init, tip_sites=[m.name2id("site", n) for n in ("object_o", "object_x", "object_y", "object_z",
+                                                                                          "target_o", "target_x", "target_y", "target_z")],
+                                 near_th=float(spec["pos_th"]), pose_thd=float(spec["rot_th"]), far_th=float(spec["drop_th"]),
+                                 w_pose=w["pos_dist"], w_reach=w["rot_dist"], w_bonus=w["bonus"], w_act_reg=w["act_reg"], w_penalty=w["penalty"],
+                                 quat_body=m.name2id("body", "target"))
+            self.obs_dim = (m.nq - 7) + (m.nv - 6) + 18
+            self.batch.set_body_quat_range([r0] * 3, [r1] * 3)
         else:
             tips = [m.name2id("site", t) for t in spec["tips"]]
             n = len(tips)
@@ -491,8 +534,8 @@ class BatchedMyoEnv:
     # -- per-env body orientation (MYO_F_BODYQUAT) ------------------------------------------------------------
     @property
     def body_quat(self):
-        """[num_envs, 4] body_quat (w x y z) of the pen task's target in every env (the batched `sim.model.body_quat[target] = ...` of
-        PenTwirlRandomEnvV0.reset): a torch view of the library's buffer (no copy; writes take effect at the next step / observation).
+        """[num_envs, 4] body_quat (w x y z) of the pen / die task's target in every env (the batched `sim.model.body_quat[target] = ...` of
+        PenTwirlRandomEnvV0.reset / ReorientEnvV0.reset): a torch view of the library's buffer (no copy; writes take effect at the next step / observation).
         With as_torch=False: a numpy copy (assign the property to write it)."""
         return self.view(capi.F_BODYQUAT)
 
@@ -522,6 +565,26 @@ class BatchedMyoEnv:
             self.view(capi.F_TARGET).copy_(self._torch.as_tensor(value, dtype=self._torch.float32).expand(self.num_envs, -1))
         else:
             self.batch.write(capi.F_TARGET, np.broadcast_to(np.asarray(value, np.float32), (self.num_envs, 5)))
+
+    # -- per-env goal offset of the die task (MYO_F_TARGET) ---------------------------------------------------
+    @property
+    def goal_offset(self):
+        """[num_envs, 3] offset of the die task's target from its compiled position in every env (the batched `sim.model.body_pos[target]
+        = goal_init_pos + ...` of ReorientEnvV0.reset, as an offset); its orientation is `body_quat`.  A torch view of the library's buffer
+        (no copy; writes move the goal from the next observation on, until the env's next reset re-draws it).  With as_torch=False: a
+        numpy copy (assign the property to write it)."""
+        if self.spec["task"] != "die":
+            raise AttributeError("goal_offset: die task only")
+        return self.view(capi.F_TARGET)
+
+    @goal_offset.setter
+    def goal_offset(self, value):
+        if self.spec["task"] != "die":
+            raise AttributeError("goal_offset: die task only")
+        if self.as_torch:
+            self.view(capi.F_TARGET).copy_(self._torch.as_tensor(value, dtype=self._torch.float32).expand(self.num_envs, -1))
+        else:
+            self.batch.write(capi.F_TARGET, np.broadcast_to(np.asarray(value, np.float32), (self.num_envs, 3)))
 
     # -- zero-copy views ---------------------------------------------------------------------------------
     def view(self, field):

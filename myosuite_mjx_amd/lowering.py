@@ -393,7 +393,6 @@ def lower(cm):
         return root_anchor[root], reach[l] + np.linalg.norm(geom_lpos[g] - first_anchor(l)) + m.geom_rbound[g]
 
     pruned = 0
-    has_frictionloss = "dof_frictionloss" in A and bool((np.asarray(A["dof_frictionloss"]) > 0).any())
     for g1, g2 in m.pair_geom:
         t1, t2 = m.geom_type[g1], m.geom_type[g2]
         margin = max(m.geom_margin[g1], m.geom_margin[g2])
@@ -420,10 +419,9 @@ def lower(cm):
             if not (plane_ok or cyl_ok):
                 raise NotImplementedError(f"HIP path: cannot prune static geom {stat} against moving geom {mov}")
         has_hull = "mesh_vert" in A and len(A["mesh_vert"]) > 0
-        # boxes go through the TRK kernel's MPR (box support function); they are accepted with convex hulls, or when the model is of the
-        # TrackEnv class anyway through joint friction loss (myohand_keyturn: the key's box bit, frictionloss on keyjoint)
-        box_ok = has_hull or has_frictionloss
-        ok = (GEOM_CAPSULE, GEOM_ELLIPSOID, GEOM_SPHERE, GEOM_CYLINDER) + ((GEOM_BOX,) if box_ok else ()) + ((GEOM_MESH,) if has_hull else ())
+        # boxes go through the TRK kernel's MPR (box support function): a colliding box puts the model in the TrackEnv class by itself
+        # (hip_trk[2] below), whatever else does (myohand_keyturn: frictionloss on keyjoint; myohand_die: nothing but the die's boxes)
+        ok = (GEOM_CAPSULE, GEOM_ELLIPSOID, GEOM_SPHERE, GEOM_CYLINDER, GEOM_BOX) + ((GEOM_MESH,) if has_hull else ())
         plane_pair = t1 == GEOM_PLANE
         hfield_pair = t1 == GEOM_HFIELD and t2 in ok and geom_link[g1] < 0      # world-fixed height field first (the compiler orders it so)
         if not plane_pair and not hfield_pair and (t1 not in ok or t2 not in ok):

@@ -131,7 +131,9 @@ class Model:
     def with_body_pos(self, body, pos) -> "Model":
         """Copy of the model with `body_pos[body] = pos` (`body`: id or name), as KeyTurnEnvV0.reset moves the key
         (envs/myo/myobase/key_turn_v0.py:164-167).  The HIP tables follow for a body that heads a kinematic root link (its link origin moves
-        by the same amount); nothing else changes (inertias, invweights and lengthranges keep their values, as without mj_setConst)."""
+        by the same amount), and for a jointless child of the world (ReorientEnvV0.reset moves the die's target,
+        envs/myo/myochallenge/reorient_v0.py:210-215: its static geoms and sites are lowered again); nothing else changes (inertias,
+        invweights and lengthranges keep their values, as without mj_setConst)."""
         b = self.body_name2id(body) if isinstance(body, str) else int(body)
         if not 0 < b < self.nbody:
             raise ValueError(f"no movable body {body!r}")
@@ -141,7 +143,14 @@ class Model:
         arrays = {k: np.array(v, copy=True) for k, v in self.arrays.items()}
         delta = pos - arrays["body_pos"][b]
         arrays["body_pos"][b] = pos
-        if "hip_body_link" in arrays:
+        if "hip_body_link" in arrays and int(arrays["body_jntnum"][b]) == 0 and int(arrays["body_parentid"][b]) == 0:
+            # a jointless child of the world (myohand_die's target, ReorientEnvV0.reset): static geoms and sites, lowered again
+            from .lowering import lower
+            from .mjcf import CompiledModel
+            cm = CompiledModel(arrays={k: v for k, v in arrays.items() if not k.startswith("hip_")}, names=self.names)
+            lower(cm)
+            arrays = cm.arrays
+        elif "hip_body_link" in arrays:
             link = int(arrays["hip_body_link"][b])
             heads = link >= 0 and int(arrays["hip_link_parent"][link]) < 0 and int(arrays["body_parentid"][b]) == 0 and \
                 min(k for k in range(1, self.nbody) if int(arrays["hip_body_link"][k]) == link) == b

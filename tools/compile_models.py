@@ -38,6 +38,7 @@ GOLDEN = {
     "myohand_keyturn": "myosuite/envs/myo/assets/hand/myohand_keyturn.xml",   # KeyTurnEnvV0: a box bit and joint friction loss (TrackEnv class)
     "myohand_pen": "myosuite/envs/myo/assets/hand/myohand_pen.xml",           # PenTwirl*EnvV0: condim-4 pen pairs (TrackEnv class), plane - cylinder
     "myohand_baoding": "myosuite/envs/myo/assets/hand/myohand_baoding.xml",   # BaodingEnvV1: two free balls (TrackEnv class), plane - sphere
+    "myohand_die": "myosuite/envs/myo/assets/hand/myohand_die.xml",           # ReorientEnvV0: the die's boxes alone make it TrackEnv class
 }
 
 if __name__ == "__main__":

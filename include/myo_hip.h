@@ -128,6 +128,19 @@ enum {
                         returns MYO_E_ARG */
 };
 
+/* touch sensors and contact forces (ids continue after MYO_F_BODYQUAT_RANGE); both read-only (a host write returns MYO_E_ARG) and absent
+ * (MYO_E_ARG) until myo_batch_enable_sensors.  Values are those of d.sensordata after mj_step: the forces of the last substep's solve of the
+ * last myo_step, at that substep's pre-integration state; zeros for an env that launch reset (bad state) or that myo_reset / myo_autoreset
+ * reset since */
+enum {
+  MYO_F_SENSORDATA = 30, /* [B][nsensor] touch sensors, in the model's sensor order: summed normal force of the contacts the sensor counts
+                            (mj_computeSensor's rule: a geom on the site's body, positive normal force, the ray from the contact point along
+                            the normal -- reversed when the site's body is geom 2's -- meets the site's box / sphere) */
+  MYO_F_CFRC             /* [B][(nsensor + 1) * 3] world force those contacts put on the model (contacts between two moving geoms are internal
+                            and add nothing), then one row with the force of ALL contacts against world-fixed geoms: the ground reaction force */
+};
+
+
 /* action -> control map applied inside myo_step (base_v0.py:87-91) */
 enum {
   MYO_ACTMAP_NONE = 0,
@@ -314,6 +327,7 @@ int myo_batch_set_fatigue_reset(myo_batch*, int mode, const float* fatigue_vec);
  * (envs/myo/myobase/obj_hold_v0.py:122-140): every reset of an env draws size ~ U(lo, hi) per axis; mass and inertia are untouched, as in
  * the reference (the model is not recompiled).  lo == hi == NULL switches the override off.  Generic large-kernel models only. */
 int myo_batch_set_geom_override(myo_batch*, int geom_id, const float* size_lo, const float* size_hi);
+/* touch sensors: myo_batch_enable_sensors / myo_model_nsensor are declared in myo_hip_sensors.h (included at the end of this file) */
 /* device pointer + pitch (elements per env row) of a field */
 int myo_batch_field(myo_batch*, int field, void** dev_ptr, size_t* pitch, size_t* width);
 /* synchronous host copies (tests / plumbing without torch); host buffers are [B][width] */
@@ -379,6 +393,8 @@ int myo_policy_load(int device, int obs_dim, int act_dim, int nlayers, const int
 void myo_policy_free(myo_policy*);
 int myo_policy_act(myo_policy*, const float* obs_dev, int B, float* action_dev, int deterministic, uint64_t seed, uint64_t step,
                    int env_offset, void* stream);
+
+#include "myo_hip_sensors.h"
 
 #ifdef __cplusplus
 }

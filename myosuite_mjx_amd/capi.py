@@ -17,6 +17,7 @@ SRC_PATH = os.path.join(_HERE, "csrc", "myo_hip.hip")
  F_QACC, F_TENLEN, F_ACTFORCE, F_SITEXPOS, F_ELAPSED, F_ACTION, F_FATIGUE, F_HFIELD, F_GEOMSIZE, F_LINKX, F_METRICS,
  F_BODYMASS, F_BODYMASS_RANGE, F_BODYPOS, F_BODYPOS_RANGE) = range(28)
 F_BODYQUAT, F_BODYQUAT_RANGE = 28, 29      # per-env orientation of one world-welded body (TaskConfig.quat_body selects it)
+F_SENSORDATA, F_CFRC = 30, 31              # touch sensors [B, nsensor] and contact forces [B, (nsensor + 1) * 3] (HipBatch.enable_sensors)
 INT_FIELDS = (F_FLAGS, F_DIAG, F_ELAPSED)
 BENCH_OBS, BENCH_FRESH_ACTIONS, BENCH_AUTORESET = 1, 2, 4
 ACTMAP_NONE, ACTMAP_MUSCLE_SIGMOID, ACTMAP_SIGMOID_FATIGUE, ACTMAP_SIGMOID_REAFFERENTATION, ACTMAP_CTRLRANGE = 0, 1, 2, 3, 4
@@ -96,7 +97,8 @@ def build_library(force=False, verbose=False):
     """hipcc --offload-arch=gfx950 -> libmyo_hip.so next to this file (cross-compiles without a GPU)."""
     csrc = os.path.dirname(SRC_PATH)
     newest = max(os.path.getmtime(os.path.join(csrc, f)) for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
-    newest = max(newest, os.path.getmtime(os.path.join(os.path.dirname(os.path.dirname(csrc)), "include", "myo_hip.h")))
+    inc = os.path.join(os.path.dirname(os.path.dirname(csrc)), "include")
+    newest = max(newest, *(os.path.getmtime(os.path.join(inc, f)) for f in os.listdir(inc)))
     if not force and os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= newest:
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -188,6 +190,8 @@ def lib():
         L.myo_obs_reset_only.argtypes = [C.c_void_p, C.c_void_p]
         L.myo_batch_set_condition.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.myo_batch_set_fatigue_reset.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.myo_batch_enable_sensors.argtypes = [C.c_void_p]
+        L.myo_model_nsensor.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -210,6 +214,10 @@ class HipModel:
         self.dims = Dims()
         _chk(lib().myo_model_dims(self.h, C.byref(self.dims)))
         self.device = device
+
+    @property
+    def nsensor(self):
+        return int(lib().myo_model_nsensor(self.h))
 
     def set_switch(self, disable_contact=0, disable_limit=0, disable_ellipsoid=0):
         _chk(lib().myo_model_set_switch(self.h, disable_contact, disable_limit, disable_ellipsoid))
@@ -347,6 +355,11 @@ class HipBatch:
             return
         lo, hi = (C.c_float * 3)(*[float(x) for x in size_lo]), (C.c_float * 3)(*[float(x) for x in size_hi])
         _chk(lib().myo_batch_set_geom_override(self.h, int(geom_id), lo, hi))
+
+    def enable_sensors(self):
+        """Allocate F_SENSORDATA / F_CFRC and turn on their readout in the step kernel (36-dof-class Euler models with touch sensors,
+        lanes = 64; anything else raises MyoError with the library's reason)."""
+        _chk(lib().myo_batch_enable_sensors(self.h))
 
     def obs_reset_only(self, stream=None):
         _chk(lib().myo_obs_reset_only(self.h, stream))

@@ -154,6 +154,11 @@ struct DevBatch {
   float* bquat_range;      // [B][6] Euler lo | hi: body_quat = euler2quat(U(lo, hi)) at every reset of an env with hi > lo in some component
   const float* bq_c;       // [12] R(q0)^T (row-major) | body origin (lowered coordinates)
   const int* bq_flag;      // [ncg + nsite] 1: collision geom / site of that body
+  // touch sensors and contact forces (myo_batch_enable_sensors; 36-dof-class Euler instantiations of the wave kernel): written by the epilogue
+  // of the last substep's solve; NULL: off
+  float* sens;             // [B][ntouch] MYO_F_SENSORDATA: summed normal force of the contacts a touch sensor counts
+  float* cfrc;             // [B][ntouch + 1][3] MYO_F_CFRC: their summed world force on the model; last row = all contacts against world-fixed geoms
+  int ntouch;
 };
 #define NCX 48      // overflow contact rows ALLOCATED per env; a kernel with NC LDS slots uses 64 - NC of them: 64 contacts in all
 #define NCX2 96     // TRK models: 128 contacts, 32 in LDS + 96 rows; rows of the second bank also hold that contact's solver state

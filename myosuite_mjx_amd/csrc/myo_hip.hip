@@ -71,6 +71,8 @@ int myo_model_dims(const myo_model* m, myo_dims* out) {
   return MYO_OK;
 }
 
+int myo_model_nsensor(const myo_model* m) { return m ? m->dw.ntouch : 0; }
+
 int myo_model_set_switch(myo_model* m, int dc, int dl, int de) {
   if (!m) return fail(MYO_E_ARG, "null model");
   m->dm.disable_contact = dc; m->dm.disable_limit = dl; m->dm.disable_ellipsoid = de;
@@ -104,6 +106,7 @@ int myo_batch_create(const myo_model* m, int B, myo_batch** out) {
   BA(b->d_action, (size_t)B * nu)
   BA(d.fatigue, (size_t)B * 3 * nu)
   d.hfield = nullptr; d.gsize = nullptr; d.gsize_cg = -1;
+  d.sens = nullptr; d.cfrc = nullptr; d.ntouch = 0;
   d.ovf = nullptr; d.ovf_cand = nullptr; d.ovf_row = 0; d.ovf_rows = 0; d.linkx = nullptr; d.track = nullptr; d.env_offset = 0;
   if (m->trk) { BA(d.linkx, (size_t)B * 12 * m->dm.nl) }
   if (m->wave_ok) {   // contact-table overflow rows of the wave kernel (instantiations <24,8,...> and <36,20,...>)
@@ -437,6 +440,33 @@ static int bq_start(myo_batch* b) {
   return MYO_OK;
 }
 
+// touch sensors and contact forces (MYO_F_SENSORDATA / MYO_F_CFRC): the refusals, shared by the start and the launches after it.  Host
+// side only: a refused model never reaches the GPU
+static int sens_check(const myo_batch* b) {
+  const myo_model* m = b->model;
+  if (m->dw.ntouch <= 0) return fail(MYO_E_UNSUPPORTED, "sensors: the model blob has no touch sensors (no hip_touch table)");
+  if (m->rk4) return fail(MYO_E_UNSUPPORTED, "sensors: RK4 models are not supported");
+  if (m->trk) return fail(MYO_E_UNSUPPORTED, "sensors: models of the TrackEnv class are not supported");
+  if (!m->wave_ok || m->wave_cfg != 1) return fail(MYO_E_UNSUPPORTED, "sensors: models of the hand class (24-dof step kernels) are not supported");
+  if (g_lanes != 64) return fail(MYO_E_UNSUPPORTED, "sensors: wave-per-env kernel only (lanes = 64)");
+  return MYO_OK;
+}
+
+int myo_batch_enable_sensors(myo_batch* b) {
+  if (!b) return fail(MYO_E_ARG, "myo_batch_enable_sensors: null");
+  int rc = sens_check(b);
+  if (rc) return rc;
+  if (b->sens_on) return MYO_OK;
+  DevBatch& d = b->db;
+  const int n = b->model->dw.ntouch;
+  float *sd = nullptr, *cf = nullptr;
+  HIPCHK(hipSetDevice(b->model->device));
+  if ((rc = balloc(b, (void**)&sd, (size_t)d.B * n * 4)) || (rc = balloc(b, (void**)&cf, (size_t)d.B * 3 * (n + 1) * 4))) return rc;
+  d.sens = sd; d.cfrc = cf; d.ntouch = n;
+  b->sens_on = true;
+  return MYO_OK;
+}
+
 static int field_info(myo_batch* b, int f, void** p, size_t* pitch, size_t* width) {
   const DevModel& dm = b->model->dm;
   DevBatch& d = b->db;
@@ -485,6 +515,12 @@ static int field_info(myo_batch* b, int f, void** p, size_t* pitch, size_t* widt
     case MYO_F_BODYPOS_RANGE: *p = d.bpos_range; *pitch = *width = 6; break;
     case MYO_F_BODYQUAT: *p = d.bquat; *pitch = *width = 4; break;         // (NULL until the orientation is started)
     case MYO_F_BODYQUAT_RANGE: *p = d.bquat_range; *pitch = *width = 6; break;
+    case MYO_F_SENSORDATA:
+    case MYO_F_CFRC:
+      if (!b->sens_on) return fail(MYO_E_ARG, "MYO_F_SENSORDATA / MYO_F_CFRC: sensors are not enabled (myo_batch_enable_sensors)");
+      *p = f == MYO_F_SENSORDATA ? d.sens : d.cfrc;
+      *pitch = *width = f == MYO_F_SENSORDATA ? (size_t)d.ntouch : (size_t)3 * (d.ntouch + 1);
+      break;
     default: return fail(MYO_E_ARG, "unknown field");
   }
   return MYO_OK;
@@ -535,6 +571,7 @@ int myo_batch_read(myo_batch* b, int field, void* host, size_t nbytes) {
 int myo_batch_write(myo_batch* b, int field, const void* host, size_t nbytes) {
   void* p; size_t pitch, width;
   if (!b || !host) return fail(MYO_E_ARG, "myo_batch_write: null");
+  if (field == MYO_F_SENSORDATA || field == MYO_F_CFRC) return fail(MYO_E_ARG, "MYO_F_SENSORDATA / MYO_F_CFRC are read-only");
   int rc = field_info(b, field, &p, &pitch, &width);
   if (rc) return rc;
   if (nbytes != (size_t)b->db.B * width * 4) return fail(MYO_E_ARG, "myo_batch_write: size mismatch");
@@ -699,6 +736,7 @@ static int launch_step(myo_batch* b, const float* action, int actmap, int nsub, 
     return fail(MYO_E_UNSUPPORTED, "this model (tendon limits / free joint / equalities / plane contacts) needs the wave-per-env kernel (lanes = 64)");
   // per-env body masses: link tables of every env recomposed once per launch; the step runs on the run-time-sizes instantiation of the
   // model's class (the only ones that read them)
+  if (b->sens_on) { int rc = sens_check(b); if (rc) return rc; }   // (lanes may have changed since the sensors were enabled)
   const bool bm = b->bm_on;
   if (bm) {
     int rc = bm_check(b);

@@ -76,6 +76,7 @@ struct myo_batch {
   bool bm_on = false;            // per-env body-mass override started (DevBatch.bmass / bmass_range / linkc allocated)
   bool bp_on = false;            // per-env root-body offset started (DevBatch.bpos / bpos_range allocated)
   int bq_body = -1;              // body of MYO_F_BODYQUAT (myo_task_config.quat_body; -1: none selected)
+  bool sens_on = false;          // touch sensors / contact forces enabled (DevBatch.sens / cfrc allocated)
   bool bq_on = false;            // per-env body orientation started (DevBatch.bquat / bquat_range / bq_c / bq_flag allocated)
   std::vector<hipEvent_t> kev;   // per-launch event pairs around the step kernel (bench only)
   int kev_pending = 0;           // pairs recorded by asynchronous bench calls and not collected yet

@@ -412,6 +412,34 @@ static int load_body_mass_tables(myo_model* m, const Blob& B) {
   return MYO_OK;
 }
 
+// touch sensors (lowering.py hip_touch / hip_cg_body); optional in the blob: absent tables leave the model without sensors
+static int load_touch_tables(myo_model* m, const Blob& B) {
+  DevModelW& w = m->dw;
+  w.ntouch = 0; w.touch = nullptr; w.cg_body = nullptr;
+  if (!B.has("hip_touch") || !B.has("hip_cg_body")) return MYO_OK;
+  const std::vector<double> t = B.doubles("hip_touch");
+  const std::vector<int> cb = B.ints("hip_cg_body");
+  if (B.rc) return B.rc;
+  const int n = (int)(t.size() / 18);
+  if (n == 0) return MYO_OK;
+  if (t.size() != (size_t)n * 18 || (int)cb.size() != m->dm.ncg) return fail(MYO_E_BLOB, "hip_touch / hip_cg_body: unexpected shape");
+  if (n > MYO_MAX_TOUCH) return fail(MYO_E_UNSUPPORTED, "more than 8 touch sensors");
+  std::vector<float> rec((size_t)n * TOUCHR, 0.f);
+  for (int s = 0; s < n; s++) {
+    const double* T = &t[18 * (size_t)s];
+    float* R = &rec[(size_t)s * TOUCHR];
+    const int link = (int)T[0], type = (int)T[13], body = (int)T[17];
+    if (link >= m->dm.nl || (type != GEOM_SPHERE && type != 6)) return fail(MYO_E_BLOB, "hip_touch: bad link or site type");
+    R[0] = bits_f(link); R[13] = bits_f(type); R[17] = bits_f(body);
+    for (int k = 1; k < 13; k++) R[k] = (float)T[k];
+    for (int k = 14; k < 17; k++) R[k] = (float)T[k];
+  }
+  int rc;
+  if ((rc = upload(m, rec, &w.touch)) || (rc = upload(m, cb, &w.cg_body))) return rc;
+  w.ntouch = n;
+  return MYO_OK;
+}
+
 // the whole load into a model that the caller owns (and frees on any failure)
 static int load_model(myo_model* m, const Blob& B) {
   DevModel& d = m->dm;
@@ -433,6 +461,7 @@ static int load_model(myo_model* m, const Blob& B) {
       (rc = upload(m, P.link_desc, &w.link_desc)) || (rc = upload(m, P.link_adof, &w.link_adof)) || (rc = upload(m, P.dof_anc, &w.dof_anc))) return rc;
   if (B.has("integrator")) { const std::vector<int> ig = B.ints("integrator"); if (B.rc) return B.rc; m->rk4 = !ig.empty() && ig[0] == 1; }
   if ((rc = classify(m, pair_i, dpar))) return rc;
+  if ((rc = load_touch_tables(m, B))) return rc;
   void* p1 = nullptr; void* p2 = nullptr;
   if (hipMalloc(&p1, sizeof(DevModel)) == hipSuccess) m->dev_allocs.push_back(p1);
   if (hipMalloc(&p2, sizeof(DevModelW)) == hipSuccess) m->dev_allocs.push_back(p2);

@@ -89,7 +89,13 @@ struct DevModelW {
   gpi link_adof;        // [nl][2] dofs on the path root -> link l, its own included
   gpi dof_anc;          // [nv][2] dof d and its ancestors
   unsigned int free_rot[2], free_j3[2];   // dofs that are rotations of a free joint / the first rotation of one
+  // touch sensors (lowering.py hip_touch / hip_cg_body; ntouch = 0: the blob has none)
+  int ntouch;
+  gpf touch;            // [ntouch][TOUCHR]: link of the site (bits) | site position (3) | site rotation (9) in that link's frame | type (bits) | half sizes (3) | body (bits)
+  gpi cg_body;          // [ncg] body id of every collision geom
 };
+#define TOUCHR 20
+#define MYO_MAX_TOUCH 8
 #define SEGR 9
 #ifndef MPR_TOL
 #define MPR_TOL 1e-8f      // portal refinement stops when the support plane gains less than this (metres)
@@ -569,6 +575,9 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
     E[Y.ctrl + i] = c;
   }
   float time = uniformf(ldstate<SCHED>(Bt.time + env));
+  if constexpr (SCHED && FULL && !TRK && !RK4) {   // sensors under the scheduler: the first substep's wave clears the env's "reset in this launch" mark
+    if (Bt.sens && s0 == 0 && lane_id == 0) Bt.sens[(size_t)env * Bt.ntouch] = 0.f;
+  }
   // MYO_TASK_TRACK (TRK models): this launch is a whole TrackEnv.step -- reference row of the pre-step time now, reward / done / reset at the end
   const bool track_on = TRK && Bt.track != nullptr && action != nullptr && actmap == MYO_ACTMAP_CTRLRANGE && nsub > 0;
   if constexpr (TRK) { if (track_on) track_lookup(*Bt.track, env, env + Bt.env_offset, time, Bt.elapsed[env], lane_id); }
@@ -2428,6 +2437,97 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
       if (__any(bad) && alive) { flags |= MYO_FLAG_BAD_QACC; alive = false; }
     }
     if (lane < nv) warm_row[lane] = qacc;
+    // ---------------------------------------------------------------- touch sensors and contact forces (DevBatch.sens; NULL: off, one uniform branch)
+    // Readout of the solve that has just finished, on the last substep of the launch only (under the scheduler: by the wave that runs it).
+    // lane = contact: the pyramid forces of the final iterate are -cD * cjar on the active rows, exactly what the last J^T f used; the contact
+    // frame is rebuilt as the row stage built it.  A touch sensor counts a contact by MuJoCo's rule (mj_computeSensor): one of
+    // its geoms on the sensor's body, a positive normal force, and the ray from the contact point along the normal (reversed when the
+    // sensor's body is geom 2's) meeting the site volume.  The 24-dof, TRK and RK4 instantiations have no such code.
+    if constexpr (FULL && !TRK && !RK4) {
+      if (Bt.sens && step == nsub - 1) {
+        const int nts = Bt.ntouch;
+        float fn = 0.f, Fw[3] = {0.f, 0.f, 0.f}, cp[3] = {0.f, 0.f, 0.f}, cn[3] = {0.f, 0.f, 1.f};
+        int cb1 = -1, cb2 = -1;
+        if (lane < ncon_real) {   // (lanes beyond the contacts -- tendon-limit rows included -- contribute exact zeros, whatever their registers hold)
+          const float* g = lane < NC ? nullptr : ovf_env + (lane - NC) * ovf_row;
+          const int cw_ = lane < NC ? ((const int*)(E + Y.cpair))[lane] : ((const int*)g)[7];
+#pragma unroll
+          for (int k = 0; k < 3; k++) { cp[k] = lane < NC ? E[Y.cpos + 3 * lane + k] : g[1 + k]; cn[k] = lane < NC ? E[Y.cnrm + 3 * lane + k] : g[4 + k]; }
+          const int pw_ = __float_as_int(W.pair_rec[4 * (size_t)(cw_ & 2047)].x);
+          const int g1 = pw_ & 255, g2 = (pw_ >> 8) & 255;
+          float t1[3], t2[3];
+          make_frame(cn, t1, t2);
+          if (((pw_ >> 16) & 15) == 2) {   // plane - capsule: first tangent along the capsule axis, as in the row stage (its gax table is gone by now)
+            float R[9];
+            geom_world_mat(W, Y, E, g2, R);
+            const float ax[3] = {R[2], R[5], R[8]};
+            float t = dot3(ax, cn), y[3] = {ax[0] - t * cn[0], ax[1] - t * cn[1], ax[2] - t * cn[2]};
+            float yn = norm3(y);
+            if (yn >= 0.5f) {
+              float inv = 1.0f / yn;
+              t1[0] = y[0] * inv; t1[1] = y[1] * inv; t1[2] = y[2] * inv;
+              cross3(t2, cn, t1);
+            }
+          }
+          const float f0 = fmaxf(0.f, -cD * cjar[0]), f1 = fmaxf(0.f, -cD * cjar[1]), f2 = fmaxf(0.f, -cD * cjar[2]), f3 = fmaxf(0.f, -cD * cjar[3]);
+          fn = f0 + f1 + f2 + f3;
+          const float a1 = cmu * (f0 - f1), a2 = cmu * (f2 - f3);
+          // the force acts on geom 2's body and its opposite on geom 1's: what reaches the model from outside is the force of a contact whose
+          // other geom is world-fixed; a contact between two moving geoms is internal and adds nothing
+          const float sg = __float_as_int(W.cg_rec[4 * g1].x) < 0 ? 1.f : (__float_as_int(W.cg_rec[4 * g2].x) < 0 ? -1.f : 0.f);
+#pragma unroll
+          for (int k = 0; k < 3; k++) Fw[k] = sg * (fn * cn[k] + a1 * t1[k] + a2 * t2[k]);
+          cb1 = W.cg_body[g1]; cb2 = W.cg_body[g2];
+        }
+        float* const srow = Bt.sens + (size_t)env * nts;
+        float* const crow = Bt.cfrc + (size_t)env * 3 * (nts + 1);
+        // an env reset in this launch reads zeros like mj_resetData: a bad state seen by this wave, or (scheduler) by the wave of an earlier
+        // substep, which left a negative mark in the env's first sensor word
+        bool wiped = !alive;
+        if (SCHED && s0 > 0) wiped = wiped || ldstate<SCHED>(srow) < 0.f;
+        const float keep = wiped ? 0.f : 1.f;
+        for (int s = 0; s < nts; s++) {
+          const gpf T = W.touch + TOUCHR * s;
+          const int sl = __float_as_int(T[0]), sty = __float_as_int(T[13]), sb = __float_as_int(T[17]);
+          const float sgn = cb2 == sb ? -1.f : 1.f;
+          float x[3] = {cp[0], cp[1], cp[2]}, r[3] = {sgn * cn[0], sgn * cn[1], sgn * cn[2]};
+          if (sl >= 0) {   // into the link frame of the last position stage (wave-uniform branch)
+            const float* P = E + Y.lpos + 3 * sl;
+            const float* R = E + Y.lmat + 9 * sl;
+            x[0] -= P[0]; x[1] -= P[1]; x[2] -= P[2];
+            matTvec(x, R, x);
+            matTvec(r, R, r);
+          }
+          const float sm[9] = {T[4], T[5], T[6], T[7], T[8], T[9], T[10], T[11], T[12]}, sz[3] = {T[14], T[15], T[16]};
+          x[0] -= T[1]; x[1] -= T[2]; x[2] -= T[3];
+          float p[3], d[3];
+          matTvec(p, sm, x);
+          matTvec(d, sm, r);
+          bool meets;
+          if (sty == GEOM_SPHERE) {
+            const float bq = dot3(p, d), det = bq * bq - (dot3(p, p) - sz[0] * sz[0]);
+            meets = det >= 0.f && sqrtf(fmaxf(det, 0.f)) - bq >= 0.f;
+          } else {   // box: slab test
+            float tmin = 0.f, tmax = 3.0e38f;
+            meets = true;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+              if (fabsf(d[k]) < 1e-12f) meets = meets && fabsf(p[k]) <= sz[k];
+              else {
+                const float inv = 1.0f / d[k], ta = (-sz[k] - p[k]) * inv, tb = (sz[k] - p[k]) * inv;
+                tmin = fmaxf(tmin, fminf(ta, tb)); tmax = fminf(tmax, fmaxf(ta, tb));
+              }
+            }
+            meets = meets && tmax >= tmin;
+          }
+          const bool counts = fn > 0.f && (cb1 == sb || cb2 == sb) && meets;
+          const float S = wave_sum(counts ? fn : 0.f), Sx = wave_sum(counts ? Fw[0] : 0.f), Sy = wave_sum(counts ? Fw[1] : 0.f), Sz = wave_sum(counts ? Fw[2] : 0.f);
+          if (lane == 0) { srow[s] = keep * S; crow[3 * s] = keep * Sx; crow[3 * s + 1] = keep * Sy; crow[3 * s + 2] = keep * Sz; }
+        }
+        const float Gx = wave_sum(Fw[0]), Gy = wave_sum(Fw[1]), Gz = wave_sum(Fw[2]);
+        if (lane == 0) { crow[3 * nts] = keep * Gx; crow[3 * nts + 1] = keep * Gy; crow[3 * nts + 2] = keep * Gz; }
+      }
+    }
     if constexpr (RK4) {
       if (alive) {
         const float Bw = (rk_stage == 0 || rk_stage == 3) ? (1.f / 6.f) : (1.f / 3.f), a = rk_stage < 2 ? 0.5f : 1.f;
@@ -2524,6 +2624,9 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
     if (lane_id < nv) { E[Y.qvel + lane_id] = 0; warm_row[lane_id] = 0.f; }
     for (int i = lane_id; i < nu; i += 64) { E[Y.act + i] = 0; E[Y.ctrl + i] = 0; }
     time = 0;
+    if constexpr (SCHED && FULL && !TRK && !RK4) {   // (the wave of the last substep reads the mark and writes zeros)
+      if (Bt.sens && s1 < nsub && lane_id == 0) Bt.sens[(size_t)env * Bt.ntouch] = -1.f;
+    }
   }
   bool track_reset = false;
   if constexpr (TRK) {

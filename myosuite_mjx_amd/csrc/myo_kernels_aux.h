@@ -153,6 +153,10 @@ __device__ __forceinline__ bool reset_body(const DevBatch& Bt, const TaskDev& T,
     } else if (T.fatigue_mode == 2 && T.fatigue_vec) { MF = T.fatigue_vec[i]; MR = 1.f - MF; }   // fatigue_reset_vec (:124-130)
     Bt.fatigue[(size_t)e * 3 * nu + i] = MA; Bt.fatigue[(size_t)e * 3 * nu + nu + i] = MR; Bt.fatigue[(size_t)e * 3 * nu + 2 * nu + i] = MF;
   }
+  if (Bt.sens) {   // sensor rows of a fresh episode read zero, like mj_resetData
+    for (int i = lane; i < Bt.ntouch; i += 64) Bt.sens[(size_t)e * Bt.ntouch + i] = 0.f;
+    for (int i = lane; i < 3 * (Bt.ntouch + 1); i += 64) Bt.cfrc[(size_t)e * 3 * (Bt.ntouch + 1) + i] = 0.f;
+  }
   for (int i = lane; i < T.ntarget; i += 64) {
     float lo = T.target_lo[i], hi = T.target_hi[i];
     float t = T.target_generate ? lo + (hi - lo) * u01(seed, ge * 4096 + 2048 + i, 2) : lo;

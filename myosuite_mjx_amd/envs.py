@@ -255,7 +255,7 @@ class BatchedMyoEnv:
     DIE_KWARGS = ("goal_pos", "goal_rot", "pos_th", "rot_th", "drop_th")
     DIE_REFUSED = ("obj_size_change", "obj_mass_range", "obj_friction_change")
 
-    def __init__(self, env_id, num_envs=1, device=0, seed=0, env_offset=0, autoreset=True, as_torch=True, **env_kwargs):
+    def __init__(self, env_id, num_envs=1, device=0, seed=0, env_offset=0, autoreset=True, as_torch=True, sensors=False, **env_kwargs):
         if env_id in UNSUPPORTED:
             raise NotImplementedError(f"{env_id}: {UNSUPPORTED[env_id]}")
         if env_id not in REGISTRY:
@@ -292,6 +292,9 @@ class BatchedMyoEnv:
         self.model = capi.HipModel(self.mjmodel.blob(), device)       # raises if there is no GPU / no library
         self.batch = capi.HipBatch(self.model, self.num_envs)
         self.batch.set_env_offset(env_offset)
+        self.sensors = bool(sensors)
+        if self.sensors:       # touch sensors / contact forces of the leg models; nothing is allocated without it
+            _enable_sensors(env_id, self.batch)
         m = self.mjmodel
         self.frame_skip = spec["frame_skip"]
         self.dt = m.timestep * self.frame_skip                        # env_base.py:616-617
@@ -586,6 +589,31 @@ class BatchedMyoEnv:
         else:
             self.batch.write(capi.F_TARGET, np.broadcast_to(np.asarray(value, np.float32), (self.num_envs, 3)))
 
+    # -- touch sensors and contact forces (make(..., sensors=True)) ---------------------------------------
+    def _need_sensors(self):
+        if not self.sensors:
+            raise AttributeError(f"{self.id}: made without sensors=True")
+
+    @property
+    def sensor_names(self):
+        """Names of the model's sensors, in the column order of `sensordata`."""
+        return list(self.mjmodel.names.get("sensor", []))
+
+    @property
+    def sensordata(self):
+        """[num_envs, nsensor] touch sensors after the last step (`sim.data.sensordata` of every env): a torch view of the library's
+        buffer (no copy).  The forces of the last substep's solve; zeros for an env that was just reset.  With as_torch=False: a numpy copy."""
+        self._need_sensors()
+        return self.view(capi.F_SENSORDATA)
+
+    @property
+    def contact_force(self):
+        """[num_envs, nsensor + 1, 3] world force of the contacts each touch sensor counts, and in the last row the force of all contacts
+        against world-fixed geoms (the ground reaction force).  A torch view (no copy); with as_torch=False a numpy copy."""
+        self._need_sensors()
+        v = self.view(capi.F_CFRC)
+        return v.view(self.num_envs, -1, 3) if self.as_torch else v.reshape(self.num_envs, -1, 3)
+
     # -- zero-copy views ---------------------------------------------------------------------------------
     def view(self, field):
         """torch view (as_torch) or numpy copy of a per-env field."""
@@ -657,7 +685,15 @@ class BatchedMyoEnv:
         return self.batch.status()
 
 
-def _make_track(env_id, num_envs, reference=None, flavour="mjx", **kw):
+def _enable_sensors(env_id, batch):
+    """sensors=True: turn the readout on, or say why this id's model cannot provide it (the library's own message)."""
+    try:
+        batch.enable_sensors()
+    except capi.MyoError as e:
+        raise NotImplementedError(f"{env_id}: sensors=True is not available: {e}") from None
+
+
+def _make_track(env_id, num_envs, reference=None, flavour="mjx", sensors=False, **kw):
     from .track import ClassicTrackEnv, TrackEnv
     if flavour not in ("mjx", "classic"):
         raise ValueError(f"{env_id}: flavour must be 'mjx' (mjx/myodm_v0.py, the default) or 'classic' (envs/myo/myodm/myodm_v0.py), got {flavour!r}")
@@ -668,6 +704,8 @@ def _make_track(env_id, num_envs, reference=None, flavour="mjx", **kw):
     else:
         env = TrackEnv(num_envs=num_envs, object_name=REGISTRY[env_id]["object"], reference=reference, gym_api=True, **kw)
     env.id = env_id
+    if sensors:
+        _enable_sensors(env_id, env.batch)
     return env
 
 

@@ -718,6 +718,25 @@ def lower(cm):
         raise NotImplementedError("HIP path: plane against a moving sphere outside the TrackEnv model class")
     A["hip_cg_rbound"] = m.geom_rbound[cgs] if cgs else np.zeros(0)
     A["hip_cg_geom"] = np.array(cgs, np.int32)
+    # touch sensors: one record each = [link of the site (-1: world-fixed), site position (3) and rotation (9, row-major) in that link's
+    # frame, site type, half sizes (3), body id of the site]
+    touch = []
+    sens_type = A.get("sensor_type", np.zeros(0, np.int32))
+    for i in range(len(sens_type)):
+        if int(sens_type[i]) != 0:
+            continue
+        s = int(A["sensor_objid"][i])
+        b = int(m.site_bodyid[s])
+        name = cm.names.get("sensor", [str(i)] * (i + 1))[i]
+        if int(A["site_type"][s]) not in (GEOM_BOX, GEOM_SPHERE):
+            raise NotImplementedError(f"HIP path: touch sensor {name!r} sits on a site that is neither a box nor a sphere")
+        Rs = quat2mat(A["site_quat"][s])
+        Rl = quat2mat(xquat0[b]) @ Rs if (b == 0 or head[b] == 0) else Rrel[b] @ Rs
+        touch.append([float(site_link[s]), *site_lpos[s], *Rl.ravel(), float(A["site_type"][s]), *A["site_size"][s], float(b)])
+    if touch:
+        A["hip_touch"] = np.array(touch, float)
+        # body of every collision geom: touch sensors match contacts by body (mj_computeSensor), not by welded link
+        A["hip_cg_body"] = np.array([m.geom_bodyid[g] for g in cgs], np.int32)
     # pair order = candidate order = lane order of the narrow phase, whose 64-lane rounds each cost their slowest lane: the pairs that go
     # through MPR (generic convex, height-field prisms) come first, so that an env with more than 64 candidates (the usual case for MyoHand:
     # ~87 per substep, ~20 of them MPR) runs ONE round with MPR lanes and then rounds of analytic pairs only, instead of paying the MPR

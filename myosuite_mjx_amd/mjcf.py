@@ -264,6 +264,7 @@ class _Compiler:
         self.joints = []
         self.geoms = []
         self.sites = []
+        self.sensors = []
         self.tendons = []
         self.wraps = []
         self.actuators = []
@@ -399,6 +400,19 @@ class _Compiler:
             return mat2quat(np.stack([x, y, np.cross(x, y)], 1))
         return np.array([1.0, 0, 0, 0])
 
+    def _site_shape(self, at):
+        """Site type (geom type ids) and half sizes: a sphere of 0.005 by default; `size` overrides its leading entries."""
+        size = np.full(3, 0.005)
+        v = _floats(at["size"]) if "size" in at else np.zeros(0)
+        size[:min(3, v.size)] = v[:3]
+        return dict(type=GEOM_TYPES[at.get("type", "sphere")], size=size)
+
+    def _do_sensor(self, e):
+        # touch sensors only (name, site); every other sensor kind is skipped
+        for ch in e:
+            if ch.tag == "touch":
+                self.sensors.append(dict(name=ch.attrib.get("name", f"sensor{len(self.sensors)}"), site=ch.attrib["site"]))
+
     def _do_asset(self, e):
         for ch in e:
             if ch.tag == "hfield":
@@ -496,7 +510,7 @@ class _Compiler:
             elif t == "site":
                 at = self._attrs(ch, "site", childclass)
                 self.sites.append(dict(name=at.get("name", f"site{len(self.sites)}"), body=bid,
-                                       pos=_floats(at.get("pos", "0 0 0"), 3), quat=self._orientation(at)))
+                                       pos=_floats(at.get("pos", "0 0 0"), 3), quat=self._orientation(at), **self._site_shape(at)))
             elif t == "body":
                 self._do_body(ch, bid, childclass)
             elif t in ("camera", "light", "include"):
@@ -672,8 +686,10 @@ class _Compiler:
             elif e.tag == "equality":
                 for q in e:
                     self.equalities.append((q.tag, {kk: vv for kk, vv in q.attrib.items() if kk != "__dir"}))
+            elif e.tag == "sensor":
+                self._do_sensor(e)
             elif e.tag in ("compiler", "option", "default", "asset", "worldbody", "size", "visual", "statistic",
-                           "sensor", "custom", "extension"):
+                           "custom", "extension"):
                 pass
             else:
                 raise NotImplementedError(f"unsupported section <{e.tag}>")
@@ -688,7 +704,7 @@ class _Compiler:
             elif t == "site":
                 at = self._attrs(ch, "site", None)
                 self.sites.append(dict(name=at.get("name", f"site{len(self.sites)}"), body=0,
-                                       pos=_floats(at.get("pos", "0 0 0"), 3), quat=self._orientation(at)))
+                                       pos=_floats(at.get("pos", "0 0 0"), 3), quat=self._orientation(at), **self._site_shape(at)))
             elif t == "body":
                 self._do_body(ch, 0, None)
             elif t in ("camera", "light"):
@@ -943,6 +959,16 @@ class _Compiler:
         # sites
         A["site_bodyid"] = np.array([s["body"] for s in self.sites], np.int32)
         A["site_pos"] = np.stack([s["pos"] for s in self.sites]) if self.sites else np.zeros((0, 3))
+        if self.sensors:
+            # touch sensors (mjSENS_TOUCH = 0): one scalar each, attached to a site whose shape is the sensor's volume.  Models without touch
+            # sensors get none of these arrays (their compiled blobs stay as they were)
+            A["site_quat"] = np.stack([s["quat"] for s in self.sites])
+            A["site_type"] = np.array([s["type"] for s in self.sites], np.int32)
+            A["site_size"] = np.stack([s["size"] for s in self.sites])
+            names["sensor"] = [s["name"] for s in self.sensors]
+            A["sensor_type"] = np.zeros(len(self.sensors), np.int32)
+            A["sensor_objid"] = np.array([names["site"].index(s["site"]) for s in self.sensors], np.int32)
+            A["sensor_adr"] = np.arange(len(self.sensors), dtype=np.int32)
         # tendons + wraps
         nt = len(self.tendons)
         wtype, wobj, wprm = [], [], []

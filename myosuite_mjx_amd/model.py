@@ -243,6 +243,26 @@ def asset_stem(name) -> str:
     raise FileNotFoundError(f"compiled model {name!r} not found under {ASSET_DIR} or {GOLDEN_DIR}; run tools/compile_models.py")
 
 
+# arrays a model with touch sensors carries on top of the older ones (mjcf.py / lowering.py).  For the committed models they live in a
+# side-car blob of their own, tests/golden/sensors/<name>.myob.gz (+ a JSON with the sensor names): the model's own blob stays what it was
+SENSOR_ARRAYS = ("site_quat", "site_type", "site_size", "sensor_type", "sensor_objid", "sensor_adr", "hip_cg_body", "hip_touch")
+SENSOR_DIR = os.path.join(GOLDEN_DIR, "sensors")
+
+
+def split_sensor_arrays(m: Model):
+    """(model without the sensor arrays, side-car Model holding only them or None): how tools/compile_models.py stores a compiled model."""
+    if "hip_touch" not in m.arrays:
+        return m, None
+    base = Model({k: v for k, v in m.arrays.items() if k not in SENSOR_ARRAYS}, {k: v for k, v in m.names.items() if k != "sensor"}, m.source)
+    side = Model({k: m.arrays[k] for k in SENSOR_ARRAYS}, {"sensor": list(m.names.get("sensor", []))}, m.source)
+    return base, side
+
+
 def load_asset(name) -> Model:
-    """Load a committed compiled model by stem (e.g. 'myohand_pose')."""
-    return Model.load(asset_stem(name))
+    """Load a committed compiled model by stem (e.g. 'myohand_pose'), with its sensor side-car merged in where it has one."""
+    m = Model.load(asset_stem(name))
+    side = os.path.join(SENSOR_DIR, name)
+    if os.path.exists(side + ".myob.gz") and "hip_touch" not in m.arrays:
+        s = Model.load(side)
+        m = Model({**m.arrays, **s.arrays}, {**m.names, **s.names}, m.source)      # (the blob is packed again from the merged arrays)
+    return m

@@ -53,10 +53,29 @@ def set_(d: capi.HipBatch, field: str, value):
     d.write(_FIELDS[field], value)
 
 
+class _SensorView:
+    """`sim.data.sensor(name)`: `.data` is the sensor's block of `sensordata` as [dim, B], so that the reference's `.data[0]` reads the
+    (scalar) touch value of every env."""
+
+    def __init__(self, data):
+        self.data = data
+
+
+def _sensor(self, name):
+    if self.sensordata is None:
+        raise ValueError("sim.data.sensor: the scene was made without sensors=True")
+    i = self._mj.sensor_name2id(name) if isinstance(name, str) else int(name)
+    adr = int(self._mj.sensor_adr[i])
+    return _SensorView(self.sensordata[:, adr:adr + 1].T)
+
+
 class _HostData:
     """Host mirrors of the per-env state, [B, n] float32 (the reference's `sim.data.*` NumPy views, batched)."""
+    sensor = _sensor
 
-    def __init__(self, B, m):
+    def __init__(self, B, m, sensors=False):
+        self._mj = m
+        self.sensordata = np.zeros((B, len(m.names.get("sensor", []))), np.float32) if sensors else None
         self.qpos = np.tile(np.asarray(m.qpos0, np.float32), (B, 1))
         self.qvel = np.zeros((B, m.nv), np.float32)
         self.act = np.zeros((B, m.na), np.float32)
@@ -83,7 +102,9 @@ class _DeviceData:
     the simulation state, like the reference's NumPy views of MjData -- no upload or download around `advance`.  NumPy values may be
     assigned into them (they are uploaded); reading gives torch tensors on the device."""
 
-    def __init__(self, batch, B, device):
+    sensor = _sensor
+
+    def __init__(self, batch, B, device, mj=None, sensors=False):
         import torch
         from .envs import _DevArray
         self._keep = batch
@@ -96,6 +117,8 @@ class _DeviceData:
         self.qpos, self.qvel, self.act, self.ctrl = view(capi.F_QPOS), view(capi.F_QVEL), view(capi.F_ACT), view(capi.F_CTRL)
         self.time, self.qacc, self.qacc_warmstart = view(capi.F_TIME), view(capi.F_QACC), view(capi.F_WARMSTART)
         self.actuator_length, self.actuator_force = view(capi.F_TENLEN), view(capi.F_ACTFORCE)
+        self._mj = mj
+        self.sensordata = view(capi.F_SENSORDATA) if sensors else None      # [B, nsensor] touch sensors (HipSimScene(..., sensors=True))
 
 
 class _NullRenderer:
@@ -122,13 +145,17 @@ class HipSimScene:
     disable_option(_context), model.*_name2id -- is provided with its batched / MYOB meaning, see each method.
     """
 
-    def __init__(self, model_handle, num_envs=1, device=0, as_torch=True):
+    def __init__(self, model_handle, num_envs=1, device=0, as_torch=True, sensors=False):
         self.num_envs = int(num_envs)
         self.device = device
         self.as_torch = as_torch
         self.sim = self._load_simulation(model_handle, device)
         self.model = self.sim.mj
-        self.data = _DeviceData(self._batch, self.num_envs, device) if as_torch else _HostData(self.num_envs, self.model)
+        self.sensors = bool(sensors)
+        if self.sensors:       # `data.sensordata` / `data.sensor(name).data`: touch sensors of the leg models (raises for models without them)
+            self._batch.enable_sensors()
+        self.data = (_DeviceData(self._batch, self.num_envs, device, self.model, self.sensors) if as_torch
+                     else _HostData(self.num_envs, self.model, self.sensors))
         self.lib = self.get_mjlib()
         self.renderer = self._create_renderer(self.sim)
         self.init_qpos = np.asarray(self.model.qpos0, np.float64).copy()
@@ -215,6 +242,8 @@ class HipSimScene:
         self.data.qpos[:] = b.read(capi.F_QPOS); self.data.qvel[:] = b.read(capi.F_QVEL)
         self.data.act[:] = b.read(capi.F_ACT); self.data.time[:] = b.read(capi.F_TIME)
         self.data.qacc[:] = b.read(capi.F_QACC)
+        if self.sensors:
+            self.data.sensordata[:] = b.read(capi.F_SENSORDATA)
 
     def _stream(self):
         if self.as_torch:
@@ -261,6 +290,8 @@ class HipSimScene:
             self.data.qpos[:] = torch.as_tensor(np.asarray(self.model.qpos0, np.float32), device=self.data.qpos.device)
             for t in (self.data.qvel, self.data.act, self.data.ctrl, self.data.time, self.data.qacc_warmstart):
                 t.zero_()
+            if self.sensors:
+                self.data.sensordata.zero_()
             return
         self.data.qpos[:] = np.asarray(self.model.qpos0, np.float32)
         self.data.qvel[:] = 0; self.data.act[:] = 0; self.data.ctrl[:] = 0; self.data.time[:] = 0

@@ -50,6 +50,10 @@ if __name__ == "__main__":
             m = M.from_mjcf(os.path.join(REF, rel[0]), replace=rel[1], convex_meshes=True)
         else:
             m = M.from_mjcf(os.path.join(REF, rel[0]), terrain=True) if isinstance(rel, tuple) else M.from_mjcf(os.path.join(REF, rel))
+        m, side = M.split_sensor_arrays(m)      # touch-sensor arrays go to a side-car of their own: the model's blob keeps its older arrays only
+        if side is not None:
+            os.makedirs(M.SENSOR_DIR, exist_ok=True)
+            side.save(os.path.join(M.SENSOR_DIR, stem), compress=True)
         m.save(os.path.join(M.ASSET_DIR, stem), compress=isinstance(rel, tuple) and len(rel) == 3)
         print(stem, dict(nq=m.nq, nv=m.nv, nu=m.nu, nbody=m.nbody, ntendon=m.ntendon, bytes=len(m.blob())))
     for stem, rel in GOLDEN.items():

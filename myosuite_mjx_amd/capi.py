@@ -19,6 +19,8 @@ SRC_PATH = os.path.join(_HERE, "csrc", "myo_hip.hip")
 F_BODYQUAT, F_BODYQUAT_RANGE = 28, 29      # per-env orientation of one world-welded body (TaskConfig.quat_body selects it)
 F_SENSORDATA, F_CFRC = 30, 31              # touch sensors [B, nsensor] and contact forces [B, (nsensor + 1) * 3] (HipBatch.enable_sensors)
 INT_FIELDS = (F_FLAGS, F_DIAG, F_ELAPSED)
+# width of the per-env override fields as (per body, constant): known without asking for their device pointer, which would start the override
+_OVERRIDE_WIDTH = {F_BODYMASS: (1, 0), F_BODYMASS_RANGE: (2, 0), F_BODYPOS: (0, 3), F_BODYPOS_RANGE: (0, 6), F_BODYQUAT: (0, 4), F_BODYQUAT_RANGE: (0, 6)}
 BENCH_OBS, BENCH_FRESH_ACTIONS, BENCH_AUTORESET = 1, 2, 4
 ACTMAP_NONE, ACTMAP_MUSCLE_SIGMOID, ACTMAP_SIGMOID_FATIGUE, ACTMAP_SIGMOID_REAFFERENTATION, ACTMAP_CTRLRANGE = 0, 1, 2, 3, 4
 TASK_NONE, TASK_POSE, TASK_REACH = 0, 1, 2
@@ -205,6 +207,15 @@ def _chk(rc):
         raise MyoError(f"libmyo_hip error {rc}: {lib().myo_last_error().decode()}")
 
 
+def _f32(a):
+    return np.ascontiguousarray(a, np.float32) if a is not None else None
+
+
+def _ptr(a, ctype=C.c_float):
+    """Pointer to a contiguous array's data (None stays NULL); the caller keeps the array alive across the library call."""
+    return a.ctypes.data_as(C.POINTER(ctype)) if a is not None else None
+
+
 class HipModel:
     """Device-resident model (mjx.put_model counterpart, mjx/play.py:10)."""
 
@@ -262,18 +273,14 @@ class HipBatch:
             c.tip_site[i] = int(s)
         c.pose_thd, c.far_th, c.near_th = pose_thd, far_th, near_th
         c.w_pose, c.w_bonus, c.w_act_reg, c.w_penalty, c.w_reach = w_pose, w_bonus, w_act_reg, w_penalty, w_reach
-        iq = np.ascontiguousarray(init_qpos, np.float32) if init_qpos is not None else None
-        fp = lambda a: np.ascontiguousarray(a, np.float32)
-        extra = [fp(reset_noise[0]), fp(reset_noise[1]), fp(reset_clip[0]), fp(reset_clip[1])] if reset_noise is not None else [None] * 4
-        iv = fp(init_qvel) if init_qvel is not None else None
+        iq, iv = _f32(init_qpos), _f32(init_qvel)
+        extra = [_f32(a) for a in (*reset_noise, *reset_clip)] if reset_noise is not None else [None] * 4
         self._keep = (lo, hi, iq, extra, iv)
-        ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_float)) if a is not None else None
-        c.reset_noise_lo, c.reset_noise_hi, c.reset_clip_lo, c.reset_clip_hi = [ptr(a) for a in extra]
-        c.init_qvel = ptr(iv)
+        c.reset_noise_lo, c.reset_noise_hi, c.reset_clip_lo, c.reset_clip_hi = [_ptr(a) for a in extra]
+        c.init_qvel = _ptr(iv)
         c.tip_lpos = (C.c_float * 3)(*[float(x) for x in tip_lpos])
-        c.target_lo = lo.ctypes.data_as(C.POINTER(C.c_float)) if lo.size else None
-        c.target_hi = hi.ctypes.data_as(C.POINTER(C.c_float)) if hi.size else None
-        c.init_qpos = iq.ctypes.data_as(C.POINTER(C.c_float)) if iq is not None else None
+        c.target_lo, c.target_hi = _ptr(lo if lo.size else None), _ptr(hi if hi.size else None)
+        c.init_qpos = _ptr(iq)
         _chk(lib().myo_batch_configure(self.h, C.byref(c)))
 
     def configure_walk(self, *, frame_skip, hip_period, min_height, max_rot, target_x_vel, target_y_vel, target_rot, bodies, qadr_hip_flexion,
@@ -289,16 +296,10 @@ class HipBatch:
         c.qadr_hip_flexion_l, c.qadr_hip_flexion_r = [int(x) for x in qadr_hip_flexion]
         c.qadr_joint_angle = (C.c_int * 4)(*[int(x) for x in qadr_joint_angle])
         c.w_vel_reward, c.w_done, c.w_cyclic_hip, c.w_ref_rot, c.w_joint_angle_rew = [float(x) for x in weights]
-        iq = np.ascontiguousarray(init_qpos, np.float32)
-        iv = np.ascontiguousarray(init_qvel, np.float32) if init_qvel is not None else None
-        c.init_qpos = iq.ctypes.data_as(C.POINTER(C.c_float))
-        c.init_qvel = iv.ctypes.data_as(C.POINTER(C.c_float)) if iv is not None else None
+        iq, iv, iq2, iv2 = _f32(init_qpos), _f32(init_qvel), _f32(init_qpos_alt), _f32(init_qvel_alt)      # (alive until the call has returned)
+        c.init_qpos, c.init_qvel, c.init_qpos_alt, c.init_qvel_alt = _ptr(iq), _ptr(iv), _ptr(iq2), _ptr(iv2)
         c.knee_height, c.terrain = float(knee_height), int(terrain)
         c.terrain_scalar_lo, c.terrain_scalar_hi = float(terrain_scalar[0]), float(terrain_scalar[1])
-        iq2 = np.ascontiguousarray(init_qpos_alt, np.float32) if init_qpos_alt is not None else None
-        iv2 = np.ascontiguousarray(init_qvel_alt, np.float32) if init_qvel_alt is not None else None
-        c.init_qpos_alt = iq2.ctypes.data_as(C.POINTER(C.c_float)) if iq2 is not None else None
-        c.init_qvel_alt = iv2.ctypes.data_as(C.POINTER(C.c_float)) if iv2 is not None else None
         c.reset_noise_std = float(reset_noise_std)
         _chk(lib().myo_batch_configure_walk(self.h, C.byref(c)))
 
@@ -310,23 +311,18 @@ class HipBatch:
         """MyoDM TrackEnv as a fused task of the step kernel (myo_track_config).  reference = dict(time [H], robot [Hr, nr], robot_vel | None,
         object [Ho, no]) in float64 (the reference's own arrays); ref_type 0 FIXED / 1 RANDOM / 2 TRACK; weights = (pose, object, bonus, penalty);
         flavour 0 MJX (fused into the step kernel), 1 classic gym TrackEnv (its own observation / reward kernel, myo_obs)."""
-        f64 = lambda a: np.ascontiguousarray(a, np.float64)
-        pd = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-        pf = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
-        T, Rb, Ob = f64(reference["time"]), f64(reference["robot"]), f64(reference["object"])
-        Rv = f64(reference["robot_vel"]) if reference.get("robot_vel") is not None else None
+        f64 = lambda a: np.ascontiguousarray(a, np.float64) if a is not None else None
+        T, Rb, Rv, Ob = (f64(reference.get(k)) for k in ("time", "robot", "robot_vel", "object"))
         c = TrackConfig()
         c.n_frames, c.ref_type = int(n_frames), int(ref_type)
         c.horizon, c.robot_horizon, c.object_horizon = max(Rb.shape[0], Ob.shape[0]), Rb.shape[0], Ob.shape[0]
         assert T.shape[0] >= c.horizon or ref_type != 2, "reference time axis shorter than the motion"
         c.robot_dim, c.object_dim = Rb.shape[1], Ob.shape[1]
         c.motion_extrapolation, c.interpolation_linear, c.motion_start_time = int(motion_extrapolation), int(interpolation_linear), float(motion_start_time)
-        c.ref_time, c.ref_robot, c.ref_object = pd(T), pd(Rb), pd(Ob)
-        c.ref_robot_vel = pd(Rv) if Rv is not None else None
-        iq = np.ascontiguousarray(init_qpos, np.float32)
+        c.ref_time, c.ref_robot, c.ref_robot_vel, c.ref_object = (_ptr(a, C.c_double) for a in (T, Rb, Rv, Ob))
         cr = np.asarray(ctrl_range, np.float64)
-        lo, hi = np.ascontiguousarray(cr[:, 0], np.float32), np.ascontiguousarray(cr[:, 1], np.float32)
-        c.init_qpos, c.ctrl_lo, c.ctrl_hi = pf(iq), pf(lo), pf(hi)
+        iq, lo, hi = _f32(init_qpos), _f32(cr[:, 0]), _f32(cr[:, 1])
+        c.init_qpos, c.ctrl_lo, c.ctrl_hi = _ptr(iq), _ptr(lo), _ptr(hi)
         c.object_link, c.wrist_link = int(object_link), int(wrist_link)
         c.object_ipos = (C.c_float * 3)(*[float(x) for x in object_ipos])
         c.object_imat = (C.c_float * 9)(*[float(x) for x in np.asarray(object_imat).ravel()])
@@ -364,27 +360,24 @@ class HipBatch:
     def obs_reset_only(self, stream=None):
         _chk(lib().myo_obs_reset_only(self.h, stream))
 
+    def _set_range(self, field, width, lo, hi):
+        lo, hi = (np.broadcast_to(np.asarray(a, np.float32), (self.B, width)) for a in (lo, hi))
+        self.write(field, np.concatenate([lo, hi], axis=1))
+
     def set_body_mass_range(self, lo, hi):
         """Per-env body-mass ranges ([B, nbody] or [nbody] each): every reset of an env draws mass ~ U(lo, hi) for the bodies with
         hi > lo (MYO_F_BODYMASS_RANGE); starts the per-env body-mass override."""
-        nb = self.model.dims.nbody
-        lo = np.broadcast_to(np.asarray(lo, np.float32), (self.B, nb))
-        hi = np.broadcast_to(np.asarray(hi, np.float32), (self.B, nb))
-        self.write(F_BODYMASS_RANGE, np.concatenate([lo, hi], axis=1))
+        self._set_range(F_BODYMASS_RANGE, self.model.dims.nbody, lo, hi)
 
     def set_body_pos_range(self, lo, hi):
         """Per-env offset ranges of the root body of MYO_F_BODYPOS ([B, 3] or [3] each): every reset of an env draws offset ~ U(lo, hi) for
         the components with hi > lo (MYO_F_BODYPOS_RANGE); starts the per-env offset."""
-        lo = np.broadcast_to(np.asarray(lo, np.float32), (self.B, 3))
-        hi = np.broadcast_to(np.asarray(hi, np.float32), (self.B, 3))
-        self.write(F_BODYPOS_RANGE, np.concatenate([lo, hi], axis=1))
+        self._set_range(F_BODYPOS_RANGE, 3, lo, hi)
 
     def set_body_quat_range(self, lo, hi):
         """Per-env Euler ranges of the selected body ([B, 3] or [3] each): every reset of an env sets body_quat = euler2quat(U(lo, hi))
         (MYO_F_BODYQUAT_RANGE); starts the per-env orientation."""
-        lo = np.broadcast_to(np.asarray(lo, np.float32), (self.B, 3))
-        hi = np.broadcast_to(np.asarray(hi, np.float32), (self.B, 3))
-        self.write(F_BODYQUAT_RANGE, np.concatenate([lo, hi], axis=1))
+        self._set_range(F_BODYQUAT_RANGE, 3, lo, hi)
 
     def field_ptr(self, field):
         p, pitch, width = C.c_void_p(), C.c_size_t(), C.c_size_t()
@@ -392,16 +385,8 @@ class HipBatch:
         return p.value, pitch.value, width.value
 
     def _width(self, field):
-        # the body-mass fields have a known width; asking for their device pointer would start the override
-        if field == F_BODYMASS:
-            return self.model.dims.nbody
-        if field == F_BODYMASS_RANGE:
-            return 2 * self.model.dims.nbody
-        if field in (F_BODYPOS, F_BODYPOS_RANGE):    # likewise for the per-env root-body offset
-            return 3 if field == F_BODYPOS else 6
-        if field in (F_BODYQUAT, F_BODYQUAT_RANGE):  # ... and the per-env body orientation
-            return 4 if field == F_BODYQUAT else 6
-        return self.field_ptr(field)[2]
+        per_body, fixed = _OVERRIDE_WIDTH.get(field, (0, 0))
+        return per_body * self.model.dims.nbody + fixed if per_body or fixed else self.field_ptr(field)[2]
 
     def read(self, field) -> np.ndarray:
         width = self._width(field)
@@ -461,6 +446,31 @@ class HipBatch:
     def bench_rollout_async(self, steps, nsub, seed=0, mode=BENCH_OBS | BENCH_FRESH_ACTIONS | BENCH_AUTORESET, max_episode_steps=100, stream=None):
         """Enqueues `steps` env steps on `stream` without waiting; `last_kernel_ms()` later collects the step-kernel time of all of them."""
         _chk(lib().myo_bench_rollout(self.h, steps, nsub, seed, mode, max_episode_steps, stream, None))
+
+
+class _DevArray:
+    """__cuda_array_interface__ holder so torch can view library-owned device memory without a copy."""
+
+    def __init__(self, ptr, shape, typestr, owner):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+        self._owner = owner
+
+
+class FieldViews:
+    """`view` / `_stream` of the env classes: the env has batch, num_envs, device, _views = {} and _torch (the module, or None for numpy I/O)."""
+
+    def view(self, field):
+        """torch view (zero copy, cached) of a per-env field; without torch a numpy copy."""
+        if self._torch is None:
+            return self.batch.read(field)
+        if field not in self._views:
+            ptr, pitch, width = self.batch.field_ptr(field)
+            arr = _DevArray(ptr, (self.num_envs, width), "<i4" if field in INT_FIELDS else "<f4", self.batch)
+            self._views[field] = self._torch.as_tensor(arr, device=f"cuda:{self.device}")
+        return self._views[field]
+
+    def _stream(self):
+        return self._torch.cuda.current_stream(self.device).cuda_stream if self._torch is not None else None
 
 
 def set_lanes(lanes):

@@ -15,8 +15,9 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import capi
+from . import capi, tasks, track
 from . import model as _model
+from .capi import _DevArray  # noqa: F401  (sim.py takes it from here)
 
 # ASL pose table (envs/myo/myobase/__init__.py:326-376): target joint vectors of myoHandPose{k}Fixed-v0;
 # the per-joint min/max over the ten rows is the target range of myoHandPoseRandom-v0 (:396-399)
@@ -225,15 +226,27 @@ class Box:
         return rng.uniform(self.low, self.high).astype(self.dtype)
 
 
-class _DevArray:
-    """__cuda_array_interface__ holder so torch can view library-owned device memory without a copy."""
+def _field_property(name, field, width, task=None, doc=None):
+    """Property of a per-env field [num_envs, width] (width None: one column per body): get = `view(field)`; set broadcasts one row or takes
+    [num_envs, width], into the torch view or (as_torch=False) through a host write.  `task`: the only task that has the field."""
+    def check(self):
+        if task is not None and self.spec["task"] != task:
+            raise AttributeError(f"{name}: {task} task only")
 
-    def __init__(self, ptr, shape, typestr, owner):
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
-        self._owner = owner
+    def fget(self):
+        check(self)
+        return self.view(field)
+
+    def fset(self, value):
+        check(self)
+        if self.as_torch:
+            self.view(field).copy_(self._torch.as_tensor(value, dtype=self._torch.float32).expand(self.num_envs, -1))
+        else:
+            self.batch.write(field, np.broadcast_to(np.asarray(value, np.float32), (self.num_envs, width or self.mjmodel.nbody)))
+    return property(fget, fset, doc=doc)
 
 
-class BatchedMyoEnv:
+class BatchedMyoEnv(capi.FieldViews):
     """`num_envs` copies of one MyoSuite task, stepped together on one MI355X.
 
     step(action[B, nu] in [-1, 1]) -> (obs[B, obs_dim] f32, reward[B], terminated[B] bool, truncated[B] bool, info)
@@ -241,19 +254,11 @@ class BatchedMyoEnv:
     are reset in place and the returned obs row is the first observation of the new episode.
     """
 
-    # env kwargs of the reference that gym.make forwards to the env class and that are honoured here (others raise)
-    ENV_KWARGS = ("reset_type", "fatigue_reset_random", "fatigue_reset_vec", "weight_bodyname", "weight_range", "target_jnt_range",
-                  "goal_th", "key_init_range", "task_choice", "goal_time_period", "goal_xrange", "goal_yrange", "drop_th", "proximity_th",
-                  "goal_pos", "goal_rot", "pos_th", "rot_th")
-    POSE_KWARGS = ("weight_bodyname", "weight_range", "target_jnt_range")   # PoseEnvV0 kwargs (pose_v0.py:56-75): pose tasks only
-    KEYTURN_KWARGS = ("goal_th", "key_init_range")                           # KeyTurnEnvV0._setup kwargs (key_turn_v0.py:54-61): key turn only
-    # BaodingEnvV1._setup kwargs (baoding_v1.py:54-69): baoding only; its per-env ball size / mass / friction kwargs are refused
-    BAODING_KWARGS = ("task_choice", "goal_time_period", "goal_xrange", "goal_yrange", "drop_th", "proximity_th")
-    BAODING_REFUSED = ("obj_size_range", "obj_mass_range", "obj_friction_change")
-    # ReorientEnvV0._setup kwargs (reorient_v0.py:45-62): die only (drop_th is shared with baoding); its per-env die size / mass / friction
-    # kwargs are refused
-    DIE_KWARGS = ("goal_pos", "goal_rot", "pos_th", "rot_th", "drop_th")
-    DIE_REFUSED = ("obj_size_change", "obj_mass_range", "obj_friction_change")
+    # env kwargs of the reference that gym.make forwards to the env class and that are honoured here (others raise): the task records' tables
+    ENV_KWARGS = tasks.ENV_KWARGS
+    POSE_KWARGS = tasks.TASKS["pose"].kwargs
+    KEYTURN_KWARGS = tasks.TASKS["keyturn"].kwargs
+    _target_jnt_range = staticmethod(tasks.target_jnt_range)
 
     def __init__(self, env_id, num_envs=1, device=0, seed=0, env_offset=0, autoreset=True, as_torch=True, sensors=False, **env_kwargs):
         if env_id in UNSUPPORTED:
@@ -262,197 +267,42 @@ class BatchedMyoEnv:
             raise KeyError(f"unknown env id {env_id!r}; known: {sorted(REGISTRY)}")
         self.id = env_id
         self.spec = spec = dict(REGISTRY[env_id])
-        for k, v in env_kwargs.items():
-            if k in self.BAODING_REFUSED and spec.get("task") == "baoding" and v is not None:
-                raise NotImplementedError(f"{env_id}: {k} re-draws the balls' size, mass or friction per episode; the TrackEnv-class step "
-                                          "kernel has no per-env ball size, mass or friction")
-            if k in self.BAODING_REFUSED and spec.get("task") == "baoding":
-                continue
-            if k in self.DIE_REFUSED and spec.get("task") == "die":
-                if v is not None:
-                    raise NotImplementedError(f"{env_id}: {k} re-draws the die's size, mass or friction per episode; the TrackEnv-class step "
-                                              "kernel has no per-env die size, mass or friction")
-                continue
-            task_kw = [t for t, names in (("baoding", self.BAODING_KWARGS), ("die", self.DIE_KWARGS)) if k in names]
-            if k not in self.ENV_KWARGS or (k in self.POSE_KWARGS and spec.get("task") != "pose") or (k in self.KEYTURN_KWARGS and spec.get("task") != "keyturn") or (
-                    task_kw and spec.get("task") not in task_kw):
-                raise TypeError(f"{env_id}: unsupported env kwarg {k!r} (supported: {self.ENV_KWARGS}; {self.POSE_KWARGS} for pose tasks only, "
-                                f"{self.KEYTURN_KWARGS} for the key-turn task only, {self.BAODING_KWARGS} for the baoding task only, "
-                                f"{self.DIE_KWARGS} for the die task only)")
-            spec[k] = v
-        self.num_envs = int(num_envs)
-        self.device = device
-        self.seed = int(seed)
-        self.autoreset = autoreset
-        self.as_torch = as_torch
-        self.mjmodel = _model.load_asset(spec["model"])
+        tasks.filter_kwargs(env_id, spec, env_kwargs)
+        self.num_envs, self.device, self.seed, self.autoreset, self.as_torch = int(num_envs), device, int(seed), autoreset, as_torch
+        self.mjmodel = m = _model.load_asset(spec["model"])
         self.muscle_condition = spec.get("muscle_condition", "")
         if self.muscle_condition == "sarcopenia":                      # base_v0.py:64-68: a model edit
-            self.mjmodel = self.mjmodel.with_sarcopenia()
-        self.model = capi.HipModel(self.mjmodel.blob(), device)       # raises if there is no GPU / no library
+            self.mjmodel = m = m.with_sarcopenia()
+        self.model = capi.HipModel(m.blob(), device)                   # raises if there is no GPU / no library
         self.batch = capi.HipBatch(self.model, self.num_envs)
         self.batch.set_env_offset(env_offset)
         self.sensors = bool(sensors)
         if self.sensors:       # touch sensors / contact forces of the leg models; nothing is allocated without it
             _enable_sensors(env_id, self.batch)
-        m = self.mjmodel
-        self.frame_skip = spec["frame_skip"]
+        self.frame_skip, self.max_episode_steps = spec["frame_skip"], spec["max_episode_steps"]
         self.dt = m.timestep * self.frame_skip                        # env_base.py:616-617
-        self.max_episode_steps = spec["max_episode_steps"]
-        w = spec["weights"]
-        if spec.get("target_jnt_range") is not None:   # pose_v0.py:67-75: {joint name: (lo, hi)} replaces the registered target range
-            spec["target_lo"], spec["target_hi"] = self._target_jnt_range(m, spec)
-        if spec["task"] == "pose":
-            self.batch.configure(task=capi.TASK_POSE, frame_skip=self.frame_skip,
-                                 reset_random=spec["reset_type"] == "random", target_generate=spec["target_type"] == "generate",
-                                 target_lo=spec["target_lo"], target_hi=spec["target_hi"], init_qpos=m.qpos0,
-                                 pose_thd=spec["pose_thd"], far_th=4 * np.pi / 2,
-                                 w_pose=w["pose"], w_bonus=w["bonus"], w_act_reg=w["act_reg"], w_penalty=w["penalty"])
-            self.obs_dim = 3 * m.nq + m.n_muscle
-            if spec.get("weight_bodyname") is not None:                # pose_v0.py:163-176: body mass ~ U(weight_range) at every reset
-                if spec.get("weight_range") is None:
-                    raise ValueError(f"{env_id}: weight_bodyname needs weight_range")
-                self.set_body_mass_range(spec["weight_bodyname"], *spec["weight_range"])
-        elif spec["task"] == "walk":
-            key_qpos = np.asarray(m.key_qpos).reshape(-1, m.nq)
-            key_qvel = np.asarray(m.key_qvel).reshape(-1, m.nv)
-            # walk_v0.py:254 init_qpos = key_qpos[0] (the reference orientation of ref_rot); reset "init" starts from keyframe 2
-            # (walk_v0.py:339-349), "random" from keyframe 2 or 3 with N(0, 0.02) noise (:316-332; drawn by the reset kernel)
-            if spec["reset_type"] not in ("init", "random"):
-                raise NotImplementedError("myoLegWalk: reset_type 'init' (keyframe 2) or 'random' (walk_v0.py:316-332)")
-            rnd = spec["reset_type"] == "random"
-            jadr = lambda n: int(m.jnt_qposadr[m.name2id("joint", n)])
-            self.batch.configure_walk(
-                frame_skip=self.frame_skip, hip_period=spec["hip_period"], min_height=spec["min_height"], max_rot=spec["max_rot"],
-                target_x_vel=spec["target_x_vel"], target_y_vel=spec["target_y_vel"],
-                target_rot=spec["target_rot"] if spec["target_rot"] is not None else key_qpos[0][3:7],
-                bodies=[m.name2id("body", n) for n in ("talus_l", "talus_r", "pelvis", "torso")],
-                qadr_hip_flexion=[jadr("hip_flexion_l"), jadr("hip_flexion_r")],
-                qadr_joint_angle=[jadr(n) for n in ("hip_adduction_l", "hip_adduction_r", "hip_rotation_l", "hip_rotation_r")],
-                weights=[w[k] for k in ("vel_reward", "done", "cyclic_hip", "ref_rot", "joint_angle_rew")],
-                init_qpos=key_qpos[2], init_qvel=key_qvel[2], knee_height=spec.get("knee_height", 0.0),
-                terrain={"rough": capi.TERRAIN_ROUGH, "hilly": capi.TERRAIN_HILLY, "stairs": capi.TERRAIN_STAIRS}.get(spec.get("terrain"), capi.TERRAIN_NONE),
-                terrain_scalar=spec.get("terrain_scalar", (0.0, 0.0)),
-                init_qpos_alt=key_qpos[3] if rnd else None, init_qvel_alt=key_qvel[3] if rnd else None, reset_noise_std=0.02 if rnd else 0.0)
-            self.obs_dim = (m.nq - 2) + m.nv + 16 + 4 * m.nu
-        elif spec["task"] == "stand":
-            from .mjcf import quat2mat
-            key_qpos = np.asarray(m.key_qpos).reshape(-1, m.nq)
-            key_qvel = np.asarray(m.key_qvel).reshape(-1, m.nv)
-            init = key_qpos[0].astype(float)                              # walk_v0.py:63-64
-            adr = np.asarray(m.jnt_qposadr)
-            nlo, nhi = np.zeros(m.nq), np.zeros(m.nq)
-            clo, chi = np.full(m.nq, -1e30), np.full(m.nq, 1e30)
-            nlo[adr], nhi[adr] = spec["joint_random_range"]               # generate_qpos (:152-167): only each joint's first coordinate moves ...
-            clo[adr], chi[adr] = m.jnt_range[:, 0], m.jnt_range[:, 1]      # ... and is clipped to jnt_range -- (0, 0) for the unlimited free root: x = 0
-            tsid = m.name2id("site", spec["tip"])
-            if int(m.hip_site_link[tsid]) != 0:
-                raise NotImplementedError("stand task: the tip site must ride on the free root link")
-            lpos = np.asarray(m.hip_site_lpos[tsid], float)
-            q0 = np.clip(init[:7] + 0.0, np.r_[clo[:1], [-1e30] * 6], np.r_[chi[:1], [1e30] * 6])
-            p0 = q0[:3] + quat2mat(q0[3:7] / np.linalg.norm(q0[3:7])) @ lpos     # generate_targets (:140-149): the site in the first random pose
-            span = np.asarray(spec["target_span"], float)
-            self.batch.configure(task=capi.TASK_STAND, frame_skip=self.frame_skip, reset_random=0, target_generate=1,
-                                 target_lo=p0 + span[0], target_hi=p0 + span[1], init_qpos=init, init_qvel=key_qvel[0],
-                                 reset_noise=(nlo, nhi), reset_clip=(clo, chi), tip_lpos=lpos,
-                                 near_th=spec["near_th"], far_th=spec["far_th"],
-                                 w_reach=w["reach"], w_bonus=w["bonus"], w_act_reg=w["act_reg"], w_penalty=w["penalty"])
-            self.obs_dim = m.nq + m.nv + 6 + m.n_muscle
-        elif spec["task"] == "hold":
-            init = np.array(m.qpos0, float)
-            init[:-7] = 0.0                                            # obj_hold_v0.py:63-64: fully open hand, palm up
-            init[0] = -1.5
-            if spec["goal"] is None:                                   # Random: around the object's site at the model's initial pose (:125-131)
-                glo, ghi = np.asarray(m.qpos0[-7:-4], float) - spec["goal_span"], np.asarray(m.qpos0[-7:-4], float) + spec["goal_span"]
-            else:
-                glo = ghi = np.asarray(spec["goal"], float)
-            self.batch.configure(task=capi.TASK_HOLD, frame_skip=self.frame_skip, reset_random=0, target_generate=int(spec["goal"] is None),
-                                 target_lo=glo, target_hi=ghi, init_qpos=init,
-                                 near_th=spec["goal_th"], far_th=spec["drop_th"],
-                                 w_reach=w["goal_dist"], w_bonus=w["bonus"], w_act_reg=w["act_reg"], w_penalty=w["penalty"])
-            self.obs_dim = (m.nq - 7) + (m.nv - 6) + 6 + m.n_muscle
-            if "object_size" in spec:
-                self.batch.set_geom_override(m.name2id("geom", "object"), *spec["object_size"])
-        elif spec["task"] == "keyturn":
-            # key_turn_v0.py:54-75, 157-169: fully open hand (init_qpos[:-1] = 0), key angle ~ U(key_init_range) (a reset noise on the last
-            # coordinate only); the Random variant (key_init_range[0] != key_init_range[1]) also re-draws the key body's position
-            lo_k, hi_k = (float(x) for x in spec["key_init_range"])
-            if not hi_k >= lo_k:
-                raise ValueError(f"{env_id}: key_init_range must be (lo, hi) with lo <= hi")
-            init = np.zeros(m.nq)
-            nlo, nhi = np.zeros(m.nq), np.zeros(m.nq)
-            nlo[-1], nhi[-1] = lo_k, hi_k
-            big = np.full(m.nq, 1e30)
-            self.batch.configure(task=capi.TASK_KEYTURN, frame_skip=self.frame_skip, reset_random=0, target_generate=0, init_qpos=init,
-                                 reset_noise=(nlo, nhi), reset_clip=(-big, big),
-                                 tip_sites=[m.name2id("site", n) for n in ("keyhead", "IFtip", "THtip")],
-                                 pose_thd=float(spec["goal_th"]), near_th=0.030, far_th=0.1,
-                                 w_pose=w["key_turn"], w_reach=w["IFtip_approach"], w_act_reg=w["act_reg"], w_bonus=w["bonus"], w_penalty=w["penalty"])
-            self.obs_dim = 2 * m.nq + 6 + m.n_muscle
-            if lo_k != hi_k:                                           # key_turn_v0.py:164-167: key_init_pos + U(-0.01, 0.01)^3
-                self.batch.set_body_pos_range(np.full(3, -0.01), np.full(3, 0.01))
-        elif spec["task"] == "pen":
-            # pen_v0.py:60-96: palm-up open hand, pen at qpos0; sites object top / bottom, target top / bottom, eps_ball; the object body's
-            # origin in its link frame.  Random (pen_v0.py:173-184): the target's orientation is re-drawn at every reset
-            init = np.array(m.qpos0, float)
-            init[:-6] = 0.0
-            init[0] = -1.5
-            ob = m.name2id("body", "Object")
-            self.batch.configure(task=capi.TASK_PEN, frame_skip=self.frame_skip, reset_random=0, target_generate=0, init_qpos=init,
-                                 tip_sites=[m.name2id("site", n) for n in ("object_top", "object_bottom", "target_top", "target_bottom", "eps_ball")],
-                                 tip_lpos=tuple(np.asarray(m.hip_body_lpos).reshape(-1, 3)[ob]), pose_thd=0.95, far_th=0.075,
-                                 w_pose=w["pos_align"], w_reach=w["rot_align"], w_act_reg=w["act_reg"], w_bonus=w["bonus"], w_penalty=w["drop"],
-                                 quat_body=m.name2id("body", "target"))
-            self.obs_dim = (m.nq - 6) + 21 + m.n_muscle
-            if spec.get("target_euler_range") is not None:
-                lo, hi = spec["target_euler_range"]
-                self.batch.set_body_quat_range(lo, hi)
-        elif spec["task"] == "baoding":
-            # baoding_v1.py:54-145, 325-383: palm-up open hand, balls at qpos0; sites ball1, ball2, target1, target2.  Goal parameters per env
-            # (MYO_F_TARGET row: start angle, sign, x radius, y radius, period) ~ U(lo, hi) at every reset: "fixed" is BAODING_CCW from pi / 4,
-            # "random" draws the direction from HOLD / CW / CCW (the sign U(-1, 2) rounded down) and the start angle from U(0, 2 pi)
-            init = np.array(m.qpos0, float)
-            init[:-14] = 0.0
-            init[0] = -1.57
-            if spec["task_choice"] not in ("fixed", "random"):
-                raise ValueError(f"{env_id}: task_choice must be 'fixed' or 'random'")
-            rnd = spec["task_choice"] == "random"
-            (p0, p1), (x0, x1), (y0, y1) = ((float(a) for a in spec[k]) for k in ("goal_time_period", "goal_xrange", "goal_yrange"))
-            if not (0 < p0 <= p1 and x0 <= x1 and y0 <= y1):
-                raise ValueError(f"{env_id}: goal_time_period, goal_xrange and goal_yrange must be (lo, hi) with lo <= hi (periods > 0)")
-            glo = [0.0 if rnd else np.pi / 4, -1.0 if rnd else 1.0, x0, y0, p0]
-            ghi = [2 * np.pi if rnd else np.pi / 4, 2.0 if rnd else 1.0, x1, y1, p1]
-            self.batch.configure(task=capi.TASK_BAODING, frame_skip=self.frame_skip, reset_random=0, target_generate=1, target_lo=glo, target_hi=ghi,
-                                 init_qpos=init, tip_sites=[m.name2id("site", n) for n in ("ball1_site", "ball2_site", "target1_site", "target2_site")],
-                                 pose_thd=float(spec["proximity_th"]), far_th=float(spec["drop_th"]), w_pose=w["pos_dist_1"], w_reach=w["pos_dist_2"])
-            self.obs_dim = (m.nq - 14) + 24
-        elif spec["task"] == "die":
-            # reorient_v0.py:45-109, 209-250: palm-up open hand (init_qpos[:-7] = 0: the die's first slide is zeroed too, as the reference
-            # does), die at qpos0; sites = the origin and axis points of the die's and the target's frames.  The goal offset (MYO_F_TARGET row)
-            # ~ U(goal_pos)^3 and the target's Euler angles ~ U(goal_rot)^3 are re-drawn per env at every reset
-            init = np.array(m.qpos0, float)
-            init[:-7] = 0.0
-            init[0] = -1.5
-            (p0, p1), (r0, r1) = ((float(a) for a in spec[k]) for k in ("goal_pos", "goal_rot"))
-            if not (p0 <= p1 and r0 <= r1):
-                raise ValueError(f"{env_id}: goal_pos and goal_rot must be (lo, hi) with lo <= hi")
-            self.batch.configure(task=capi.TASK_DIE, frame_skip=self.frame_skip, reset_random=0, target_generate=1, target_lo=[p0] * 3, target_hi=[p1] * 3,
-                                 init_qpos=init, tip_sites=[m.name2id("site", n) for n in ("object_o", "object_x", "object_y", "object_z",
-                                                                                          "target_o", "target_x", "target_y", "target_z")],
-                                 near_th=float(spec["pos_th"]), pose_thd=float(spec["rot_th"]), far_th=float(spec["drop_th"]),
-                                 w_pose=w["pos_dist"], w_reach=w["rot_dist"], w_bonus=w["bonus"], w_act_reg=w["act_reg"], w_penalty=w["penalty"],
-                                 quat_body=m.name2id("body", "target"))
-            self.obs_dim = (m.nq - 7) + (m.nv - 6) + 18
-            self.batch.set_body_quat_range([r0] * 3, [r1] * 3)
-        else:
-            tips = [m.name2id("site", t) for t in spec["tips"]]
-            n = len(tips)
-            self.batch.configure(task=capi.TASK_REACH, frame_skip=self.frame_skip, reset_random=0,
-                                 target_generate=spec["target_type"] == "generate", target_lo=spec["target_lo"],
-                                 target_hi=spec["target_hi"], init_qpos=m.qpos0, tip_sites=tips,
-                                 far_th=spec["far_th"] * n, near_th=0.0125 * n,
-                                 w_reach=w["reach"], w_bonus=w["bonus"], w_act_reg=w["act_reg"], w_penalty=w["penalty"])
-            self.obs_dim = 2 * m.nq + 6 * n + m.n_muscle
+        s = tasks.TASKS[spec["task"]].setup(m, spec, env_id)           # host arithmetic only; the calls it asks for follow
+        getattr(self.batch, s.call)(**s.kwargs)
+        for name, args in s.then:
+            getattr(self.batch, name)(*args)
+        if s.body_mass_range is not None:
+            self.set_body_mass_range(*s.body_mass_range)
+        self.obs_dim = s.obs_dim
+        self._obs_in_step = s.call == "configure_walk"                 # the walk task's observation / reward pass is fused into the step kernel
+        self._set_condition(m, spec)
+        self.act_dim = m.nu
+        self.action_space = Box(-1.0, 1.0, (m.nu,))                    # env_base.py:101-113 (normalize_act)
+        self.observation_space = Box(-10.0, 10.0, (self.obs_dim,))     # env_base.py:172-176
+        self._episode_seed = self.seed
+        self._views = {}
+        self._action_buf = self._torch = None
+        if as_torch:
+            import torch
+            self._torch = torch
+            self._action_buf = torch.empty((self.num_envs, m.nu), dtype=torch.float32, device=f"cuda:{device}")
+
+    def _set_condition(self, m, spec):
+        """The action map of the id's muscle condition and the library calls that go with it (base_v0.py:64-80, 100-109)."""
         self.actmap = capi.ACTMAP_MUSCLE_SIGMOID
         if self.muscle_condition == "fatigue":                         # base_v0.py:70-74, 100-104
             self.actmap = capi.ACTMAP_SIGMOID_FATIGUE
@@ -471,123 +321,39 @@ class BatchedMyoEnv:
         elif self.muscle_condition == "reafferentation":               # base_v0.py:76-80, 105-109
             self.actmap = capi.ACTMAP_SIGMOID_REAFFERENTATION
             self.batch.set_condition(self.frame_skip, m.name2id("actuator", "EPL"), m.name2id("actuator", "EIP"))
-        self.act_dim = m.nu
-        self.action_space = Box(-1.0, 1.0, (m.nu,))                    # env_base.py:101-113 (normalize_act)
-        self.observation_space = Box(-10.0, 10.0, (self.obs_dim,))     # env_base.py:172-176
-        self._episode_seed = self.seed
-        self._views = {}
-        self._action_buf = None
-        if as_torch:
-            import torch
-            self._torch = torch
-            self._action_buf = torch.empty((self.num_envs, m.nu), dtype=torch.float32, device=f"cuda:{device}")
 
-    @staticmethod
-    def _target_jnt_range(m, spec):
-        n = len(spec["target_lo"])
-        targeted = [m.names["joint"][j] for j in range(m.njnt) if int(m.jnt_qposadr[j]) < n]
-        rng = dict(spec["target_jnt_range"])
-        if sorted(rng) != sorted(targeted):
-            raise ValueError(f"target_jnt_range must name exactly the joints {targeted} (got {sorted(rng)})")
-        lo, hi = np.array(spec["target_lo"], float), np.array(spec["target_hi"], float)
-        for name, (a, b) in rng.items():
-            q = int(m.jnt_qposadr[m.name2id("joint", name)])
-            lo[q], hi[q] = float(a), float(b)
-        return lo, hi
-
-    # -- per-env body masses (MYO_F_BODYMASS) -----------------------------------------------------------------
-    @property
-    def body_mass(self):
+    # -- per-env fields: body masses (MYO_F_BODYMASS), root-body offset (MYO_F_BODYPOS), body orientation (MYO_F_BODYQUAT), goal (MYO_F_TARGET) --
+    body_mass = _field_property("body_mass", capi.F_BODYMASS, None, doc=
         """[num_envs, nbody] mass of every body in every env: a torch view of the library's buffer (no copy; writes take effect at the
         next step) -- the batched `sim.model.body_mass[bid] = ...`.  First use starts the per-env body-mass override, which steps the model
-        on the run-time-sizes kernel of its class.  With as_torch=False: a numpy copy (assign the property to write it back)."""
-        return self.view(capi.F_BODYMASS)
-
-    @body_mass.setter
-    def body_mass(self, value):
-        if self.as_torch:
-            self.view(capi.F_BODYMASS).copy_(self._torch.as_tensor(value, dtype=self._torch.float32).expand(self.num_envs, -1))
-        else:
-            self.batch.write(capi.F_BODYMASS, np.broadcast_to(np.asarray(value, np.float32), (self.num_envs, self.mjmodel.nbody)))
+        on the run-time-sizes kernel of its class.  With as_torch=False: a numpy copy (assign the property to write it back).""")
 
     def set_body_mass_range(self, body, lo, hi):
         """Re-draw the mass of `body` (id or name) ~ U(lo, hi) at every reset of every env (PoseEnvV0 weight_bodyname / weight_range);
         lo == hi: no re-draw.  Ranges of the other bodies are left as they are."""
         b = self.mjmodel.body_name2id(body) if isinstance(body, str) else int(body)
-        nb = self.mjmodel.nbody
         r = self.batch.read(capi.F_BODYMASS_RANGE)
-        r[:, b], r[:, nb + b] = float(lo), float(hi)
+        r[:, b], r[:, self.mjmodel.nbody + b] = float(lo), float(hi)
         self.batch.write(capi.F_BODYMASS_RANGE, r)
 
-    # -- per-env root-body offset (MYO_F_BODYPOS) --------------------------------------------------------------
-    @property
-    def body_pos(self):
+    body_pos = _field_property("body_pos", capi.F_BODYPOS, 3, doc=
         """[num_envs, 3] offset of the key body from its compiled position in every env (the batched `sim.model.body_pos[-1] = ...` of
         KeyTurnEnvV0.reset, as an offset): a torch view of the library's buffer (no copy; writes take effect at the next step / observation).
-        TrackEnv-class models whose last joint sits on a root body only.  With as_torch=False: a numpy copy (assign the property to write it)."""
-        return self.view(capi.F_BODYPOS)
-
-    @body_pos.setter
-    def body_pos(self, value):
-        if self.as_torch:
-            self.view(capi.F_BODYPOS).copy_(self._torch.as_tensor(value, dtype=self._torch.float32).expand(self.num_envs, -1))
-        else:
-            self.batch.write(capi.F_BODYPOS, np.broadcast_to(np.asarray(value, np.float32), (self.num_envs, 3)))
-
-    # -- per-env body orientation (MYO_F_BODYQUAT) ------------------------------------------------------------
-    @property
-    def body_quat(self):
+        TrackEnv-class models whose last joint sits on a root body only.  With as_torch=False: a numpy copy (assign the property to write it).""")
+    body_quat = _field_property("body_quat", capi.F_BODYQUAT, 4, doc=
         """[num_envs, 4] body_quat (w x y z) of the pen / die task's target in every env (the batched `sim.model.body_quat[target] = ...` of
         PenTwirlRandomEnvV0.reset / ReorientEnvV0.reset): a torch view of the library's buffer (no copy; writes take effect at the next step / observation).
-        With as_torch=False: a numpy copy (assign the property to write it)."""
-        return self.view(capi.F_BODYQUAT)
-
-    @body_quat.setter
-    def body_quat(self, value):
-        if self.as_torch:
-            self.view(capi.F_BODYQUAT).copy_(self._torch.as_tensor(value, dtype=self._torch.float32).expand(self.num_envs, -1))
-        else:
-            self.batch.write(capi.F_BODYQUAT, np.broadcast_to(np.asarray(value, np.float32), (self.num_envs, 4)))
-
-    # -- per-env goal parameters of the baoding task (MYO_F_TARGET) ------------------------------------------
-    @property
-    def goal_params(self):
+        With as_torch=False: a numpy copy (assign the property to write it).""")
+    goal_params = _field_property("goal_params", capi.F_TARGET, 5, task="baoding", doc=
         """[num_envs, 5] goal parameters of the baoding task in every env: start angle, direction sign (0 hold, -1 CW, +1 CCW), x radius, y
         radius, period (BaodingEnvV1's ball_1_starting_angle, which_task, x_radius, y_radius, time_period).  A torch view of the library's
         buffer (no copy; writes move the targets from the next observation on, until the env's next reset re-draws them).  With
-        as_torch=False: a numpy copy (assign the property to write it)."""
-        if self.spec["task"] != "baoding":
-            raise AttributeError("goal_params: baoding task only")
-        return self.view(capi.F_TARGET)
-
-    @goal_params.setter
-    def goal_params(self, value):
-        if self.spec["task"] != "baoding":
-            raise AttributeError("goal_params: baoding task only")
-        if self.as_torch:
-            self.view(capi.F_TARGET).copy_(self._torch.as_tensor(value, dtype=self._torch.float32).expand(self.num_envs, -1))
-        else:
-            self.batch.write(capi.F_TARGET, np.broadcast_to(np.asarray(value, np.float32), (self.num_envs, 5)))
-
-    # -- per-env goal offset of the die task (MYO_F_TARGET) ---------------------------------------------------
-    @property
-    def goal_offset(self):
+        as_torch=False: a numpy copy (assign the property to write it).""")
+    goal_offset = _field_property("goal_offset", capi.F_TARGET, 3, task="die", doc=
         """[num_envs, 3] offset of the die task's target from its compiled position in every env (the batched `sim.model.body_pos[target]
         = goal_init_pos + ...` of ReorientEnvV0.reset, as an offset); its orientation is `body_quat`.  A torch view of the library's buffer
         (no copy; writes move the goal from the next observation on, until the env's next reset re-draws it).  With as_torch=False: a
-        numpy copy (assign the property to write it)."""
-        if self.spec["task"] != "die":
-            raise AttributeError("goal_offset: die task only")
-        return self.view(capi.F_TARGET)
-
-    @goal_offset.setter
-    def goal_offset(self, value):
-        if self.spec["task"] != "die":
-            raise AttributeError("goal_offset: die task only")
-        if self.as_torch:
-            self.view(capi.F_TARGET).copy_(self._torch.as_tensor(value, dtype=self._torch.float32).expand(self.num_envs, -1))
-        else:
-            self.batch.write(capi.F_TARGET, np.broadcast_to(np.asarray(value, np.float32), (self.num_envs, 3)))
+        numpy copy (assign the property to write it).""")
 
     # -- touch sensors and contact forces (make(..., sensors=True)) ---------------------------------------
     def _need_sensors(self):
@@ -614,23 +380,6 @@ class BatchedMyoEnv:
         v = self.view(capi.F_CFRC)
         return v.view(self.num_envs, -1, 3) if self.as_torch else v.reshape(self.num_envs, -1, 3)
 
-    # -- zero-copy views ---------------------------------------------------------------------------------
-    def view(self, field):
-        """torch view (as_torch) or numpy copy of a per-env field."""
-        if not self.as_torch:
-            return self.batch.read(field)
-        if field not in self._views:
-            ptr, pitch, width = self.batch.field_ptr(field)
-            ts = "<i4" if field in capi.INT_FIELDS else "<f4"
-            arr = _DevArray(ptr, (self.num_envs, width), ts, self.batch)
-            self._views[field] = self._torch.as_tensor(arr, device=f"cuda:{self.device}")
-        return self._views[field]
-
-    def _stream(self):
-        if self.as_torch:
-            return self._torch.cuda.current_stream(self.device).cuda_stream
-        return None
-
     # -- gym API -------------------------------------------------------------------------------------------
     def reset(self, seed=None):
         if seed is not None:
@@ -651,7 +400,7 @@ class BatchedMyoEnv:
             # host actions are uploaded into the library's action buffer; the action map runs in the step kernel either way
             self.batch.write(capi.F_ACTION, a)
             self.batch.step(self.batch.field_ptr(capi.F_ACTION)[0], self.actmap, self.frame_skip, s)
-        if self.spec["task"] != "walk":      # the walk task's observation / reward pass is fused into the step kernel
+        if not self._obs_in_step:
             self.batch.obs(s)
         if self.as_torch:
             reward = self.view(capi.F_REWARD)[:, 0].clone()
@@ -694,15 +443,14 @@ def _enable_sensors(env_id, batch):
 
 
 def _make_track(env_id, num_envs, reference=None, flavour="mjx", sensors=False, **kw):
-    from .track import ClassicTrackEnv, TrackEnv
     if flavour not in ("mjx", "classic"):
         raise ValueError(f"{env_id}: flavour must be 'mjx' (mjx/myodm_v0.py, the default) or 'classic' (envs/myo/myodm/myodm_v0.py), got {flavour!r}")
     reference = _myodm_reference(env_id, reference)
     kw.setdefault("max_episode_steps", REGISTRY[env_id]["max_episode_steps"])
     if flavour == "classic":
-        env = ClassicTrackEnv(num_envs=num_envs, object_name=REGISTRY[env_id]["object"], reference=reference, **kw)
+        env = track.ClassicTrackEnv(num_envs=num_envs, object_name=REGISTRY[env_id]["object"], reference=reference, **kw)
     else:
-        env = TrackEnv(num_envs=num_envs, object_name=REGISTRY[env_id]["object"], reference=reference, gym_api=True, **kw)
+        env = track.TrackEnv(num_envs=num_envs, object_name=REGISTRY[env_id]["object"], reference=reference, gym_api=True, **kw)
     env.id = env_id
     if sensors:
         _enable_sensors(env_id, env.batch)
@@ -729,27 +477,19 @@ def myodm_spec(env_id, flavour="mjx", reference=None):
     """What make(env_id, flavour=...) builds for a MyoDM id, worked out on the host (no GPU): frame_skip, obs_dim, act_dim, init_qpos,
     max_episode_steps (the TimeLimit) and the reference type.  init_qpos = qpos0 with [:robot_dim] = robot_init, the object position from
     object_init[:3] and its three hinges from quat2euler(object_init[3:]) (envs/myo/myodm/myodm_v0.py:168-179, mjx/myodm_v0.py:144-150)."""
-    from .track import ReferenceMotion, quat2euler
     if flavour not in ("mjx", "classic"):
         raise ValueError(f"{env_id}: flavour must be 'mjx' or 'classic', got {flavour!r}")
     spec = REGISTRY[env_id]
     if spec.get("task") != "track":
         raise KeyError(f"{env_id} is not a MyoDM id")
     m = _model.load_asset(f"myohand_object_{spec['object']}")
-    ref = ReferenceMotion(_myodm_reference(env_id, reference))
-    init = np.array(m.qpos0, float)
-    ri, oi = ref.get_init()
-    if ri is not None:
-        init[: ref.robot_dim] = ri
-    if oi is not None:
-        init[ref.robot_dim: ref.robot_dim + 3] = oi[:3]
-        init[-3:] = quat2euler(oi[3:])
+    ref = track.ReferenceMotion(_myodm_reference(env_id, reference))
     nr = ref.robot_dim
     if flavour == "classic":     # qp, qv, hand_qpos_err, hand_qvel_err ([0] without robot_vel), obj_com_err, act (base_v0.py:34-38)
         obs_dim = m.nq + m.nv + nr + (nr if ref.reference["robot_vel"] is not None else 1) + 3 + m.n_muscle
     else:
         obs_dim = m.nq + m.nv
-    return dict(frame_skip=10 if flavour == "classic" else 5, obs_dim=obs_dim, act_dim=m.nu, init_qpos=init.astype(np.float32),
+    return dict(frame_skip=10 if flavour == "classic" else 5, obs_dim=obs_dim, act_dim=m.nu, init_qpos=track.myodm_init_qpos(m, ref),
                 max_episode_steps=spec["max_episode_steps"], ref_type=ref.type)
 
 

@@ -712,26 +712,13 @@ class _Compiler:
             else:
                 raise NotImplementedError(f"unsupported worldbody child <{t}>")
 
-    # ---- finalisation: numbering, inertias, derived constants
+    # ---- finalisation: numbering, inertias, derived constants.  Each _xxx_arrays method returns its arrays in blob order
     def _finalize(self):
-        # MuJoCo numbers bodies depth-first in document order.  _do_body appended them in
-        # document order already, but worldbody-level geoms/sites interleave with bodies, which
-        # only affects geom/site ids: renumber geoms and sites grouped by body id (stable).
-        nb = len(self.bodies)
-        gorder = sorted(range(len(self.geoms)), key=lambda i: self.geoms[i]["body"])
-        sorder = sorted(range(len(self.sites)), key=lambda i: self.sites[i]["body"])
-        self.geoms = [self.geoms[i] for i in gorder]
-        self.sites = [self.sites[i] for i in sorder]
-        for b in self.bodies:
-            b["geoms"] = []
-        for gi, g in enumerate(self.geoms):
-            self.bodies[g["body"]]["geoms"].append(gi)
+        self._group_by_body()
         # joints were appended in body order already (body ids are document order)
-        A = {}
         names = dict(body=[b["name"] for b in self.bodies], joint=[j["name"] for j in self.joints],
                      geom=[g["name"] for g in self.geoms], site=[s["name"] for s in self.sites],
                      tendon=[t["name"] for t in self.tendons], actuator=[a["name"] for a in self.actuators])
-        njnt = len(self.joints)
         # qpos / dof addressing
         qadr, dadr = 0, 0
         jnt_qposadr, jnt_dofadr = [], []
@@ -741,6 +728,44 @@ class _Compiler:
             qadr += {JNT_FREE: 7, JNT_BALL: 4, JNT_SLIDE: 1, JNT_HINGE: 1}[j["type"]]
             dadr += {JNT_FREE: 6, JNT_BALL: 3, JNT_SLIDE: 1, JNT_HINGE: 1}[j["type"]]
         nq, nv = qadr, dadr
+        A = self._body_arrays(jnt_dofadr)
+        weld = A["body_weldid"]
+        A.update(self._body_inertias(weld))
+        A.update(self._joint_arrays(jnt_qposadr, jnt_dofadr))
+        dofs, nM = self._dof_arrays(jnt_qposadr, jnt_dofadr, nq, nv, A["body_dofadr"], A["body_dofnum"])
+        A.update(dofs)
+        geoms, mesh_vert, mesh_adr = self._kept_geoms()
+        names["geom"] = [g["name"] for g in geoms]
+        A.update(self._geom_arrays(geoms, mesh_vert, mesh_adr))
+        A.update(self._site_arrays(names))
+        A.update(self._tendon_arrays(names, geoms))
+        A.update(self._actuator_arrays(names))
+        A.update(self._pair_arrays(names, geoms, weld))
+        A.update(self._keyframe_arrays(A["qpos0"], nq, nv))
+        A.update(self._option_arrays())
+        nu = len(self.actuators)
+        A["sizes"] = np.array([nq, nv, nu, nu, len(self.bodies), len(self.joints), len(geoms), len(self.sites), len(self.tendons), len(A["wrap_type"]),
+                               len(A["pair_geom"]), nM, len(self.equalities)], np.int32)
+        A.update(self._equality_arrays(names))
+        A["sizes"][12] = len(A["eq_obj1id"])
+        return CompiledModel(arrays=A, names=names, source=self.path)
+
+    def _group_by_body(self):
+        # MuJoCo numbers bodies depth-first in document order.  _do_body appended them in
+        # document order already, but worldbody-level geoms/sites interleave with bodies, which
+        # only affects geom/site ids: renumber geoms and sites grouped by body id (stable).
+        gorder = sorted(range(len(self.geoms)), key=lambda i: self.geoms[i]["body"])
+        sorder = sorted(range(len(self.sites)), key=lambda i: self.sites[i]["body"])
+        self.geoms = [self.geoms[i] for i in gorder]
+        self.sites = [self.sites[i] for i in sorder]
+        for b in self.bodies:
+            b["geoms"] = []
+        for gi, g in enumerate(self.geoms):
+            self.bodies[g["body"]]["geoms"].append(gi)
+
+    def _body_arrays(self, jnt_dofadr):
+        nb = len(self.bodies)
+        A = {}
         A["body_parentid"] = np.array([b["parent"] for b in self.bodies], np.int32)
         A["body_pos"] = np.stack([b["pos"] for b in self.bodies])
         A["body_quat"] = np.stack([b["quat"] for b in self.bodies])
@@ -762,12 +787,46 @@ class _Compiler:
             weld[bi] = bi if self.bodies[bi]["jnts"] else weld[p]
             rootid[bi] = bi if p == 0 else rootid[p]
         A["body_weldid"], A["body_rootid"] = weld, rootid
-        # inertias
+        return A
+
+    def _geom_inertia(self, b):
+        """(mass, COM, inertia about the COM, any mass at all?) of a body from its geoms (inertiafromgeom)."""
+        glo, ghi = self.comp["inertiagrouprange"]
+        m, c, I = 0.0, np.zeros(3), np.zeros((3, 3))
+        parts = []
+        for gi in b["geoms"]:
+            g = self.geoms[gi]
+            if not (glo <= g["group"] <= ghi):
+                continue
+            R = quat2mat(g["quat"])
+            if g["type"] == GEOM_MESH:
+                V, mc, mI = self._mesh_props(g["mesh"])
+                gm = g["mass"] if g["mass"] is not None else g["density"] * V
+                Ig = R @ (mI * (gm / V)) @ R.T
+                pc = g["pos"] + R @ mc
+            elif g["type"] in (GEOM_PLANE, GEOM_HFIELD):
+                continue
+            else:
+                V, Id = geom_volume_inertia(g["type"], g["size"])
+                gm = g["mass"] if g["mass"] is not None else g["density"] * V
+                Ig = R @ np.diag(Id * (gm / V)) @ R.T
+                pc = g["pos"]
+            parts.append((gm, pc, Ig))
+            m += gm
+            c += gm * pc
+        if m > 0:
+            c /= m
+            for gm, pc, Ig in parts:
+                d = pc - c
+                I += Ig + gm * (np.dot(d, d) * np.eye(3) - np.outer(d, d))
+        return m, c, I, m > 0
+
+    def _body_inertias(self, weld):
+        nb = len(self.bodies)
         mass = np.zeros(nb)
         ipos = np.zeros((nb, 3))
         iquat = np.tile(np.array([1.0, 0, 0, 0]), (nb, 1))
         inertia = np.zeros((nb, 3))
-        glo, ghi = self.comp["inertiagrouprange"]
         for bi, b in enumerate(self.bodies):
             if bi == 0:
                 continue
@@ -777,36 +836,7 @@ class _Compiler:
             if use_geoms:
                 if static:
                     continue  # never enters the dynamics; skip loading big visual meshes
-                m, c, I = 0.0, np.zeros(3), np.zeros((3, 3))
-                parts = []
-                for gi in b["geoms"]:
-                    g = self.geoms[gi]
-                    if not (glo <= g["group"] <= ghi):
-                        continue
-                    R = quat2mat(g["quat"])
-                    if g["type"] == GEOM_MESH:
-                        V, mc, mI = self._mesh_props(g["mesh"])
-                        gm = g["mass"] if g["mass"] is not None else g["density"] * V
-                        Ig = R @ (mI * (gm / V)) @ R.T
-                        pc = g["pos"] + R @ mc
-                    elif g["type"] in (GEOM_PLANE, GEOM_HFIELD):
-                        continue
-                    else:
-                        V, Id = geom_volume_inertia(g["type"], g["size"])
-                        gm = g["mass"] if g["mass"] is not None else g["density"] * V
-                        Ig = R @ np.diag(Id * (gm / V)) @ R.T
-                        pc = g["pos"]
-                    parts.append((gm, pc, Ig))
-                    m += gm
-                    c += gm * pc
-                if m > 0:
-                    c /= m
-                    for gm, pc, Ig in parts:
-                        d = pc - c
-                        I += Ig + gm * (np.dot(d, d) * np.eye(3) - np.outer(d, d))
-                mass[bi], ipos[bi] = m, c
-                full = I
-                have = m > 0
+                mass[bi], ipos[bi], full, have = self._geom_inertia(b)
             else:
                 ine = b["inertial"]
                 mass[bi], ipos[bi] = ine["mass"], ine["pos"]
@@ -835,8 +865,11 @@ class _Compiler:
                     inertia[bi] = (a + bb + c3) / 3.0
                 elif not static:
                     raise ValueError(f"body {b['name']}: inertia violates A+B>=C")
-        A["body_mass"], A["body_ipos"], A["body_iquat"], A["body_inertia"] = mass, ipos, iquat, inertia
-        # joints / dofs
+        return {"body_mass": mass, "body_ipos": ipos, "body_iquat": iquat, "body_inertia": inertia}
+
+    def _joint_arrays(self, jnt_qposadr, jnt_dofadr):
+        njnt = len(self.joints)
+        A = {}
         A["jnt_type"] = np.array([j["type"] for j in self.joints], np.int32)
         A["jnt_qposadr"] = np.array(jnt_qposadr, np.int32)
         A["jnt_dofadr"] = np.array(jnt_dofadr, np.int32)
@@ -849,6 +882,11 @@ class _Compiler:
         A["jnt_solref"] = np.stack([j["solref"] for j in self.joints]) if njnt else np.zeros((0, 2))
         A["jnt_solimp"] = np.stack([j["solimp"] for j in self.joints]) if njnt else np.zeros((0, 5))
         A["jnt_stiffness"] = np.array([j["stiffness"] for j in self.joints])
+        return A
+
+    def _dof_arrays(self, jnt_qposadr, jnt_dofadr, nq, nv, body_dofadr, body_dofnum):
+        """(qpos0 and the per-dof arrays, number of non-zeros nM of the tree-sparse mass matrix)."""
+        A = {}
         qpos0 = np.zeros(nq)
         qspring = np.zeros(nq)
         dof_bodyid = np.zeros(nv, np.int32)
@@ -900,7 +938,10 @@ class _Compiler:
                 nM += 1
                 k = dof_parent[k]
         A["dof_Madr"] = madr
-        # geoms: keep everything that collides or wraps (visual-only geoms dropped)
+        return A, nM
+
+    def _kept_geoms(self):
+        """(kept geoms, hull vertex lists, mesh name -> (first vertex, count)): everything that collides or wraps (visual-only geoms dropped)."""
         wrap_geoms = {w["obj"] for w in self.wraps if w["type"] == -1}
         keep = [i for i, g in enumerate(self.geoms)
                 if (g["contype"] or g["conaffinity"]) or (g["name"] and g["name"] in wrap_geoms)]
@@ -916,7 +957,7 @@ class _Compiler:
                 if _can_pair(i):
                     self._mesh_props(self.geoms[i]["mesh"])
                     self.geoms[i]["size"] = np.array([self.meshes[self.geoms[i]["mesh"]]["rmax"], 0.0, 0.0])
-                    if self.convex_meshes:      # (after the inertia pass above, which used the file's frame)
+                    if self.convex_meshes:      # (after the inertia pass, which used the file's frame)
                         mm = self.meshes[self.geoms[i]["mesh"]]
                         self.geoms[i] = dict(self.geoms[i], pos=self.geoms[i]["pos"] + quat2mat(self.geoms[i]["quat"]) @ mm["hull_center"],
                                              size=np.array([mm["hull_rmax"], 0.0, 0.0]))
@@ -934,9 +975,11 @@ class _Compiler:
         # explicit pairs may name geoms that neither collide dynamically nor wrap: keep them too
         pair_names = {pr[k] for pr in self.pairs for k in ("geom1", "geom2")}
         keep = sorted(set(keep) | {i for i, g in enumerate(self.geoms) if g["name"] and g["name"] in pair_names})
-        geoms = [self.geoms[i] for i in keep]
-        names["geom"] = [g["name"] for g in geoms]
+        return [self.geoms[i] for i in keep], mesh_vert, mesh_adr
+
+    def _geom_arrays(self, geoms, mesh_vert, mesh_adr):
         ng = len(geoms)
+        A = {}
         A["geom_type"] = np.array([g["type"] for g in geoms], np.int32)
         A["geom_bodyid"] = np.array([g["body"] for g in geoms], np.int32)
         A["geom_pos"] = np.stack([g["pos"] for g in geoms]) if ng else np.zeros((0, 3))
@@ -956,7 +999,11 @@ class _Compiler:
         A["geom_meshadr"] = np.array([mesh_adr[g["mesh"]][0] if (g["type"] == GEOM_MESH and g["mesh"] in mesh_adr) else -1 for g in geoms], np.int32)
         A["geom_meshnum"] = np.array([mesh_adr[g["mesh"]][1] if (g["type"] == GEOM_MESH and g["mesh"] in mesh_adr) else 0 for g in geoms], np.int32)
         A["mesh_vert"] = np.concatenate(mesh_vert) if mesh_vert else np.zeros((0, 3))
-        # sites
+        return A
+
+    def _site_arrays(self, names):
+        """Sites and, for models that have them, touch sensors (whose names go to names["sensor"])."""
+        A = {}
         A["site_bodyid"] = np.array([s["body"] for s in self.sites], np.int32)
         A["site_pos"] = np.stack([s["pos"] for s in self.sites]) if self.sites else np.zeros((0, 3))
         if self.sensors:
@@ -969,7 +1016,9 @@ class _Compiler:
             A["sensor_type"] = np.zeros(len(self.sensors), np.int32)
             A["sensor_objid"] = np.array([names["site"].index(s["site"]) for s in self.sensors], np.int32)
             A["sensor_adr"] = np.arange(len(self.sensors), dtype=np.int32)
-        # tendons + wraps
+        return A
+
+    def _tendon_arrays(self, names, geoms):
         nt = len(self.tendons)
         wtype, wobj, wprm = [], [], []
         for w in self.wraps:
@@ -988,6 +1037,7 @@ class _Compiler:
                     raise ValueError(f"wrap geom {w['obj']} must be sphere or cylinder")
                 wobj.append(gi)
                 wprm.append(float(names["site"].index(w["prm"])) if w["prm"] else -1.0)
+        A = {}
         A["wrap_type"] = np.array(wtype, np.int32)
         A["wrap_objid"] = np.array(wobj, np.int32)
         A["wrap_prm"] = np.array(wprm)
@@ -1003,8 +1053,11 @@ class _Compiler:
         for t in self.tendons:
             if t["frictionloss"] != 0:
                 raise NotImplementedError("tendon frictionloss")
-        # actuators
+        return A
+
+    def _actuator_arrays(self, names):
         nu = len(self.actuators)
+        A = {}
         A["actuator_trnid"] = np.array(
             [names["tendon"].index(a["target"]) if a["trntype"] == "tendon" else names["joint"].index(a["target"])
              for a in self.actuators], np.int32)
@@ -1021,14 +1074,17 @@ class _Compiler:
         A["actuator_has_lengthrange"] = np.array([a["has_lengthrange"] for a in self.actuators], np.int32)
         A["actuator_acc0"] = np.zeros(nu)
         A["actuator_kind"] = np.array([a["kind"] for a in self.actuators], np.int32)
-        # collision pair table (static part of mj_collision's filtering)
+        return A
+
+    def _dynamic_pairs(self, names, geoms, weld):
+        """Geom pairs that can collide: the static part of mj_collision's filtering (contype / conaffinity, same or adjacent weld, excludes)."""
         excl = set()
         for b1, b2 in self.excludes:
             i1, i2 = names["body"].index(b1), names["body"].index(b2)
             excl.add((min(i1, i2), max(i1, i2)))
         pairs = []
-        for g1 in range(ng):
-            for g2 in range(g1 + 1, ng):
+        for g1 in range(len(geoms)):
+            for g2 in range(g1 + 1, len(geoms)):
                 a, b = geoms[g1], geoms[g2]
                 if not ((a["contype"] & b["conaffinity"]) or (b["contype"] & a["conaffinity"])):
                     continue
@@ -1043,6 +1099,11 @@ class _Compiler:
                 if (min(b1, b2), max(b1, b2)) in excl:
                     continue
                 pairs.append((g1, g2))
+        return pairs
+
+    def _pair_arrays(self, names, geoms, weld):
+        """Collision pair table: dynamic pairs, the height-field record, then explicit <contact><pair>s."""
+        pairs = self._dynamic_pairs(names, geoms, weld)
         # heightfield geoms: kept as geoms, but their pairs are dropped (myoLegWalk-v0 parks the terrain below the floor plane,
         # envs/myo/myobase/walk_v0.py:257-261); recorded so that callers can see it
         nhf = sum(1 for (a, b) in pairs if geoms[a]["type"] == GEOM_HFIELD or geoms[b]["type"] == GEOM_HFIELD)
@@ -1061,6 +1122,7 @@ class _Compiler:
                     raise NotImplementedError("height field against a non-convex-primitive geom")
         else:
             pairs = [(a, b) for (a, b) in pairs if geoms[a]["type"] != GEOM_HFIELD and geoms[b]["type"] != GEOM_HFIELD]
+        A = {}
         A["dropped_hfield_pairs"] = np.array([nhf], np.int32)
         hf = self.hfields[geoms[hf_geoms[0]]["hfield"]] if hf_geoms else None
         A["hfield_size"] = np.array(hf["size"], float) if hf else np.zeros(4)            # x, y half-extents, z scale, base depth
@@ -1076,26 +1138,29 @@ class _Compiler:
             pair_condim.append(int(pr.get("condim", 3)))
         A["pair_geom"] = np.array(pairs, np.int32).reshape(-1, 2)
         A["pair_condim"] = np.array(pair_condim, np.int32)
-        # keyframes
+        return A
+
+    def _keyframe_arrays(self, qpos0, nq, nv):
         kq = []
         for k in self.keys:
             q = qpos0.copy()
             if "qpos" in k:
                 q = _floats(k["qpos"], nq)
             kq.append(q)
-        A["key_qpos"] = np.stack(kq) if kq else np.zeros((0, nq))
-        A["key_qvel"] = np.stack([_floats(k["qvel"], nv) if "qvel" in k else np.zeros(nv) for k in self.keys]) if kq else np.zeros((0, nv))
-        # options
+        return {"key_qpos": np.stack(kq) if kq else np.zeros((0, nq)),
+                "key_qvel": np.stack([_floats(k["qvel"], nv) if "qvel" in k else np.zeros(nv) for k in self.keys]) if kq else np.zeros((0, nv))}
+
+    def _option_arrays(self):
         o = self.opt
         if o["cone"] != "pyramidal" or o["solver"] != "Newton" or o["integrator"] not in ("Euler", "RK4"):
             raise NotImplementedError("only pyramidal cones, the Newton solver and Euler / RK4 integration are restated")
-        A["integrator"] = np.array([1 if o["integrator"] == "RK4" else 0], np.int32)
-        A["opt"] = np.array([o["timestep"], o["gravity"][0], o["gravity"][1], o["gravity"][2], o["tolerance"],
-                             float(o["iterations"]), float(o["ls_iterations"]), o["ls_tolerance"], o["impratio"],
-                             0.0])  # last slot: stat.meaninertia, filled by setconst
-        A["sizes"] = np.array([nq, nv, nu, nu, nb, njnt, ng, len(self.sites), nt, len(wtype), len(pairs), nM,
-                               len(self.equalities)], np.int32)
-        # equality constraints: joint couplings q1 - q1_0 = poly(q2 - q2_0)
+        return {"integrator": np.array([1 if o["integrator"] == "RK4" else 0], np.int32),
+                "opt": np.array([o["timestep"], o["gravity"][0], o["gravity"][1], o["gravity"][2], o["tolerance"],
+                                 float(o["iterations"]), float(o["ls_iterations"]), o["ls_tolerance"], o["impratio"],
+                                 0.0])}  # last slot: stat.meaninertia, filled by setconst
+
+    def _equality_arrays(self, names):
+        """Equality constraints: joint couplings q1 - q1_0 = poly(q2 - q2_0)."""
         eq_j1, eq_j2, eq_data, eq_solref, eq_solimp = [], [], [], [], []
         for tag, at in self.equalities:
             if tag != "joint":
@@ -1108,14 +1173,9 @@ class _Compiler:
             eq_solref.append(_floats(at.get("solref", "0.02 1"), 2))
             eq_solimp.append(_solimp(at.get("solimp")))
         ne = len(eq_j1)
-        A["eq_obj1id"] = np.array(eq_j1, np.int32)
-        A["eq_obj2id"] = np.array(eq_j2, np.int32)
-        A["eq_data"] = np.stack(eq_data) if ne else np.zeros((0, 5))
-        A["eq_solref"] = np.stack(eq_solref) if ne else np.zeros((0, 2))
-        A["eq_solimp"] = np.stack(eq_solimp) if ne else np.zeros((0, 5))
-        A["sizes"][12] = ne
-        cm = CompiledModel(arrays=A, names=names, source=self.path)
-        return cm
+        return {"eq_obj1id": np.array(eq_j1, np.int32), "eq_obj2id": np.array(eq_j2, np.int32),
+                "eq_data": np.stack(eq_data) if ne else np.zeros((0, 5)), "eq_solref": np.stack(eq_solref) if ne else np.zeros((0, 2)),
+                "eq_solimp": np.stack(eq_solimp) if ne else np.zeros((0, 5))}
 
 
 def _solimp(s):

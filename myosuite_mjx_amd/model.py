@@ -231,9 +231,6 @@ def from_mjcf(path, terrain=False, replace=None, convex_meshes=False) -> Model:
     return Model(cm.arrays, cm.names, path)
 
 
-_ASSETS = {"myohand_pose": "myohand_pose", "myofinger_v0": "myofinger_v0", "myolegs": "myolegs"}
-
-
 def asset_stem(name) -> str:
     """Path stem of a committed compiled model: under ASSET_DIR, else under GOLDEN_DIR (e.g. 'myohand_keyturn')."""
     for d in (ASSET_DIR, GOLDEN_DIR):

@@ -83,6 +83,43 @@ def test_unsupported_feature_raises(tmp_path):
         compile_mjcf(str(p))
 
 
+def test_a_model_that_trips_several_refusals_reports_the_first(tmp_path):
+    """The lowering's refusal is data (model.from_mjcf stores the message in hip_unsupported), so which one a model with several
+    unsupported features reports is pinned: the free-joint / ball-joint checks in joint order, then joint transmission, then two
+    actuators on one tendon."""
+    from myosuite_mjx_amd import model as M
+    from myosuite_mjx_amd.lowering import lower
+    from myosuite_mjx_amd.mjcf import JNT_BALL, compile_mjcf
+    from myosuite_mjx_amd.setconst import set_constants
+    xml = """<mujoco><compiler angle="radian"/><worldbody>
+      <body name="a" pos="0 0 1"><joint name="j0" type="hinge" axis="0 1 0"/><geom type="capsule" size="0.05 0.2" pos="0 0 -0.2"/>
+        <site name="s0" pos="0 0 -0.1"/>
+        <body name="b" pos="0 0 -0.4"><joint name="j1" type="free"/><geom type="capsule" size="0.04 0.15" pos="0 0 -0.15"/><site name="s1" pos="0 0 -0.1"/></body>
+      </body></worldbody>
+      <tendon><spatial name="t0"><site site="s0"/><site site="s1"/></spatial></tendon>
+      <actuator><muscle name="m0" joint="j0"/><muscle name="m1" tendon="t0"/><muscle name="m2" tendon="t0"/></actuator></mujoco>"""
+
+    def refusal(text, name):
+        p = tmp_path / name
+        p.write_text(text)
+        m = M.from_mjcf(str(p))
+        assert [k for k in m.arrays if k.startswith("hip_")] == ["hip_unsupported"]
+        return bytes(m.arrays["hip_unsupported"].astype(np.uint8)).decode()
+
+    # a free joint below another body + a muscle on a joint + two muscles on one tendon
+    assert refusal(xml, "free.xml") == "HIP path: a free joint must be the only joint of a root body"
+    # without the free joint the next refusal in line shows
+    assert refusal(xml.replace('type="free"', 'type="slide" axis="0 0 1"'), "slide.xml") == "HIP path: joint transmission is for stateless actuators on hinge / slide joints"
+    # a ball joint (the MJCF compiler refuses those itself, so it is set in the compiled arrays) ahead of the misplaced free joint
+    p = tmp_path / "free.xml"
+    cm = compile_mjcf(str(p))
+    set_constants(cm)
+    cm.arrays["jnt_type"][0] = JNT_BALL
+    with pytest.raises(NotImplementedError) as e:
+        lower(cm)
+    assert str(e.value) == "HIP path: ball joints"
+
+
 def test_sim_scene_style_inline_model(tmp_path):
     """Same shape as the reference's physics/sim_scene_test.py:19-40 (tiny inline hinge chain): compiles and steps."""
     from myosuite_mjx_amd import blob as B

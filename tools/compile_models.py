@@ -1,7 +1,11 @@
 """Compile the reference's MJCF config models into committed MYOB blobs.
 
 Runs in the build container only (reads the model *data* files under /root/reference;
-they do not travel to the GPU box).  Usage: python tools/compile_models.py"""
+they do not travel to the GPU box).  Usage: python tools/compile_models.py [--check] [model ...]
+
+--check compiles without writing and compares every model with the committed files: blob bytes after
+decompression, the JSON side-car and the sensor side-car; one line per model, exit status 1 on any difference."""
+import json
 import os
 import sys
 
@@ -41,24 +45,57 @@ GOLDEN = {
     "myohand_die": "myosuite/envs/myo/assets/hand/myohand_die.xml",           # ReorientEnvV0: the die's boxes alone make it TrackEnv class
 }
 
+
+def compile_model(stem):
+    """(model, sensor side-car or None, path stem of the model's files, stored gzip-compressed?) of one model of MODELS / GOLDEN."""
+    if stem in GOLDEN:
+        return M.from_mjcf(os.path.join(REF, GOLDEN[stem])), None, os.path.join(M.GOLDEN_DIR, stem), True
+    rel = MODELS[stem]
+    if isinstance(rel, tuple) and len(rel) >= 2:
+        m = M.from_mjcf(os.path.join(REF, rel[0]), replace=rel[1], convex_meshes=True)
+    else:
+        m = M.from_mjcf(os.path.join(REF, rel[0]), terrain=True) if isinstance(rel, tuple) else M.from_mjcf(os.path.join(REF, rel))
+    m, side = M.split_sensor_arrays(m)      # touch-sensor arrays go to a side-car of their own: the model's blob keeps its older arrays only
+    return m, side, os.path.join(M.ASSET_DIR, stem), isinstance(rel, tuple) and len(rel) == 3
+
+
+def differences(m, path):
+    """What differs between a fresh model and the files committed at `path`: blob bytes (after decompression) and the JSON side-car."""
+    if not (os.path.exists(path + ".myob") or os.path.exists(path + ".myob.gz")) or not os.path.exists(path + ".json"):
+        return ["missing"]
+    with open(path + ".json") as f:
+        meta = json.load(f)
+    return [what for what, same in (("blob", m.blob() == M.Model.load(path).blob()),
+                                    ("json", meta == {"names": m.names, "source": os.path.basename(m.source)})) if not same]
+
+
+def check(stem):
+    """Compile one model without writing and compare with the committed files; returns the list of differences."""
+    m, side, path, _ = compile_model(stem)
+    diff = differences(m, path)
+    side_path = os.path.join(M.SENSOR_DIR, stem)
+    if side is not None:
+        diff += ["sensors." + d for d in differences(side, side_path)]
+    elif os.path.exists(side_path + ".json"):
+        diff.append("sensors.stale")
+    return diff
+
+
 if __name__ == "__main__":
-    only = sys.argv[1:]
-    for stem, rel in MODELS.items():
-        if only and stem not in only:
-            continue
-        if isinstance(rel, tuple) and len(rel) >= 2:
-            m = M.from_mjcf(os.path.join(REF, rel[0]), replace=rel[1], convex_meshes=True)
-        else:
-            m = M.from_mjcf(os.path.join(REF, rel[0]), terrain=True) if isinstance(rel, tuple) else M.from_mjcf(os.path.join(REF, rel))
-        m, side = M.split_sensor_arrays(m)      # touch-sensor arrays go to a side-car of their own: the model's blob keeps its older arrays only
+    only = [a for a in sys.argv[1:] if a != "--check"]
+    stems = [s for s in (*MODELS, *GOLDEN) if not only or s in only]
+    if "--check" in sys.argv[1:]:
+        bad = 0
+        for stem in stems:
+            diff = check(stem)
+            bad += bool(diff)
+            print(stem, "identical" if not diff else "DIFFERS: " + ", ".join(diff), flush=True)
+        print(f"{len(stems) - bad} of {len(stems)} models identical to the committed files")
+        sys.exit(1 if bad else 0)
+    for stem in stems:
+        m, side, path, compress = compile_model(stem)
         if side is not None:
             os.makedirs(M.SENSOR_DIR, exist_ok=True)
             side.save(os.path.join(M.SENSOR_DIR, stem), compress=True)
-        m.save(os.path.join(M.ASSET_DIR, stem), compress=isinstance(rel, tuple) and len(rel) == 3)
-        print(stem, dict(nq=m.nq, nv=m.nv, nu=m.nu, nbody=m.nbody, ntendon=m.ntendon, bytes=len(m.blob())))
-    for stem, rel in GOLDEN.items():
-        if only and stem not in only:
-            continue
-        m = M.from_mjcf(os.path.join(REF, rel))
-        m.save(os.path.join(M.GOLDEN_DIR, stem), compress=True)
+        m.save(path, compress=compress)
         print(stem, dict(nq=m.nq, nv=m.nv, nu=m.nu, nbody=m.nbody, ntendon=m.ntendon, bytes=len(m.blob())))

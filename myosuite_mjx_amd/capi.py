@@ -12,26 +12,20 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MYO_HIP_LIB") or os.path.join(_HERE, "libmyo_hip.so")
 SRC_PATH = os.path.join(_HERE, "csrc", "myo_hip.hip")
 
-# field ids (myo_field)
+# field ids (myo_field and the enums that continue it in include/myo_hip.h; tests/test_capi_host.py compares every constant here with the header)
 (F_QPOS, F_QVEL, F_ACT, F_CTRL, F_WARMSTART, F_TIME, F_TARGET, F_OBS, F_REWARD, F_DONE, F_SOLVED, F_FLAGS, F_DIAG,
  F_QACC, F_TENLEN, F_ACTFORCE, F_SITEXPOS, F_ELAPSED, F_ACTION, F_FATIGUE, F_HFIELD, F_GEOMSIZE, F_LINKX, F_METRICS,
- F_BODYMASS, F_BODYMASS_RANGE, F_BODYPOS, F_BODYPOS_RANGE) = range(28)
-F_BODYQUAT, F_BODYQUAT_RANGE = 28, 29      # per-env orientation of one world-welded body (TaskConfig.quat_body selects it)
-F_SENSORDATA, F_CFRC = 30, 31              # touch sensors [B, nsensor] and contact forces [B, (nsensor + 1) * 3] (HipBatch.enable_sensors)
+ F_BODYMASS, F_BODYMASS_RANGE, F_BODYPOS, F_BODYPOS_RANGE,
+ F_BODYQUAT, F_BODYQUAT_RANGE,              # per-env orientation of one world-welded body (TaskConfig.quat_body selects it)
+ F_SENSORDATA, F_CFRC) = range(32)          # touch sensors [B, nsensor] and contact forces [B, (nsensor + 1) * 3] (HipBatch.enable_sensors)
+F_COUNT = F_BODYPOS                         # size of the myo_field list proper
 INT_FIELDS = (F_FLAGS, F_DIAG, F_ELAPSED)
 # width of the per-env override fields as (per body, constant): known without asking for their device pointer, which would start the override
 _OVERRIDE_WIDTH = {F_BODYMASS: (1, 0), F_BODYMASS_RANGE: (2, 0), F_BODYPOS: (0, 3), F_BODYPOS_RANGE: (0, 6), F_BODYQUAT: (0, 4), F_BODYQUAT_RANGE: (0, 6)}
 BENCH_OBS, BENCH_FRESH_ACTIONS, BENCH_AUTORESET = 1, 2, 4
 ACTMAP_NONE, ACTMAP_MUSCLE_SIGMOID, ACTMAP_SIGMOID_FATIGUE, ACTMAP_SIGMOID_REAFFERENTATION, ACTMAP_CTRLRANGE = 0, 1, 2, 3, 4
-TASK_NONE, TASK_POSE, TASK_REACH = 0, 1, 2
-TASK_HOLD = 4
-TASK_STAND = 5
-TASK_TRACK = 6
-TASK_KEYTURN = 7
-TASK_PEN = 8
-TASK_BAODING = 9
-TASK_DIE = 10
-FLAG_BAD_STATE, FLAG_BAD_QACC, FLAG_CONTACT_OVERFLOW, FLAG_CAND_OVERFLOW = 1, 2, 4, 8
+TASK_NONE, TASK_POSE, TASK_REACH, TASK_WALK, TASK_HOLD, TASK_STAND, TASK_TRACK, TASK_KEYTURN, TASK_PEN, TASK_BAODING, TASK_DIE = range(11)
+FLAG_BAD_STATE, FLAG_BAD_QACC, FLAG_CONTACT_OVERFLOW, FLAG_CAND_OVERFLOW, FLAG_SCHED_TIMEOUT = 1, 2, 4, 8, 16
 
 
 class Dims(C.Structure):

@@ -11,7 +11,8 @@
 //   myo_host.h          host records: myo_model, myo_batch, the per-task hook record (TaskHooks) and its generic launchers
 //   myo_task_*.h        key-turn, pen, baoding, die, classic MyoDM: a task's observation body, its configure checks and its hook record
 //   myo_host_model.h    myo_model_load in pieces: blob view, table upload, packing of the per-lane records, kernel class
-//   myo_hip.hip         host side: batches, the table of step-kernel instantiations, launches, the task table, the extern "C" entry points
+//   myo_host_batch.h    batch creation, the per-env override records, the table of fields behind myo_batch_field / read / write
+//   myo_hip.hip         host side: task configuration, the table of step-kernel instantiations, launches, the task table, the extern "C" entry points
 //
 // Execution model: one environment = one wavefront = one workgroup; the whole working set of an env (link
 // frames, sparse tendon Jacobian rows, spatial inertias, mass matrix, contact rows, Newton vectors) lives in that wave's LDS slice
@@ -34,6 +35,7 @@
 #include "myo_task_die.h"
 #include "myo_task_myodm.h"
 #include "myo_host_model.h"
+#include "myo_host_batch.h"
 
 extern "C" {
 
@@ -80,85 +82,16 @@ int myo_model_set_switch(myo_model* m, int dc, int dl, int de) {
   return MYO_OK;
 }
 
-static int balloc(myo_batch* b, void** p, size_t nbytes) {
-  HIPCHK(hipMalloc(p, nbytes));
-  HIPCHK(hipMemset(*p, 0, nbytes));
-  b->dev_allocs.push_back(*p);
-  return 0;
-}
-
-int myo_batch_create(const myo_model* m, int B, myo_batch** out) {
-  if (!m || !out || B <= 0) return fail(MYO_E_ARG, "myo_batch_create: bad arguments");
-  HIPCHK(hipSetDevice(m->device));
-  myo_batch* b = new myo_batch();
-  b->model = m;
-  DevBatch& d = b->db;
-  d.B = B;
-  int nv = m->dm.nv, nu = m->dm.nu, nq = m->nq, rc;
-  b->ntarget_alloc = nv > 24 ? nv : 24;
-  b->obs_alloc = 3 * nv + 4 * nu + 64;
-#define BA(ptr, n) if ((rc = balloc(b, (void**)&ptr, (size_t)(n) * 4))) { myo_batch_free(b); return rc; }
-  BA(d.qpos, (size_t)B * nq) BA(d.qvel, (size_t)B * nv) BA(d.act, (size_t)B * nu) BA(d.ctrl, (size_t)B * nu) BA(d.warm, (size_t)B * nv)
-  BA(d.time, B) BA(d.target, (size_t)B * b->ntarget_alloc) BA(d.obs, (size_t)B * b->obs_alloc) BA(d.reward, B) BA(d.done, B)
-  BA(d.solved, B) BA(d.qacc, (size_t)B * nv) BA(d.tenlen, (size_t)B * nu) BA(d.actforce, (size_t)B * nu) BA(d.sitexpos, (size_t)B * 24)
-  BA(d.flags, B) BA(d.diag, (size_t)B * 8) BA(d.elapsed, B) BA(d.episode, B) BA(d.mprw, (size_t)B * 64)
-  BA(b->d_tlo, b->ntarget_alloc) BA(b->d_thi, b->ntarget_alloc) BA(b->d_init, nq) BA(b->d_jlo, nv) BA(b->d_jhi, nv) BA(b->d_rnd, 4 * (size_t)nq)
-  BA(b->d_action, (size_t)B * nu)
-  BA(d.fatigue, (size_t)B * 3 * nu)
-  d.hfield = nullptr; d.gsize = nullptr; d.gsize_cg = -1;
-  d.sens = nullptr; d.cfrc = nullptr; d.ntouch = 0;
-  d.ovf = nullptr; d.ovf_cand = nullptr; d.ovf_row = 0; d.ovf_rows = 0; d.linkx = nullptr; d.track = nullptr; d.env_offset = 0;
-  if (m->trk) { BA(d.linkx, (size_t)B * 12 * m->dm.nl) }
-  if (m->wave_ok) {   // contact-table overflow rows of the wave kernel (instantiations <24,8,...> and <36,20,...>)
-    const int kc = m->wave_cfg == 0 ? 8 : 20, nj = m->trk ? 4 : 3;
-    d.ovf_row = 8 + nj * kc + (kc + 3) / 4 + (m->trk ? TRK_STATE : 0);
-    d.ovf_rows = m->trk ? NCX2 : NCX;
-    BA(d.ovf, (size_t)B * d.ovf_rows * d.ovf_row) BA(d.ovf_cand, (size_t)B * NCANDX)
-  }
-  if (m->dw.hf.on) { BA(d.hfield, (size_t)B * m->dw.hf.nrow * m->dw.hf.ncol) }   // zero-filled: flat terrain at the geom's height
-  BA(b->d_initv, nv) BA(b->d_init2, nq) BA(b->d_initv2, nv) BA(b->d_fatvec, nu)
-  { void* pw = nullptr; if ((rc = balloc(b, &pw, sizeof(DevWalk)))) { myo_batch_free(b); return rc; } b->d_walk = (DevWalk*)pw; }
-  BA(b->d_stamps, (size_t)B * 12 * 3 * 2)      // 3 x 12 long long per workgroup (diagnostic build)
-  BA(b->d_order, B)
-  b->sched_stride = (B + 7) / 8 + 1;                 // per queue with 8 queues; launch_step widens it when the device shows fewer XCDs
-  BA(b->d_sched, 32 + B + 64)
-#undef BA
-  if (const char* e = getenv("MYO_LANES")) { int g = atoi(e); if (g == 16 || g == 32 || g == 64) g_lanes = g; }
-  HIPCHK(hipMemcpy(b->d_jlo, m->jnt_lo.data(), nv * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(b->d_jhi, m->jnt_hi.data(), nv * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(b->d_init, m->qpos0.data(), nq * 4, hipMemcpyHostToDevice));
-  // default: every env at qpos0
-  std::vector<float> q((size_t)B * nq);
-  for (int e = 0; e < B; e++) memcpy(&q[(size_t)e * nq], m->qpos0.data(), nq * 4);
-  HIPCHK(hipMemcpy(d.qpos, q.data(), q.size() * 4, hipMemcpyHostToDevice));
-  {
-    std::vector<float> f((size_t)B * 3 * nu, 0.f);
-    for (int e = 0; e < B; e++) for (int i = 0; i < nu; i++) f[(size_t)e * 3 * nu + nu + i] = 1.f;      // MR = 1
-    HIPCHK(hipMemcpy(d.fatigue, f.data(), f.size() * 4, hipMemcpyHostToDevice));
-    d.fat_dt = m->dm.timestep; d.reaf_epl = d.reaf_eip = -1;
-  }
-  b->task.task = MYO_TASK_NONE; b->task.frame_skip = 1; b->task.obs_dim = 0; b->task.ntarget = 0;
-  b->task.jnt_lo = b->d_jlo; b->task.jnt_hi = b->d_jhi; b->task.init_qpos = b->d_init; b->task.target_lo = b->d_tlo; b->task.target_hi = b->d_thi;
-  b->task.init_qvel = nullptr;
-  b->task.init_qpos_alt = nullptr; b->task.init_qvel_alt = nullptr; b->task.reset_noise_std = 0.f; b->task.fatigue_mode = 0; b->task.fatigue_vec = nullptr;
-  HIPCHK(hipEventCreate(&b->ev0));
-  HIPCHK(hipEventCreate(&b->ev1));
-  *out = b;
-  return MYO_OK;
-}
-
-void myo_batch_free(myo_batch* b) {
-  if (!b) return;
-  for (hipEvent_t e : b->kev) (void)hipEventDestroy(e);
-  for (void* p : b->dev_allocs) (void)hipFree(p);
-  if (b->ev0) (void)hipEventDestroy(b->ev0);
-  if (b->ev1) (void)hipEventDestroy(b->ev1);
-  delete b;
-}
+// batches, per-env fields and overrides: myo_host_batch.h
+int myo_batch_create(const myo_model* m, int B, myo_batch** out) { return m && out && B > 0 ? batch_create(m, B, out) : fail(MYO_E_ARG, "myo_batch_create: bad arguments"); }
+void myo_batch_free(myo_batch* b) { batch_free(b); }
+int myo_batch_enable_sensors(myo_batch* b) { return b ? enable_sensors(b) : fail(MYO_E_ARG, "myo_batch_enable_sensors: null"); }
+int myo_batch_field(myo_batch* b, int field, void** p, size_t* pitch, size_t* width) { return b && p && pitch && width ? batch_field(b, field, p, pitch, width) : fail(MYO_E_ARG, "myo_batch_field: null"); }
+int myo_batch_read(myo_batch* b, int field, void* host, size_t nbytes) { return b && host ? batch_read(b, field, host, nbytes) : fail(MYO_E_ARG, "myo_batch_read: null"); }
+int myo_batch_write(myo_batch* b, int field, const void* host, size_t nbytes) { return b && host ? batch_write(b, field, host, nbytes) : fail(MYO_E_ARG, "myo_batch_write: null"); }
 
 int myo_batch_size(const myo_batch* b) { return b ? b->db.B : 0; }
 
-static int set_quat_body(myo_batch* b, int body);   // (below, with the rest of MYO_F_BODYQUAT)
 static const TaskHooks* task_hooks(int task);       // (below, after the launches the hooks make)
 
 int myo_batch_configure(myo_batch* b, const myo_task_config* c) {
@@ -335,290 +268,6 @@ int myo_batch_configure_track(myo_batch* b, const myo_track_config* c) {
   T.task = MYO_TASK_TRACK; T.frame_skip = c->n_frames; T.nq = nq; T.obs_dim = obs_dim;
   HIPCHK(hipMemcpy(b->d_init, c->init_qpos, (size_t)nq * 4, hipMemcpyHostToDevice));
   T.init_qpos = b->d_init; T.jnt_lo = b->d_jlo; T.jnt_hi = b->d_jhi; T.target_lo = b->d_tlo; T.target_hi = b->d_thi;
-  return MYO_OK;
-}
-
-// per-env body-mass override (MYO_F_BODYMASS / MYO_F_BODYMASS_RANGE): the refusals, shared by its start and the launches after it
-static int bm_check(const myo_batch* b) {
-  const myo_model* m = b->model;
-  if (m->rk4) return fail(MYO_E_UNSUPPORTED, "per-env body masses: RK4 models are not supported");
-  if (m->trk) return fail(MYO_E_UNSUPPORTED, "per-env body masses: models of the TrackEnv class are not supported");
-  if (m->dw.hf.on) return fail(MYO_E_UNSUPPORTED, "per-env body masses: height-field models are not supported");
-  if (!m->wave_ok || g_lanes != 64) return fail(MYO_E_UNSUPPORTED, "per-env body masses: wave-per-env kernel only (lanes = 64)");
-  const int t = b->task.task;
-  if (t == MYO_TASK_WALK || t == MYO_TASK_STAND || t == MYO_TASK_TRACK)
-    return fail(MYO_E_UNSUPPORTED, "per-env body masses: the walk / stand / track tasks use model-wide mass totals");
-  if (m->body_mass0.empty() || !m->d_lm_adr) return fail(MYO_E_UNSUPPORTED, "per-env body masses: the model blob lacks the body tables");
-  return MYO_OK;
-}
-
-static int bm_start(myo_batch* b) {
-  if (b->bm_on) return MYO_OK;
-  int rc = bm_check(b);
-  if (rc) return rc;
-  const myo_model* m = b->model;
-  DevBatch& d = b->db;
-  const int nb = (int)m->body_mass0.size();
-  float *bm = nullptr, *br = nullptr, *lc = nullptr;
-  if ((rc = balloc(b, (void**)&bm, (size_t)d.B * nb * 4)) || (rc = balloc(b, (void**)&br, (size_t)d.B * 2 * nb * 4)) ||
-      (rc = balloc(b, (void**)&lc, (size_t)d.B * m->dm.nl * 10 * 4))) return rc;
-  std::vector<float> v((size_t)d.B * nb);
-  for (int e = 0; e < d.B; e++) memcpy(&v[(size_t)e * nb], m->body_mass0.data(), nb * 4);
-  HIPCHK(hipSetDevice(m->device));
-  HIPCHK(hipMemcpy(bm, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-  d.bmass = bm; d.bmass_range = br; d.linkc = lc; d.nbody = nb;
-  b->bm_on = true;
-  return MYO_OK;
-}
-
-// per-env root-body offset (MYO_F_BODYPOS / MYO_F_BODYPOS_RANGE): TrackEnv-class models whose last joint sits on a root body only
-static int bp_check(const myo_batch* b) {
-  const myo_model* m = b->model;
-  if (!(m->wave_ok && m->trk)) return fail(MYO_E_UNSUPPORTED, "per-env body position: models of the TrackEnv class only");
-  if (m->bp_link < 0) return fail(MYO_E_UNSUPPORTED, "per-env body position: the body of the model's last joint is not a root body (a child of the world heading its link)");
-  return MYO_OK;
-}
-
-static int bp_start(myo_batch* b) {
-  if (b->bp_on) return MYO_OK;
-  int rc = bp_check(b);
-  if (rc) return rc;
-  DevBatch& d = b->db;
-  float *bp = nullptr, *br = nullptr;
-  HIPCHK(hipSetDevice(b->model->device));
-  if ((rc = balloc(b, (void**)&bp, (size_t)d.B * 3 * 4)) || (rc = balloc(b, (void**)&br, (size_t)d.B * 6 * 4))) return rc;   // zero: no offset
-  d.bpos = bp; d.bpos_range = br; d.bpos_link = b->model->bp_link;
-  b->bp_on = true;
-  return MYO_OK;
-}
-
-// per-env orientation of one world-welded body (MYO_F_BODYQUAT / MYO_F_BODYQUAT_RANGE): TrackEnv-class models, the body selected first
-// (myo_task_config.quat_body)
-static int set_quat_body(myo_batch* b, int body) {
-  const myo_model* m = b->model;
-  if (!(m->wave_ok && m->trk)) return fail(MYO_E_UNSUPPORTED, "per-env body orientation: models of the TrackEnv class only");
-  if (body <= 0 || body >= (int)m->body_parent.size()) return fail(MYO_E_ARG, "quat_body: body id out of range");
-  if (m->body_parent[body] != 0 || m->body_jntnum[body] != 0) return fail(MYO_E_UNSUPPORTED, "per-env body orientation: a jointless child of the world only");
-  if (b->bq_on && body != b->bq_body) return fail(MYO_E_ARG, "quat_body: the orientation of another body has started");
-  b->bq_body = body;
-  return MYO_OK;
-}
-
-static int bq_check(const myo_batch* b) {
-  const myo_model* m = b->model;
-  if (!(m->wave_ok && m->trk)) return fail(MYO_E_UNSUPPORTED, "per-env body orientation: models of the TrackEnv class only");
-  if (b->bq_body < 0) return fail(MYO_E_ARG, "per-env body orientation: no body selected (myo_task_config.quat_body)");
-  return MYO_OK;
-}
-
-static int bq_start(myo_batch* b) {
-  if (b->bq_on) return MYO_OK;
-  int rc = bq_check(b);
-  if (rc) return rc;
-  const myo_model* m = b->model;
-  DevBatch& d = b->db;
-  const int bd = b->bq_body, ncg = m->dm.ncg, ns = m->dims.nsite;
-  std::vector<float> q((size_t)d.B * 4), c(12);
-  double R0[9];
-  quat2mat_d(R0, &m->body_quat0[4 * (size_t)bd]);
-  for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) c[3 * i + j] = (float)R0[3 * j + i];   // R(q0)^T
-  for (int k = 0; k < 3; k++) c[9 + k] = (float)(m->body_pos0[3 * (size_t)bd + k] - m->dm.origin[k]);   // (lowered coordinates)
-  for (int e = 0; e < d.B; e++) for (int k = 0; k < 4; k++) q[4 * (size_t)e + k] = (float)m->body_quat0[4 * (size_t)bd + k];
-  std::vector<int> fl((size_t)ncg + ns, 0);
-  for (int g = 0; g < ncg; g++) fl[g] = m->cg_body[g] == bd;
-  for (int s2 = 0; s2 < ns; s2++) fl[ncg + s2] = m->site_body[s2] == bd;
-  float *bq = nullptr, *br = nullptr, *bc = nullptr;
-  int* bf = nullptr;
-  HIPCHK(hipSetDevice(m->device));
-  if ((rc = balloc(b, (void**)&bq, (size_t)d.B * 4 * 4)) || (rc = balloc(b, (void**)&br, (size_t)d.B * 6 * 4)) ||
-      (rc = balloc(b, (void**)&bc, 12 * 4)) || (rc = balloc(b, (void**)&bf, fl.size() * 4))) return rc;
-  HIPCHK(hipMemcpy(bq, q.data(), q.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(bc, c.data(), c.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(bf, fl.data(), fl.size() * 4, hipMemcpyHostToDevice));
-  d.bquat = bq; d.bquat_range = br; d.bq_c = bc; d.bq_flag = bf;
-  b->bq_on = true;
-  return MYO_OK;
-}
-
-// touch sensors and contact forces (MYO_F_SENSORDATA / MYO_F_CFRC): the refusals, shared by the start and the launches after it.  Host
-// side only: a refused model never reaches the GPU
-static int sens_check(const myo_batch* b) {
-  const myo_model* m = b->model;
-  if (m->dw.ntouch <= 0) return fail(MYO_E_UNSUPPORTED, "sensors: the model blob has no touch sensors (no hip_touch table)");
-  if (m->rk4) return fail(MYO_E_UNSUPPORTED, "sensors: RK4 models are not supported");
-  if (m->trk) return fail(MYO_E_UNSUPPORTED, "sensors: models of the TrackEnv class are not supported");
-  if (!m->wave_ok || m->wave_cfg != 1) return fail(MYO_E_UNSUPPORTED, "sensors: models of the hand class (24-dof step kernels) are not supported");
-  if (g_lanes != 64) return fail(MYO_E_UNSUPPORTED, "sensors: wave-per-env kernel only (lanes = 64)");
-  return MYO_OK;
-}
-
-int myo_batch_enable_sensors(myo_batch* b) {
-  if (!b) return fail(MYO_E_ARG, "myo_batch_enable_sensors: null");
-  int rc = sens_check(b);
-  if (rc) return rc;
-  if (b->sens_on) return MYO_OK;
-  DevBatch& d = b->db;
-  const int n = b->model->dw.ntouch;
-  float *sd = nullptr, *cf = nullptr;
-  HIPCHK(hipSetDevice(b->model->device));
-  if ((rc = balloc(b, (void**)&sd, (size_t)d.B * n * 4)) || (rc = balloc(b, (void**)&cf, (size_t)d.B * 3 * (n + 1) * 4))) return rc;
-  d.sens = sd; d.cfrc = cf; d.ntouch = n;
-  b->sens_on = true;
-  return MYO_OK;
-}
-
-static int field_info(myo_batch* b, int f, void** p, size_t* pitch, size_t* width) {
-  const DevModel& dm = b->model->dm;
-  DevBatch& d = b->db;
-  size_t nv = dm.nv, nu = dm.nu;
-  switch (f) {
-    case MYO_F_QPOS: *p = d.qpos; *pitch = *width = (size_t)b->model->nq; break;
-    case MYO_F_QVEL: *p = d.qvel; *pitch = *width = nv; break;
-    case MYO_F_ACT: *p = d.act; *pitch = *width = nu; break;
-    case MYO_F_CTRL: *p = d.ctrl; *pitch = *width = nu; break;
-    case MYO_F_WARMSTART: *p = d.warm; *pitch = *width = nv; break;
-    case MYO_F_TIME: *p = d.time; *pitch = *width = 1; break;
-    case MYO_F_TARGET: *p = d.target; *pitch = *width = b->task.ntarget > 0 ? b->task.ntarget : 1; break;
-    case MYO_F_OBS: *p = d.obs; *pitch = *width = b->task.obs_dim > 0 ? b->task.obs_dim : 1; break;
-    case MYO_F_REWARD: *p = d.reward; *pitch = *width = 1; break;
-    case MYO_F_DONE: *p = d.done; *pitch = *width = 1; break;
-    case MYO_F_SOLVED: *p = d.solved; *pitch = *width = 1; break;
-    case MYO_F_FLAGS: *p = d.flags; *pitch = *width = 1; break;
-    case MYO_F_DIAG: *p = d.diag; *pitch = *width = 8; break;
-    case MYO_F_QACC: *p = d.qacc; *pitch = *width = nv; break;
-    case MYO_F_TENLEN: *p = d.tenlen; *pitch = *width = nu; break;
-    case MYO_F_ACTFORCE: *p = d.actforce; *pitch = *width = nu; break;
-    case MYO_F_ELAPSED: *p = d.elapsed; *pitch = *width = 1; break;
-    case MYO_F_LINKX:
-      if (!d.linkx) return fail(MYO_E_ARG, "MYO_F_LINKX: this model's kernel does not export link frames");
-      *p = d.linkx; *pitch = *width = (size_t)12 * b->model->dm.nl; break;
-    case MYO_F_ACTION: *p = b->d_action; *pitch = *width = nu; break;
-    case MYO_F_FATIGUE: *p = d.fatigue; *pitch = *width = 3 * nu; break;
-    case MYO_F_GEOMSIZE:
-      if (!d.gsize) return fail(MYO_E_ARG, "MYO_F_GEOMSIZE: no geom override set (myo_batch_set_geom_override)");
-      *p = d.gsize; *pitch = *width = 4; break;
-    case MYO_F_HFIELD:
-      if (!d.hfield) return fail(MYO_E_ARG, "MYO_F_HFIELD: the model has no colliding height field");
-      *p = d.hfield; *pitch = *width = b->model->dw.hf.nrow * b->model->dw.hf.ncol; break;
-    case MYO_F_METRICS:
-      if (!b->d_metrics) return fail(MYO_E_ARG, "MYO_F_METRICS: the track task is not configured (myo_batch_configure_track)");
-      *p = b->d_metrics; *pitch = *width = 4; break;
-    case MYO_F_SITEXPOS: *p = d.sitexpos; *pitch = *width = b->task.ntip > 0 ? 3 * b->task.ntip : 1; break;
-    case MYO_F_BODYMASS:
-    case MYO_F_BODYMASS_RANGE: {   // (callers start the override first; before that the pointer is NULL)
-      const size_t nb = b->model->body_mass0.size();
-      *p = f == MYO_F_BODYMASS ? (void*)d.bmass : (void*)d.bmass_range;
-      *pitch = *width = f == MYO_F_BODYMASS ? nb : 2 * nb;
-      break;
-    }
-    case MYO_F_BODYPOS: *p = d.bpos; *pitch = *width = 3; break;          // (NULL until the offset is started)
-    case MYO_F_BODYPOS_RANGE: *p = d.bpos_range; *pitch = *width = 6; break;
-    case MYO_F_BODYQUAT: *p = d.bquat; *pitch = *width = 4; break;         // (NULL until the orientation is started)
-    case MYO_F_BODYQUAT_RANGE: *p = d.bquat_range; *pitch = *width = 6; break;
-    case MYO_F_SENSORDATA:
-    case MYO_F_CFRC:
-      if (!b->sens_on) return fail(MYO_E_ARG, "MYO_F_SENSORDATA / MYO_F_CFRC: sensors are not enabled (myo_batch_enable_sensors)");
-      *p = f == MYO_F_SENSORDATA ? d.sens : d.cfrc;
-      *pitch = *width = f == MYO_F_SENSORDATA ? (size_t)d.ntouch : (size_t)3 * (d.ntouch + 1);
-      break;
-    default: return fail(MYO_E_ARG, "unknown field");
-  }
-  return MYO_OK;
-}
-
-int myo_batch_field(myo_batch* b, int field, void** dev_ptr, size_t* pitch, size_t* width) {
-  if (!b || !dev_ptr || !pitch || !width) return fail(MYO_E_ARG, "myo_batch_field: null");
-  if (field == MYO_F_BODYMASS || field == MYO_F_BODYMASS_RANGE) { int rc = bm_start(b); if (rc) return rc; }
-  if (field == MYO_F_BODYPOS || field == MYO_F_BODYPOS_RANGE) { int rc = bp_start(b); if (rc) return rc; }
-  if (field == MYO_F_BODYQUAT || field == MYO_F_BODYQUAT_RANGE) { int rc = bq_start(b); if (rc) return rc; }
-  return field_info(b, field, dev_ptr, pitch, width);
-}
-
-int myo_batch_read(myo_batch* b, int field, void* host, size_t nbytes) {
-  void* p; size_t pitch, width;
-  if (!b || !host) return fail(MYO_E_ARG, "myo_batch_read: null");
-  int rc = field_info(b, field, &p, &pitch, &width);
-  if (rc) return rc;
-  if (nbytes != (size_t)b->db.B * width * 4) return fail(MYO_E_ARG, "myo_batch_read: size mismatch");
-  if ((field == MYO_F_BODYMASS || field == MYO_F_BODYMASS_RANGE) && !b->bm_on) {   // not started: the model's masses, empty ranges
-    const std::vector<float>& m0 = b->model->body_mass0;
-    if (m0.empty()) return fail(MYO_E_UNSUPPORTED, "per-env body masses: the model blob lacks the body tables");
-    float* h = (float*)host;
-    for (int e = 0; e < b->db.B; e++) {
-      if (field == MYO_F_BODYMASS) memcpy(h + (size_t)e * width, m0.data(), width * 4);
-      else memset(h + (size_t)e * width, 0, width * 4);
-    }
-    return MYO_OK;
-  }
-  if ((field == MYO_F_BODYPOS || field == MYO_F_BODYPOS_RANGE) && !b->bp_on) {   // not started: no offsets, empty ranges
-    if ((rc = bp_check(b))) return rc;
-    memset(host, 0, nbytes);
-    return MYO_OK;
-  }
-  if ((field == MYO_F_BODYQUAT || field == MYO_F_BODYQUAT_RANGE) && !b->bq_on) {   // not started: the compiled quaternion, empty ranges
-    if ((rc = bq_check(b))) return rc;
-    float* h = (float*)host;
-    for (int e = 0; e < b->db.B; e++)
-      for (size_t k = 0; k < width; k++) h[(size_t)e * width + k] = field == MYO_F_BODYQUAT ? (float)b->model->body_quat0[4 * (size_t)b->bq_body + k] : 0.f;
-    return MYO_OK;
-  }
-  HIPCHK(hipSetDevice(b->model->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(host, p, nbytes, hipMemcpyDeviceToHost));
-  return MYO_OK;
-}
-
-int myo_batch_write(myo_batch* b, int field, const void* host, size_t nbytes) {
-  void* p; size_t pitch, width;
-  if (!b || !host) return fail(MYO_E_ARG, "myo_batch_write: null");
-  if (field == MYO_F_SENSORDATA || field == MYO_F_CFRC) return fail(MYO_E_ARG, "MYO_F_SENSORDATA / MYO_F_CFRC are read-only");
-  int rc = field_info(b, field, &p, &pitch, &width);
-  if (rc) return rc;
-  if (nbytes != (size_t)b->db.B * width * 4) return fail(MYO_E_ARG, "myo_batch_write: size mismatch");
-  if (field == MYO_F_BODYMASS || field == MYO_F_BODYMASS_RANGE) {
-    if (b->model->body_mass0.empty()) return fail(MYO_E_UNSUPPORTED, "per-env body masses: the model blob lacks the body tables");
-    const float* h = (const float*)host;
-    const size_t nb = b->model->body_mass0.size();
-    for (int e = 0; e < b->db.B; e++)
-      for (size_t i = 0; i < nb; i++) {
-        if (field == MYO_F_BODYMASS) { if (!(h[e * nb + i] >= 0.f)) return fail(MYO_E_ARG, "MYO_F_BODYMASS: masses must be >= 0"); }
-        else {
-          const float lo = h[2 * e * nb + i], hi = h[2 * e * nb + nb + i];
-          if (!(lo >= 0.f) || !(hi >= lo)) return fail(MYO_E_ARG, "MYO_F_BODYMASS_RANGE: need 0 <= lo <= hi");
-        }
-      }
-    if ((rc = bm_start(b))) return rc;
-    if ((rc = field_info(b, field, &p, &pitch, &width))) return rc;
-  }
-  if (field == MYO_F_BODYPOS || field == MYO_F_BODYPOS_RANGE) {
-    if ((rc = bp_check(b))) return rc;
-    const float* h = (const float*)host;
-    for (size_t i = 0; i < (size_t)b->db.B * width; i++) if (!std::isfinite(h[i])) return fail(MYO_E_ARG, "MYO_F_BODYPOS / MYO_F_BODYPOS_RANGE: values must be finite");
-    if (field == MYO_F_BODYPOS_RANGE)
-      for (int e = 0; e < b->db.B; e++)
-        for (int k = 0; k < 3; k++) if (!(h[6 * e + 3 + k] >= h[6 * e + k])) return fail(MYO_E_ARG, "MYO_F_BODYPOS_RANGE: need lo <= hi");
-    if ((rc = bp_start(b))) return rc;
-    if ((rc = field_info(b, field, &p, &pitch, &width))) return rc;
-  }
-  if (field == MYO_F_BODYQUAT || field == MYO_F_BODYQUAT_RANGE) {
-    if ((rc = bq_check(b))) return rc;
-    const float* h = (const float*)host;
-    for (size_t i = 0; i < (size_t)b->db.B * width; i++) if (!std::isfinite(h[i])) return fail(MYO_E_ARG, "MYO_F_BODYQUAT / MYO_F_BODYQUAT_RANGE: values must be finite");
-    for (int e = 0; e < b->db.B; e++) {
-      const float* r = h + (size_t)e * width;
-      if (field == MYO_F_BODYQUAT) {
-        const double n = std::sqrt((double)r[0] * r[0] + (double)r[1] * r[1] + (double)r[2] * r[2] + (double)r[3] * r[3]);
-        if (!(std::fabs(n - 1.0) <= 1e-4)) return fail(MYO_E_ARG, "MYO_F_BODYQUAT: quaternions must have norm 1");
-      } else {
-        for (int k = 0; k < 3; k++) if (!(r[3 + k] >= r[k])) return fail(MYO_E_ARG, "MYO_F_BODYQUAT_RANGE: need lo <= hi");
-      }
-    }
-    if ((rc = bq_start(b))) return rc;
-    if ((rc = field_info(b, field, &p, &pitch, &width))) return rc;
-  }
-  HIPCHK(hipSetDevice(b->model->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(p, host, nbytes, hipMemcpyHostToDevice));
   return MYO_OK;
 }
 

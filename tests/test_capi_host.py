@@ -29,6 +29,41 @@ def test_library_exports_every_declared_symbol(lib_path):
     assert not missing, missing
 
 
+def _header_enums(hdr):
+    """{name: value} of every enumerator of include/myo_hip.h: comments stripped, each `enum { ... }` body evaluated in order (an enumerator
+    is `NAME`, `NAME = <int>` or `NAME = <expression over earlier names>`)."""
+    values = {}
+    for body in re.findall(r"\benum\b[^{;]*\{([^}]*)\}", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)):
+        nxt = 0
+        for item in filter(None, (x.strip() for x in body.split(","))):
+            name, _, expr = (x.strip() for x in item.partition("="))
+            assert re.fullmatch(r"[A-Z][A-Z0-9_]*", name) and name not in values, item
+            values[name] = eval(expr, {"__builtins__": {}}, dict(values)) if expr else nxt
+            nxt = values[name] + 1
+    return values
+
+
+def test_capi_constants_equal_the_header_enums():
+    """Every MYO_F_* / MYO_TASK_* / MYO_FLAG_* / MYO_ACTMAP_* value of the header is the capi constant of the same name, and INT_FIELDS is
+    the set of fields whose header comment starts `[B][n] int32`."""
+    from myosuite_mjx_amd import capi
+    hdr = open(os.path.join(ROOT, "include", "myo_hip.h")).read()
+    enums = _header_enums(hdr)
+    assert enums["MYO_F_QPOS"] == 0 and enums["MYO_F_BODYPOS"] == enums["MYO_F_COUNT"] and enums["MYO_TASK_HOLD"] == 4    # (the parser parses)
+    checked = {n: v for n, v in enums.items() if n.startswith(("MYO_F_", "MYO_TASK_", "MYO_FLAG_", "MYO_ACTMAP_"))}
+    for prefix, known in (("MYO_F_", "MYO_F_CFRC"), ("MYO_TASK_", "MYO_TASK_DIE"), ("MYO_FLAG_", "MYO_FLAG_SCHED_TIMEOUT"), ("MYO_ACTMAP_", "MYO_ACTMAP_CTRLRANGE")):
+        assert known in checked and sum(n.startswith(prefix) for n in checked) >= 5      # every family was found
+    wrong = {n: (v, getattr(capi, n[4:], None)) for n, v in checked.items() if getattr(capi, n[4:], None) != v}
+    assert not wrong, wrong
+    extra = [n for n in dir(capi) if n.startswith(("F_", "TASK_", "FLAG_", "ACTMAP_")) and "MYO_" + n not in checked]
+    assert not extra, extra                                                      # and capi names no id the header lacks
+    fields = sorted(v for n, v in checked.items() if n.startswith("MYO_F_") and n != "MYO_F_COUNT")
+    assert fields == list(range(enums["MYO_F_CFRC"] + 1))                       # the ids are dense: the library's field table has one row each
+    documented = re.findall(r"\b(MYO_F_[A-Z_]+)\b[^,/]*,?\s*/\*\s*\[B\]\[[^\]]*\]\s*(int32)?", hdr)
+    assert sorted(enums[n] for n, _ in documented) == fields                   # every field's comment was found, MYO_F_CFRC's included
+    assert sorted(capi.INT_FIELDS) == sorted(enums[n] for n, i32 in documented if i32) and capi.F_FLAGS in capi.INT_FIELDS
+
+
 def test_error_convention_without_gpu(lib_path, hand):
     """Bad arguments return negative codes with a message; without a GPU model upload raises (no silent fallback)."""
     import torch

@@ -1,17 +1,16 @@
 """CPU tests for myoChallengeBaodingP1-v1 (envs/myo/myochallenge/baoding_v1.py): registry entries and variants, P2 and its per-env ball
-kwargs refused, the committed myohand_baoding fixture and its TrackEnv-class lowering (two free joints, plane - sphere pairs), every other
-committed asset lowered to the same bytes, the appended ABI ids, the targets' body -> link transform, and the float64 restatement of the
+kwargs refused, the committed myohand_baoding fixture and its TrackEnv-class lowering (two free joints, plane - sphere pairs), the
+targets' body -> link transform, and the float64 restatement of the
 task (tests/baoding_ref.py) against the reference's goal trajectory and on oracle states."""
-import glob
 import os
-import re
 
 import numpy as np
 import pytest
 
+import hand_task_checks as H
 from baoding_ref import CENTER, DT, baoding_restate, goal_trajectory, target_xy
+from hand_task_checks import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IDS = ("myoChallengeBaodingP1-v1", "myoSarcChallengeBaodingP1-v1", "myoFatiChallengeBaodingP1-v1")
 P2 = ("myoChallengeBaodingP2-v1", "myoSarcChallengeBaodingP2-v1", "myoFatiChallengeBaodingP2-v1")
 SITES = ("ball1_site", "ball2_site", "target1_site", "target2_site")
@@ -39,10 +38,8 @@ def test_registry_entries_and_variants():
     assert s["drop_th"] == 1.25 and s["proximity_th"] == 0.015 and s["weights"] == dict(pos_dist_1=5.0, pos_dist_2=5.0)
     assert envs.REGISTRY[IDS[1]]["muscle_condition"] == "sarcopenia" and envs.REGISTRY[IDS[2]]["muscle_condition"] == "fatigue"
     assert "myoReafChallengeBaodingP1-v1" not in envs.REGISTRY               # the challenge registry has no Reaf variant
-    for i in P2:
-        assert i not in envs.REGISTRY and "size, mass and friction" in envs.UNSUPPORTED[i]
-        with pytest.raises(NotImplementedError, match="size, mass and friction"):
-            envs.make(i, num_envs=1)
+    H.muscle_variants(IDS[0], H.CONDITIONS[:2])
+    H.assert_p2_refused(P2)
 
 
 @pytest.mark.parametrize("kw", ["obj_size_range", "obj_mass_range", "obj_friction_change"])
@@ -95,36 +92,6 @@ def test_plane_sphere_and_plane_box_refusals(bd):
     a["geom_size"][g] = [0.02, 0.02, 0.02]
     with pytest.raises(NotImplementedError):
         lower(CompiledModel(arrays=a, names=bd.names))
-
-
-def test_every_committed_asset_lowers_to_the_same_bytes():
-    """All committed assets, the gzip-compressed MyoDM objects included: lowering their compiled arrays again (with several free joints
-    and plane - sphere pairs accepted now) reproduces the committed hip_* tables byte for byte."""
-    from myosuite_mjx_amd import model as M
-    from myosuite_mjx_amd.lowering import lower
-    from myosuite_mjx_amd.mjcf import CompiledModel
-    stems = sorted({re.sub(r"\.myob(\.gz)?$", "", os.path.basename(p)) for d in (M.ASSET_DIR, M.GOLDEN_DIR) for p in glob.glob(os.path.join(d, "*.myob*"))})
-    assert "myohand_baoding" in stems and "myohand_object_teapot" in stems and len(stems) >= 60
-    for stem in stems:
-        m = M.load_asset(stem)
-        cm = CompiledModel(arrays={k: np.array(v, copy=True) for k, v in m.arrays.items() if not k.startswith("hip_")}, names=m.names)
-        try:
-            lower(cm)
-        except NotImplementedError:
-            assert "hip_unsupported" in m.arrays, stem
-            continue
-        hip = {k: v for k, v in m.arrays.items() if k.startswith("hip_")}
-        assert sorted(k for k in cm.arrays if k.startswith("hip_")) == sorted(hip), stem
-        for k, v in hip.items():
-            a, b = np.asarray(cm.arrays[k]), np.asarray(v)
-            assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), (stem, k)
-
-
-def test_abi_task_id():
-    from myosuite_mjx_amd import capi
-    hdr = open(os.path.join(ROOT, "include", "myo_hip.h")).read()
-    assert "MYO_TASK_BAODING = 9" in hdr and capi.TASK_BAODING == 9
-    assert capi.TaskConfig._fields_[-1] == ("quat_body", capi.C.c_int)          # no field added to the config
 
 
 def test_goal_trajectory_matches_reference():

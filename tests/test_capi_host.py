@@ -64,6 +64,38 @@ def test_capi_constants_equal_the_header_enums():
     assert sorted(capi.INT_FIELDS) == sorted(enums[n] for n, i32 in documented if i32) and capi.F_FLAGS in capi.INT_FIELDS
 
 
+# capi name, value, and the text the header must spell it with (None: its place in a list gives the value).  Ids are appended, never
+# renumbered: a feature that adds a field or a task adds its row at the end of its block, and changes no other row.
+ABI_PINS = (
+    ("F_METRICS", 23, None), ("F_BODYMASS", 24, None), ("F_BODYMASS_RANGE", 25, None),           # the tail of the myo_field list proper
+    ("F_BODYPOS", 26, "MYO_F_BODYPOS = MYO_F_COUNT"), ("F_BODYPOS_RANGE", 27, None),             # ... the ids continue after MYO_F_COUNT
+    ("F_BODYQUAT", 28, "MYO_F_BODYQUAT = MYO_F_BODYPOS_RANGE + 1"), ("F_BODYQUAT_RANGE", 29, None),
+    ("TASK_HOLD", 4, None), ("TASK_STAND", 5, None), ("TASK_TRACK", 6, None),
+    ("TASK_KEYTURN", 7, "MYO_TASK_KEYTURN = 7"), ("TASK_PEN", 8, "MYO_TASK_PEN = 8"), ("TASK_BAODING", 9, "MYO_TASK_BAODING = 9"),
+    ("TASK_DIE", 10, "MYO_TASK_DIE = 10"),
+)
+
+
+def test_abi_numbering_is_append_only():
+    """The numbers a client compiled against an older header relies on: the myo_field list proper and its end, the field ids that continue
+    after MYO_F_COUNT, the task ids, and the layout of myo_task_config (new members go last).  Every per-feature ABI pin lives here."""
+    from myosuite_mjx_amd import capi
+    hdr = open(os.path.join(ROOT, "include", "myo_hip.h")).read()
+    plain = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    names = re.findall(r"^\s*(MYO_F_[A-Z_]+)", plain[plain.index("typedef enum myo_field"):plain.index("} myo_field;")], flags=re.M)
+    assert names[-3:] == ["MYO_F_BODYMASS", "MYO_F_BODYMASS_RANGE", "MYO_F_COUNT"] and len(names) == 27
+    assert names.index("MYO_F_METRICS") == 23 and names.index("MYO_F_BODYMASS") == 24 and names.index("MYO_F_BODYMASS_RANGE") == 25
+    ext = plain[plain.index("} myo_field;"):plain.index("MYO_FLAG_BAD_STATE")]
+    ext = re.findall(r"^\s*(MYO_F_[A-Z_]+(?: = MYO_F_COUNT)?)", ext, flags=re.M)
+    assert ext == ["MYO_F_BODYPOS = MYO_F_COUNT", "MYO_F_BODYPOS_RANGE"]          # the ids continue after the list
+    assert re.search(r"^\s*MYO_F_BODYQUAT_RANGE,", hdr, flags=re.M)
+    for name, value, text in ABI_PINS:
+        assert getattr(capi, name) == value, name
+        assert text is None or text in hdr, text
+    assert re.search(r"^\s*int quat_body;", hdr, flags=re.M) and capi.TaskConfig._fields_[-1] == ("quat_body", capi.C.c_int)
+    assert len(capi.TaskConfig._fields_) == 25
+
+
 def test_error_convention_without_gpu(lib_path, hand):
     """Bad arguments return negative codes with a message; without a GPU model upload raises (no silent fallback)."""
     import torch

@@ -1,21 +1,17 @@
 """CPU tests for myoChallengeDieReorient{Demo,P1}-v0 (envs/myo/myochallenge/reorient_v0.py): registry entries and variants, P2 and its
 per-env die kwargs refused, the committed myohand_die fixture and its TrackEnv-class lowering (nothing but the die's boxes puts it there),
-every other committed asset lowered to the same bytes, the box rule of lowering, the appended ABI id, the float64 restatement of the task
-(tests/reorient_ref.py: its mat2euler against the reference's, and on oracle states), the oracle rollouts the GPU tests draw their
-states from, and the register / scratch figures of the two new kernels."""
-import glob
+the box rule of lowering, the float64 restatement of the task (tests/reorient_ref.py: its mat2euler against the reference's, and on
+oracle states), and the oracle rollouts the GPU tests draw their states from."""
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import hand_task_checks as H
 from die_states import init_qpos, pick_states, rollout_states
+from hand_task_checks import ROOT
 from reorient_ref import SITES, euler2quat, euler_margin, mat2euler, reorient_restate, site_frames
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IDS = ("myoChallengeDieReorientDemo-v0", "myoChallengeDieReorientP1-v0")
 P2 = ("myoChallengeDieReorientP2-v0", "myoSarcChallengeDieReorientP2-v0", "myoFatiChallengeDieReorientP2-v0")
 DT = 0.01
@@ -43,14 +39,8 @@ def test_registry_entries_and_variants():
     assert d["pos_th"] == np.inf and d["goal_pos"] == (0.0, 0.0) and d["goal_rot"] == (-0.785, 0.785)
     assert p["pos_th"] == 0.025 and p["goal_pos"] == (-0.010, 0.010) and p["goal_rot"] == (-1.57, 1.57)
     for i in IDS:
-        for c, cond in (("Sarc", "sarcopenia"), ("Fati", "fatigue")):
-            v = envs.REGISTRY[i[:3] + c + i[3:]]
-            assert v["muscle_condition"] == cond and {k: x for k, x in v.items() if k != "muscle_condition"} == envs.REGISTRY[i]
-        assert i[:3] + "Reaf" + i[3:] not in envs.REGISTRY                     # the challenge registry has no Reaf variant
-    for i in P2:
-        assert i not in envs.REGISTRY and "size, mass and friction" in envs.UNSUPPORTED[i]
-        with pytest.raises(NotImplementedError, match="size, mass and friction"):
-            envs.make(i, num_envs=1)
+        H.muscle_variants(i, H.CONDITIONS[:2])                                 # the challenge registry has no Reaf variant
+    H.assert_p2_refused(P2)
 
 
 @pytest.mark.parametrize("kw,val", [("obj_size_change", 0.007), ("obj_mass_range", (0.05, 0.25)), ("obj_friction_change", (0.2, 0.001, 0.00002))])
@@ -89,29 +79,6 @@ def test_fixture_lowers_to_trk_through_its_boxes_alone(die):
     assert np.asarray(m.jnt_range)[-6:-3].tolist() == [[-0.25, 0.25]] * 3 and not np.asarray(m.jnt_limited)[-3:].any()
 
 
-def test_every_other_committed_asset_lowers_to_the_same_bytes():
-    """All committed assets and golden blobs: lowering their compiled arrays again, with boxes accepted unconditionally now, reproduces the
-    committed hip_* tables byte for byte (and what was refused before still is)."""
-    from myosuite_mjx_amd import model as M
-    from myosuite_mjx_amd.lowering import lower
-    from myosuite_mjx_amd.mjcf import CompiledModel
-    stems = sorted({re.sub(r"\.myob(\.gz)?$", "", os.path.basename(p)) for d in (M.ASSET_DIR, M.GOLDEN_DIR) for p in glob.glob(os.path.join(d, "*.myob*"))})
-    assert "myohand_die" in stems and "myohand_keyturn" in stems and "myohand_object_teapot" in stems and len(stems) >= 61
-    for stem in stems:
-        m = M.load_asset(stem)
-        cm = CompiledModel(arrays={k: np.array(v, copy=True) for k, v in m.arrays.items() if not k.startswith("hip_")}, names=m.names)
-        try:
-            lower(cm)
-        except NotImplementedError:
-            assert "hip_unsupported" in m.arrays, stem
-            continue
-        hip = {k: v for k, v in m.arrays.items() if k.startswith("hip_")}
-        assert sorted(k for k in cm.arrays if k.startswith("hip_")) == sorted(hip), stem
-        for k, v in hip.items():
-            a, b = np.asarray(cm.arrays[k]), np.asarray(v)
-            assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), (stem, k)
-
-
 def test_box_rule_of_lowering():
     """A model whose only TrackEnv-class feature is a box lowers (the key-turn model without its friction loss), and a plane against a
     moving box is still refused."""
@@ -131,15 +98,6 @@ def test_box_rule_of_lowering():
     a["geom_size"][g] = [0.02, 0.02, 0.02]
     with pytest.raises(NotImplementedError, match="cannot prune static geom 0 against moving geom|plane against a moving box"):
         lower(CompiledModel(arrays=a, names=bd.names))                              # the floor plane against a free box
-
-
-def test_abi_task_id():
-    from myosuite_mjx_amd import capi
-    hdr = open(os.path.join(ROOT, "include", "myo_hip.h")).read()
-    assert "MYO_TASK_DIE = 10" in hdr and capi.TASK_DIE == 10
-    assert (capi.TASK_KEYTURN, capi.TASK_PEN, capi.TASK_BAODING) == (7, 8, 9)
-    assert capi.TaskConfig._fields_[-1] == ("quat_body", capi.C.c_int)          # no field added to the config
-    assert len(capi.TaskConfig._fields_) == 25
 
 
 def test_mat2euler_matches_reference():
@@ -172,10 +130,7 @@ def test_restatement_on_oracle_states(die):
     assert np.abs(x[4] - x[0] - [-0.1, 0.0, 0.0]).max() < 1e-15                      # goal_obj_offset, at qpos0
     q = init_qpos(m)
     assert q[22] == 0 and np.array_equal(q[23:], m.qpos0[23:])                       # init_qpos[:-7] = 0 reaches the die's first slide
-    o.reset()
-    o.set_state(qpos=q)
-    o.forward()
-    x, Ro, Rt = _frames(o, m)
+    x, Ro, Rt = _frames(H.forward_at(o, q), m)
     rng = np.random.default_rng(0)
     act, v = rng.uniform(0, 1, (1, 39)), rng.normal(0, 1, (1, 29))
     obs, rew, done, solved = reorient_restate(q, v, act, x[0], x[4], Ro, Rt, DT)
@@ -189,10 +144,7 @@ def test_restatement_on_oracle_states(die):
     # the die moved 0.21 m away: done, not solved
     qq = q.copy()
     qq[-6] = 0.21
-    o.reset()
-    o.set_state(qpos=qq)
-    o.forward()
-    x, Ro, Rt = _frames(o, m)
+    x, Ro, Rt = _frames(H.forward_at(o, qq), m)
     obs, rew, done, solved = reorient_restate(qq, v, act, x[0], x[4], Ro, Rt, DT)
     assert done[0] and not solved[0] and np.isclose(np.linalg.norm(obs[0, 51:54]), 0.21) and rew[0] == pytest.approx(-21.0 - np.linalg.norm(obs[0, 60:63]))
     # the goal turned and moved (Model.with_body_quat / with_body_pos): the goal sites follow; the die turned onto it within rot_th: solved
@@ -206,11 +158,7 @@ def test_restatement_on_oracle_states(die):
         qq = q.copy()
         qq[-6:-3] = off
         qq[-3:] = dq * ang
-        om = Oracle(mm.blob())
-        om.reset()
-        om.set_state(qpos=qq)
-        om.forward()
-        x, Ro, Rt = _frames(om, mm)
+        x, Ro, Rt = _frames(H.forward_at(Oracle(mm.blob()), qq), mm)
         assert np.allclose(x[4], m.body_pos[tb] + off) and np.allclose(Rt, quat2mat(euler2quat(e)))
         obs, rew, done, solved = reorient_restate(qq, v, act, x[0], x[4], Ro, Rt, DT)
         assert np.allclose(obs[0, 57:60], e) and np.abs(obs[0, 51:54]).max() < 1e-12 and not done[0]
@@ -237,10 +185,7 @@ def test_oracle_rollouts_stay_inside_the_kernel_limits(die, rollouts):
     for ep in range(4):
         drop_at = None
         for k, s in enumerate(S[150 * ep:150 * (ep + 1)]):
-            o.reset()
-            o.set_state(qpos=s[0])
-            o.forward()
-            x, Ro, Rt = _frames(o, m)
+            x, Ro, Rt = _frames(H.forward_at(o, s[0]), m)
             cy, cut = euler_margin(Ro)
             left_out += bool(cy < 1e-3 or cut < 1e-3)
             if drop_at is None and reorient_restate(s[0], s[1], s[2], x[0], x[4], Ro, Rt, DT)[2][0]:
@@ -248,17 +193,3 @@ def test_oracle_rollouts_stay_inside_the_kernel_limits(die, rollouts):
         first_drop.append(drop_at)
     assert left_out <= 0.05 * len(S), left_out
     assert all(d is not None and 20 <= d <= 80 for d in first_drop), first_drop
-
-
-def test_new_kernels_have_no_spill_and_no_scratch():
-    """The two die kernels, read from the code object's metadata the way tests/test_kernel_resources.py reads the step kernels (that file
-    keys kernels by the demangled name up to the first parenthesis, which the function-pointer template argument of the task kernels
-    cuts short, so they are looked up by their mangled names here)."""
-    from myosuite_mjx_amd import capi
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources
-    rs = [r for r in kernel_resources.resources(capi.LIB_PATH) if "die_obs_body" in r["name"]]
-    names = sorted(subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip() for r in rs)
-    assert len(rs) == 2 and names[0].startswith("void task_obs_kernel<StateObs<&(die_obs_body(") and names[1].startswith("void task_post_kernel<StateObs<&(die_obs_body("), names
-    for r in rs:
-        assert r["vgpr_spill"] == 0 and r["scratch"] == 0 and r["vgpr"] + r["agpr"] <= 128, r

@@ -8,20 +8,15 @@ kernel: MyoHand + two free balls (two free joints in one model, plane - sphere p
     oracle on models whose target sites are moved as the reference moves them.
   * Reset draws over 4096 envs and two shards; the fused bench epilogue; the muscle-condition variants; refusals; the same file against the
     NaN-poisoned build."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+import hand_task_checks as H
 from baoding_ref import DT, baoding_restate, target_xy
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TRK = "step_kernel_w<36,20,32,2,2,false,0,false,true>"
 SITES = ("ball1_site", "ball2_site", "target1_site", "target2_site")
-IDS = ["myoChallengeBaodingP1-v1", "myoSarcChallengeBaodingP1-v1", "myoFatiChallengeBaodingP1-v1"]
+ID = "myoChallengeBaodingP1-v1"
 R = 0.022
 
 
@@ -42,6 +37,10 @@ def _configure(b, m, params=(np.pi / 4, 1.0, 0.025, 0.028, 5.0)):
     from myosuite_mjx_amd import capi
     b.configure(task=capi.TASK_BAODING, frame_skip=10, target_generate=1, target_lo=list(params), target_hi=list(params), init_qpos=_init_q(m),
                 tip_sites=[m.name2id("site", n) for n in SITES], pose_thd=0.015, far_th=1.25, w_pose=5.0, w_reach=5.0)
+
+
+CASE = H.TaskCase(stem="myohand_baoding", task="baoding", bench_id=ID, obs_dim=47, nsub=10, configure=_configure, extra_fields=("F_TARGET",),
+                  make_kwargs=dict(task_choice="random"), env_ids=(ID, "myoSarcChallengeBaodingP1-v1", "myoFatiChallengeBaodingP1-v1"))
 
 
 def _unit(rng, n):
@@ -94,10 +93,7 @@ def _states(m, kind, N, seed):
         else:               # free flight, spinning fast
             q[23:26], q[30:33] = [0.5, 0.5, 0.8], [0.6, 0.4, 0.9]
             v[26:29], v[32:35] = rng.normal(0, 20.0, (2, 3))
-        o.reset()
-        o.set_state(qpos=q)
-        o.forward()
-        pairs = {frozenset((int(c[7]), int(c[8]))) for c in o.contacts()}
+        pairs = {frozenset((int(c[7]), int(c[8]))) for c in H.forward_at(o, q).contacts()}
         balls = {p for p in pairs if g1 in p or g2 in p}
         if kind == "flight":
             if balls:
@@ -126,27 +122,19 @@ def test_contact_parity(bd, kind, nsub, tq, tv):
     q, v, tags = _states(m, kind, N, {"palm": 1, "ballball": 2, "pedestal": 3, "floor": 4, "flight": 5}[kind])
     rng = np.random.default_rng(9)
     act, ctrl = rng.uniform(0, 1, (N, m.nu)).astype(np.float32), rng.uniform(0, 1, (N, m.nu)).astype(np.float32)
-    b = capi.HipBatch(capi.HipModel(m.blob(), 0), N)
-    _configure(b, m)
-    for f, x in ((capi.F_QPOS, q), (capi.F_QVEL, v), (capi.F_ACT, act), (capi.F_CTRL, ctrl)):
-        b.write(f, x)
-    b.step(None, capi.ACTMAP_NONE, nsub)
-    assert b.last_kernel_name() == TRK
-    gq, gv, dg, fl = b.read(capi.F_QPOS), b.read(capi.F_QVEL), b.read(capi.F_DIAG), b.status()
+    b = H.new_batch(CASE, m, N)
     o = Oracle(m.blob())
-    eq, ev, nc = np.zeros(N), np.zeros(N), np.zeros(N, int)
     g1, g2 = m.name2id("geom", "ball1"), m.name2id("geom", "ball2")
     ball_con = np.zeros(N, int)
-    for e in range(N):
-        o.reset()
-        o.set_state(qpos=q[e], qvel=v[e], act=act[e], ctrl=ctrl[e])
-        assert o.step(nsub) == 0
-        oq = o.field("qpos")
-        eq[e], ev[e], nc[e] = np.abs(gq[e] - oq).max(), np.abs(gv[e] - o.field("qvel")).max(), o.ncon
-        ball_con[e] = sum(1 for c in o.contacts() if {int(c[7]), int(c[8])} & {g1, g2})
-        for a in (26, 33):                                            # both quaternions stay unit
-            assert abs(np.linalg.norm(gq[e, a:a + 4]) - 1) < 1e-5
-    same = (fl == 0) & (dg[:, 1] == nc)
+
+    def count_ball_contacts(e, oe):
+        ball_con[e] = sum(1 for c in oe.contacts() if {int(c[7]), int(c[8])} & {g1, g2})
+
+    eq, ev, nc, dg, fl, same = H.step_and_compare_with_oracle(m, b, {capi.F_QPOS: q, capi.F_QVEL: v, capi.F_ACT: act, capi.F_CTRL: ctrl}, nsub,
+                                                              lambda e: o, count_ball_contacts)
+    gq = b.read(capi.F_QPOS)
+    for a in (26, 33):                                                # both quaternions stay unit
+        assert np.abs(np.linalg.norm(gq[:, a:a + 4], axis=1) - 1).max() < 1e-5
     assert same.mean() > 0.8, (same.mean(), dg[:, 1].tolist(), nc.tolist())
     w = int(np.argmax(np.where(same, eq, 0)))
     assert eq[same].max() < tq and ev[same].max() < tv, (eq[same].max(), ev[same].max(), w, [sorted(p) for p in tags[w]], int(nc[w]))
@@ -168,8 +156,7 @@ def test_rollout_env_by_env(bd):
     q0 = np.tile(_init_q(m), (N, 1))
     q0[1:, 23:26] += rng.normal(0, 0.002, (N - 1, 3))
     q0 = q0.astype(np.float32)
-    b = capi.HipBatch(capi.HipModel(m.blob(), 0), N)
-    _configure(b, m)
+    b = H.new_batch(CASE, m, N)
     zero = np.zeros((N, m.nu), np.float32)
     for f, x in ((capi.F_QPOS, q0), (capi.F_QVEL, np.zeros((N, m.nv), np.float32)), (capi.F_ACT, zero), (capi.F_CTRL, zero)):
         b.write(f, x)
@@ -235,8 +222,7 @@ def test_sites_observation_and_restatement(bd):
     el[:4] = (0, 1, 2, 200)
     el[4:8] = (1, 2, 200, 1)
     q, v, params = q.astype(np.float32), v.astype(np.float32), params.astype(np.float32)
-    b = capi.HipBatch(capi.HipModel(m.blob(), 0), N)
-    _configure(b, m)
+    b = H.new_batch(CASE, m, N)
     for f, x in ((capi.F_QPOS, q), (capi.F_QVEL, v), (capi.F_TARGET, params), (capi.F_ELAPSED, el.astype(np.int32))):
         b.write(f, x)
     b.obs()
@@ -245,10 +231,7 @@ def test_sites_observation_and_restatement(bd):
     sid = [m.name2id("site", n) for n in SITES]
     for e in list(range(8)) + list(range(8, N, 32)):
         o = Oracle(_with_targets(m, target_xy(params[e].astype(np.float64), el[e])[0]))
-        o.reset()
-        o.set_state(qpos=q[e])
-        o.forward()
-        x = o.field("site_xpos").reshape(-1, 3)[sid].reshape(12)
+        x = H.forward_at(o, q[e]).field("site_xpos").reshape(-1, 3)[sid].reshape(12)
         assert np.abs(sx[e] - x).max() < 5e-6, (e, el[e], sx[e] - x)
     ro, rr, rd, rs = baoding_restate(q, v, sx, DT)
     assert np.abs(obs - ro).max() < 1e-5
@@ -270,15 +253,19 @@ def test_reset_draws_and_sharding():
     import myosuite_mjx_amd as myo
     from myosuite_mjx_amd import capi
     B = 4096
-    env = myo.make("myoChallengeBaodingP1-v1", num_envs=B, seed=7, as_torch=False, task_choice="random", goal_time_period=(4, 6),
-                   goal_xrange=(0.02, 0.03), goal_yrange=(0.022, 0.032))
+
+    def make_env(n, seed, off):
+        return myo.make(ID, num_envs=n, seed=seed, env_offset=off, as_torch=False, task_choice="random", goal_time_period=(4, 6),
+                        goal_xrange=(0.02, 0.03), goal_yrange=(0.022, 0.032))
+
+    env = make_env(B, H.SEED, 0)
     obs = env.reset()
     m = env.mjmodel
     assert np.array_equal(env.batch.read(capi.F_QPOS), np.tile(_init_q(m).astype(np.float32), (B, 1)))
     g = env.goal_params
     assert g.shape == (B, 5)
     assert g[:, 0].min() >= 0 and g[:, 0].max() < 2 * np.pi
-    assert np.abs(np.histogram(g[:, 0], bins=8, range=(0, 2 * np.pi))[0] - B / 8).max() < 5 * np.sqrt(B / 8)
+    H.assert_uniform(g[:, 0], 0, 2 * np.pi)
     assert set(np.unique(g[:, 1]).tolist()) == {-1.0, 0.0, 1.0}
     assert np.abs(np.bincount((g[:, 1] + 1).astype(int)) - B / 3).max() < 5 * np.sqrt(B / 3)
     for c, (a, z) in ((2, (0.02, 0.03)), (3, (0.022, 0.032)), (4, (4.0, 6.0))):
@@ -290,18 +277,8 @@ def test_reset_draws_and_sharding():
     d = np.linalg.norm(sx[:, 6:9] - sx[:, 9:12], axis=1)                   # the targets are opposite on the ellipse
     assert np.abs(d - 2 * np.hypot(g[:, 2] * np.cos(g[:, 0]), g[:, 3] * np.sin(g[:, 0]))).max() < 1e-5
     assert xy.shape == (B, 2, 2)
-    env2 = myo.make("myoChallengeBaodingP1-v1", num_envs=B, seed=7, as_torch=False, task_choice="random", goal_time_period=(4, 6),
-                    goal_xrange=(0.02, 0.03), goal_yrange=(0.022, 0.032))
-    env2.reset()
-    assert np.array_equal(env2.goal_params, g)
-    env2.reset(seed=8)
-    assert not np.array_equal(env2.goal_params, g)
-    for off in (0, B // 2):
-        s = myo.make("myoChallengeBaodingP1-v1", num_envs=B // 2, seed=7, env_offset=off, as_torch=False, task_choice="random",
-                     goal_time_period=(4, 6), goal_xrange=(0.02, 0.03), goal_yrange=(0.022, 0.032))
-        s.reset()
-        assert np.array_equal(s.goal_params, g[off:off + B // 2])
-    f = myo.make("myoChallengeBaodingP1-v1", num_envs=64, seed=7, as_torch=False)
+    H.assert_deterministic_and_sharded(make_env, lambda e: (e.goal_params,), B, (g,))
+    f = myo.make(ID, num_envs=64, seed=H.SEED, as_torch=False)
     f.reset()
     assert np.array_equal(f.goal_params, np.tile(np.array([np.pi / 4, 1, 0.025, 0.028, 5], np.float32), (64, 1)))
 
@@ -328,38 +305,12 @@ def test_targets_follow_the_goal_trajectory():
 
 
 def test_fused_bench_epilogue_equals_step_obs_autoreset():
-    import myosuite_mjx_amd as myo
-    from myosuite_mjx_amd import capi
-    B, seed, T = 512, 3, 5
-    envs = [myo.make("myoChallengeBaodingP1-v1", num_envs=B, seed=1, as_torch=False, task_choice="random") for _ in range(2)]
-    for e in envs:
-        e.reset()
-    a, r = envs
-    a.batch.bench_rollout(T, 10, seed=seed, mode=capi.BENCH_OBS | capi.BENCH_FRESH_ACTIONS | capi.BENCH_AUTORESET, max_episode_steps=2)
-    ptr = r.batch.field_ptr(capi.F_ACTION)[0]
-    for t in range(T):
-        r.batch.random_action(ptr, seed, t)
-        r.batch.step(ptr, capi.ACTMAP_MUSCLE_SIGMOID, 10)
-        r.batch.obs()
-        r.batch.autoreset(2, seed)
-        r.batch.obs_reset_only()
-    for f in (capi.F_QPOS, capi.F_QVEL, capi.F_ACT, capi.F_OBS, capi.F_REWARD, capi.F_DONE, capi.F_SOLVED, capi.F_ELAPSED, capi.F_SITEXPOS,
-              capi.F_TARGET):
-        assert np.array_equal(a.batch.read(f), r.batch.read(f)), f
-    assert a.batch.read(capi.F_ELAPSED).max() <= 2
+    H.fused_epilogue_equals_stepwise(CASE)
 
 
-@pytest.mark.parametrize("env_id", IDS)
+@pytest.mark.parametrize("env_id", CASE.env_ids)
 def test_every_id_steps(env_id):
-    import myosuite_mjx_amd as myo
-    env = myo.make(env_id, num_envs=256, seed=2, as_torch=False)
-    obs = env.reset()
-    assert obs.shape == (256, 47)
-    rng = np.random.default_rng(0)
-    for _ in range(5):
-        obs, rew, term, trunc, info = env.step(rng.uniform(-1, 1, (256, 39)).astype(np.float32))
-        assert np.isfinite(obs).all() and np.isfinite(rew).all()
-    assert env.batch.last_kernel_name() == TRK and not env.status().any()
+    H.every_id_steps(CASE, env_id)
 
 
 def test_goal_params_view_is_zero_copy():
@@ -394,11 +345,4 @@ def test_refusals(bd):
 
 
 def test_guard_poisoned_build():
-    """This file once more against libmyo_hip_poison.so (NaN-filled LDS, scratch and registers before every step launch)."""
-    lib = os.path.join(ROOT, "myosuite_mjx_amd", "libmyo_hip_poison.so")
-    assert os.path.exists(lib), "libmyo_hip_poison.so is missing: run __graft_entry__.build()"
-    env = dict(os.environ, MYO_HIP_LIB=lib)
-    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider", "-k", "not guard",
-                        "tests/test_gpu_baoding.py"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
-    assert " passed" in r.stdout
+    H.rerun_file_against_poison_build(__file__, timeout=1500)

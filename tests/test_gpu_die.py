@@ -7,18 +7,16 @@ step kernel: MyoHand + a die of 12 capsules and 3 boxes on 3 slides + 3 hinges +
   * MYO_F_SITEXPOS, observation, reward, done and solved against tests/reorient_ref.py on the 600 rollout states with goals drawn per env;
     reset draws over 4096 envs; the goal_offset / body_quat views; the fused bench epilogue; no dropped contact over a 150-step random
     rollout at 4096 envs; every id steps; refusals."""
-import os
-
 import numpy as np
 import pytest
 
+import hand_task_checks as H
 from die_states import init_qpos, pick_states, rollout_states
+from hand_task_checks import TRK
 from reorient_ref import SITES, euler2quat, euler_margin, mat2euler, reorient_restate
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TRK = "step_kernel_w<36,20,32,2,2,false,0,false,true>"
-IDS = [f"myo{c}ChallengeDieReorient{v}-v0" for c in ("", "Sarc", "Fati") for v in ("Demo", "P1")]
+ID = "myoChallengeDieReorientP1-v0"
 DT = 0.01
 
 
@@ -38,6 +36,10 @@ def _configure(b, m, pos_th=0.025, goal_pos=(-0.010, 0.010)):
     b.configure(task=capi.TASK_DIE, frame_skip=5, target_generate=1, target_lo=[goal_pos[0]] * 3, target_hi=[goal_pos[1]] * 3,
                 init_qpos=init_qpos(m), tip_sites=[m.name2id("site", n) for n in SITES], near_th=pos_th, pose_thd=0.262, far_th=0.2,
                 w_pose=100.0, w_reach=1.0, w_bonus=0.0, w_act_reg=0.0, w_penalty=0.0, quat_body=m.name2id("body", "target"))
+
+
+CASE = H.TaskCase(stem="myohand_die", task="die", bench_id=ID, obs_dim=63, nsub=5, configure=_configure, extra_fields=("F_BODYQUAT", "F_TARGET"),
+                  env_ids=tuple(f"myo{c}ChallengeDieReorient{v}-v0" for c in ("", "Sarc", "Fati") for v in ("Demo", "P1")))
 
 
 def _quat2mat(q):
@@ -64,21 +66,10 @@ def test_contact_parity(die, rollouts, nsub, tq, tv):
     rng = np.random.default_rng(9)
     q, v, act = (np.array([s[k] for s in P]).astype(f32) for k in range(3))
     a = rng.uniform(-1, 1, (N, m.nu)).astype(f32)
-    b = capi.HipBatch(capi.HipModel(m.blob(), 0), N)
-    _configure(b, m)
-    for f, x in ((capi.F_QPOS, q), (capi.F_QVEL, v), (capi.F_ACT, act), (capi.F_ACTION, a)):
-        b.write(f, x)
-    b.step(b.field_ptr(capi.F_ACTION)[0], capi.ACTMAP_MUSCLE_SIGMOID, nsub)
-    assert b.last_kernel_name() == TRK
-    gq, gv, ctrl, dg, fl = b.read(capi.F_QPOS), b.read(capi.F_QVEL), b.read(capi.F_CTRL), b.read(capi.F_DIAG), b.status()
+    b = H.new_batch(CASE, m, N)
     o = Oracle(m.blob())
-    eq, ev, nc = np.zeros(N), np.zeros(N), np.zeros(N, int)
-    for e in range(N):
-        o.reset()
-        o.set_state(qpos=q[e], qvel=v[e], act=act[e], ctrl=ctrl[e])
-        assert o.step(nsub) == 0
-        eq[e], ev[e], nc[e] = np.abs(gq[e] - o.field("qpos")).max(), np.abs(gv[e] - o.field("qvel")).max(), o.ncon
-    same = (fl == 0) & (dg[:, 1] == nc)
+    eq, ev, nc, dg, fl, same = H.step_and_compare_with_oracle(m, b, {capi.F_QPOS: q, capi.F_QVEL: v, capi.F_ACT: act, capi.F_ACTION: a}, nsub,
+                                                              lambda e: o)
     print(f"die parity nsub={nsub}: same contact count {same.mean():.3f}, max|dqpos| {eq[same].max():.3e}, max|dqvel| {ev[same].max():.3e}, "
           f"all states {eq.max():.3e} / {ev.max():.3e}, flags {sorted(set(fl.tolist()))}, ncon max {nc.max()}")
     assert same.mean() > 0.8, (same.mean(), dg[:, 1].tolist(), nc.tolist())
@@ -87,7 +78,7 @@ def test_contact_parity(die, rollouts, nsub, tq, tv):
     for tag in ("palm", "finger", "falling"):
         assert any(same[e] and tag in P[e][3] for e in range(N)), tag
     assert any(same[e] and (3, 6) in P[e][4] for e in range(N)) and any(same[e] and (3, 3) in P[e][4] for e in range(N))
-    assert np.abs(gq - q).max() > 1e-5
+    assert np.abs(b.read(capi.F_QPOS) - q).max() > 1e-5
 
 
 def _goals(m, S, rng, Ro, xo):
@@ -126,15 +117,12 @@ def test_observation_against_restatement(die, rollouts):
     sid = [m.name2id("site", n) for n in SITES]
     xs = np.zeros((N, 8, 3))
     for e in range(N):
-        o.reset()
-        o.set_state(qpos=q[e])
-        o.forward()
+        H.forward_at(o, q[e])
         Ro[e], xo[e] = o.field("xmat").reshape(-1, 3, 3)[ob], o.field("site_xpos").reshape(-1, 3)[sid[0]]
         xs[e] = o.field("site_xpos").reshape(-1, 3)[sid]
     rng = np.random.default_rng(11)
     off, quat = _goals(m, S, rng, Ro, xo)
-    b = capi.HipBatch(capi.HipModel(m.blob(), 0), N)
-    _configure(b, m)
+    b = H.new_batch(CASE, m, N)
     for f, x in ((capi.F_QPOS, q), (capi.F_QVEL, v), (capi.F_ACT, act), (capi.F_BODYQUAT, quat), (capi.F_TARGET, off)):
         b.write(f, x)
     b.obs()
@@ -179,7 +167,11 @@ def test_reset_draws_and_sharding():
     import myosuite_mjx_amd as myo
     from myosuite_mjx_amd import capi
     B = 4096
-    env = myo.make("myoChallengeDieReorientP1-v0", num_envs=B, seed=7, as_torch=False)
+
+    def make_env(n, seed, off):
+        return myo.make(ID, num_envs=n, seed=seed, env_offset=off, as_torch=False)
+
+    env = make_env(B, H.SEED, 0)
     obs = env.reset()
     m = env.mjmodel
     tb = m.name2id("body", "target")
@@ -193,8 +185,7 @@ def test_reset_draws_and_sharding():
     assert np.abs(euler2quat(eul) - quat).max() < 2e-6                                 # the reference's euler2quat of ...
     assert eul.min() >= -1.57 - 1e-5 and eul.max() <= 1.57 + 1e-5                      # ... angles inside goal_rot
     for a, lo, hi in [(off[:, k], -0.010, 0.010) for k in range(3)] + [(eul[:, k], -1.57, 1.57) for k in range(3)]:
-        h = np.histogram(a, bins=8, range=(lo, hi))[0]
-        assert np.abs(h - B / 8).max() < 5 * np.sqrt(B / 8)                            # uniform, and different from env to env
+        H.assert_uniform(a, lo, hi)                                                    # uniform, and different from env to env
     assert len(np.unique(off[:, 0])) > 0.9 * B and abs(np.corrcoef(off[:, 0], off[:, 1])[0, 1]) < 0.1
     # the first observation shows the drawn goal
     assert np.abs(obs[:, 48:51] - (m.body_pos[tb] + off)).max() < 5e-6 and np.abs(obs[:, 51:54] - off).max() < 5e-6
@@ -212,17 +203,9 @@ def test_reset_draws_and_sharding():
     assert (off2 != off).any(axis=1).mean() > 0.99 and (quat2 != quat).any(axis=1).mean() > 0.99
     assert off2.min() >= -0.010 and off2.max() <= 0.010
     # same seed: same draws; another seed: others; shards draw what the full batch draws
-    env2 = myo.make("myoChallengeDieReorientP1-v0", num_envs=B, seed=7, as_torch=False)
-    env2.reset()
-    assert np.array_equal(env2.goal_offset, off) and np.array_equal(env2.body_quat, quat)
-    env2.reset(seed=8)
-    assert not np.array_equal(env2.goal_offset, off) and not np.array_equal(env2.body_quat, quat)
-    for o_ in (0, B // 2):
-        s = myo.make("myoChallengeDieReorientP1-v0", num_envs=B // 2, seed=7, env_offset=o_, as_torch=False)
-        s.reset()
-        assert np.array_equal(s.goal_offset, off[o_:o_ + B // 2]) and np.array_equal(s.body_quat, quat[o_:o_ + B // 2])
+    H.assert_deterministic_and_sharded(make_env, lambda e: (e.goal_offset, e.body_quat), B, (off, quat))
     # Demo: no position draw, +-45 degrees, pos_th = inf
-    d = myo.make("myoChallengeDieReorientDemo-v0", num_envs=256, seed=7, as_torch=False)
+    d = myo.make("myoChallengeDieReorientDemo-v0", num_envs=256, seed=H.SEED, as_torch=False)
     od = d.reset()
     assert not d.goal_offset.any() and np.abs(od[:, 51:54]).max() < 5e-6
     ed = mat2euler(np.array([_quat2mat(x) for x in d.body_quat]))
@@ -236,7 +219,7 @@ def test_goal_views_are_writable_and_take_effect():
     import torch
     import myosuite_mjx_amd as myo
     from myosuite_mjx_amd import capi
-    env = myo.make("myoChallengeDieReorientP1-v0", num_envs=64, seed=3)
+    env = myo.make(ID, num_envs=64, seed=3)
     env.reset()
     m = env.mjmodel
     tb = m.name2id("body", "target")
@@ -262,25 +245,7 @@ def test_goal_views_are_writable_and_take_effect():
 
 
 def test_fused_bench_epilogue_equals_step_obs_autoreset():
-    import myosuite_mjx_amd as myo
-    from myosuite_mjx_amd import capi
-    B, seed, T = 512, 3, 5
-    envs = [myo.make("myoChallengeDieReorientP1-v0", num_envs=B, seed=1, as_torch=False) for _ in range(2)]
-    for e in envs:
-        e.reset()
-    a, r = envs
-    a.batch.bench_rollout(T, 5, seed=seed, mode=capi.BENCH_OBS | capi.BENCH_FRESH_ACTIONS | capi.BENCH_AUTORESET, max_episode_steps=2)
-    ptr = r.batch.field_ptr(capi.F_ACTION)[0]
-    for t in range(T):
-        r.batch.random_action(ptr, seed, t)
-        r.batch.step(ptr, capi.ACTMAP_MUSCLE_SIGMOID, 5)
-        r.batch.obs()
-        r.batch.autoreset(2, seed)
-        r.batch.obs_reset_only()
-    for f in (capi.F_QPOS, capi.F_QVEL, capi.F_ACT, capi.F_OBS, capi.F_REWARD, capi.F_DONE, capi.F_SOLVED, capi.F_ELAPSED, capi.F_SITEXPOS,
-              capi.F_BODYQUAT, capi.F_TARGET):
-        assert np.array_equal(a.batch.read(f), r.batch.read(f)), f
-    assert a.batch.read(capi.F_ELAPSED).max() <= 2 and a.batch.last_kernel_name() == TRK
+    assert H.fused_epilogue_equals_stepwise(CASE).last_kernel_name() == TRK
 
 
 def test_no_dropped_contact_over_a_random_rollout():
@@ -288,7 +253,7 @@ def test_no_dropped_contact_over_a_random_rollout():
     candidate pair is ever dropped (the other flag bits are printed)."""
     import myosuite_mjx_amd as myo
     from myosuite_mjx_amd import capi
-    env = myo.make("myoChallengeDieReorientP1-v0", num_envs=4096, seed=5, as_torch=False)
+    env = myo.make(ID, num_envs=4096, seed=5, as_torch=False)
     env.reset()
     ncon, resets = 0, 0
     for k in range(6):
@@ -302,25 +267,16 @@ def test_no_dropped_contact_over_a_random_rollout():
     assert np.isfinite(env.batch.read(capi.F_OBS)).all() and ncon >= 8 and resets > 4096
 
 
-@pytest.mark.parametrize("env_id", IDS)
+@pytest.mark.parametrize("env_id", CASE.env_ids)
 def test_every_id_steps(env_id):
-    import myosuite_mjx_amd as myo
-    from myosuite_mjx_amd import capi
-    env = myo.make(env_id, num_envs=256, seed=2, as_torch=False)
-    obs = env.reset()
-    assert obs.shape == (256, 63) and env.max_episode_steps == 150 and env.frame_skip == 5
-    rng = np.random.default_rng(0)
-    for _ in range(5):
-        obs, rew, term, trunc, info = env.step(rng.uniform(-1, 1, (256, 39)).astype(np.float32))
-        assert np.isfinite(obs).all() and np.isfinite(rew).all()
-    assert env.batch.last_kernel_name() == TRK and not env.status().any()
-    assert np.abs(env.batch.read(capi.F_ACT)).max() > 0
+    env = H.every_id_steps(CASE, env_id)
+    assert env.max_episode_steps == 150 and env.frame_skip == 5
 
 
 def test_env_api_matches_restatement():
     import myosuite_mjx_amd as myo
     from myosuite_mjx_amd import capi
-    env = myo.make("myoChallengeDieReorientP1-v0", num_envs=1024, seed=4, as_torch=False, autoreset=False)
+    env = myo.make(ID, num_envs=1024, seed=4, as_torch=False, autoreset=False)
     env.reset()
     rng = np.random.default_rng(1)
     for _ in range(12):

@@ -7,30 +7,21 @@ kernel: MyoHand + a key on a hinge with friction loss, whose head (ellipsoid), s
   * reset draws over 4096 envs (key angle, key offset), determinism and sharding; the per-env key offset against the oracle on a blob whose
     key body was moved (Model.with_body_pos); the fused bench epilogue against step + obs + autoreset; the muscle-condition variants; the
     same file against the NaN-poisoned build."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+import hand_task_checks as H
 from keyturn_ref import keyturn_restate
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TRK = "step_kernel_w<36,20,32,2,2,false,0,false,true>"
 SITES = ("keyhead", "IFtip", "THtip")
+ID = "myoHandKeyTurnRandom-v0"
 
 
 @pytest.fixture(scope="module")
 def key():
     from myosuite_mjx_amd import model as M
     return M.load_asset("myohand_keyturn")
-
-
-def _sites(o, m):
-    x = o.field("site_xpos").reshape(-1, 3)
-    return np.concatenate([x[m.name2id("site", n)] for n in SITES])
 
 
 def _key_geoms(m):
@@ -59,9 +50,7 @@ def _contact_states(m, N, seed):
         q = np.zeros(m.nq)
         q[:23] = lo + rng.uniform(0.1, 0.9, 23) * (hi - lo)
         q[23] = rng.uniform(-1.5, 1.5)
-        o.reset()
-        o.set_state(qpos=q)
-        o.forward()
+        H.forward_at(o, q)
         d = np.zeros(3)
         if len(qs) >= N // 2:      # bring the box bit to a fingertip
             tip = o.field("site_xpos").reshape(-1, 3)[tips[len(qs) % 3]]
@@ -92,35 +81,34 @@ def _configure(b, m, goal_th=3.14):
                 far_th=0.1, w_pose=1.0, w_reach=10.0, w_act_reg=1.0, w_bonus=4.0, w_penalty=25.0, init_qpos=np.zeros(m.nq))
 
 
+CASE = H.TaskCase(stem="myohand_keyturn", task="keyturn", bench_id=ID, obs_dim=93, nsub=10, configure=_configure, extra_fields=("F_BODYPOS",),
+                  env_ids=("myoSarcHandKeyTurnFixed-v0", "myoFatiHandKeyTurnRandom-v0", "myoReafHandKeyTurnRandom-v0"))
+
+
 @pytest.mark.parametrize("nsub,tq,tv", [(1, 2e-5, 2e-2), (10, 2e-3, 0.2)])
 def test_key_contact_parity(key, nsub, tq, tv):
     from myosuite_mjx_amd import capi
     from oracle.oracle import Oracle
     m = key
     assert (m.nq, m.nv, m.nu) == (24, 24, 39) and list(m.hip_trk) == [0, 1, 1] and m.hip_fl[23, 0] == pytest.approx(0.02)
-    hm = capi.HipModel(m.blob(), 0)
     o = Oracle(m.blob())
     N = 96
     q, v, act, a, d, hits = _contact_states(m, N, 3)
     kb = m.name2id("body", "key")
-    b = capi.HipBatch(hm, N)
-    _configure(b, m)                                      # a non-track task on the TRK instantiation
-    for f, x in ((capi.F_QPOS, q), (capi.F_QVEL, v), (capi.F_ACT, act), (capi.F_ACTION, a), (capi.F_BODYPOS, d)):
-        b.write(f, x)
-    b.step(b.field_ptr(capi.F_ACTION)[0], capi.ACTMAP_MUSCLE_SIGMOID, nsub)
-    assert b.last_kernel_name() == TRK
-    gq, gv, ctrl, dg, fl = b.read(capi.F_QPOS), b.read(capi.F_QVEL), b.read(capi.F_CTRL), b.read(capi.F_DIAG), b.status()
-    assert np.allclose(ctrl, 1 / (1 + np.exp(-5 * (a - 0.5))), atol=1e-6)    # base_v0.py:87-91
-    eq, ev, nc, fr = np.zeros(N), np.zeros(N), np.zeros(N, int), np.zeros(N, int)
-    for e in range(N):
-        oe = o if not d[e].any() else Oracle(m.with_body_pos(kb, m.body_pos[kb] + d[e].astype(np.float64)).blob())
-        oe.reset()
-        oe.set_state(qpos=q[e], qvel=v[e], act=act[e], ctrl=ctrl[e])
-        assert oe.step(nsub) == 0
-        eq[e], ev[e], nc[e] = np.abs(gq[e] - oe.field("qpos")).max(), np.abs(gv[e] - oe.field("qvel")).max(), oe.ncon
+    b = H.new_batch(CASE, m, N)                           # a non-track task on the TRK instantiation
+    fr = np.zeros(N, int)
+
+    def oracle_for_env(e):
+        return o if not d[e].any() else Oracle(m.with_body_pos(kb, m.body_pos[kb] + d[e].astype(np.float64)).blob())
+
+    def extra_rows(e, oe):
         fr[e] = oe.nefc - 4 * oe.ncon        # rows beyond the condim-3 pyramids: limits and the key's friction loss
+
+    eq, ev, nc, dg, fl, same = H.step_and_compare_with_oracle(
+        m, b, {capi.F_QPOS: q, capi.F_QVEL: v, capi.F_ACT: act, capi.F_ACTION: a, capi.F_BODYPOS: d}, nsub, oracle_for_env, extra_rows)
+    gq = b.read(capi.F_QPOS)
+    assert np.allclose(b.read(capi.F_CTRL), 1 / (1 + np.exp(-5 * (a - 0.5))), atol=1e-6)    # base_v0.py:87-91
     assert (fr >= 1).all()
-    same = (fl == 0) & (dg[:, 1] == nc)
     assert same.mean() > 0.85
     box = [g for g in range(m.ngeom) if m.geom_bodyid[g] == kb and int(m.geom_type[g]) == 6][0]
     assert sum(1 for e in range(N) if same[e] and box in hits[e]) >= N // 4            # box-bit contacts among the compared envs
@@ -136,7 +124,6 @@ def test_site_positions_and_restatement(key):
     from myosuite_mjx_amd import capi
     from oracle.oracle import Oracle
     m = key
-    hm = capi.HipModel(m.blob(), 0)
     N = 1024
     rng = np.random.default_rng(5)
     lo, hi = m.jnt_range[:23, 0], m.jnt_range[:23, 1]
@@ -144,7 +131,7 @@ def test_site_positions_and_restatement(key):
     q[:, :23] = lo + rng.uniform(0, 1, (N, 23)) * (hi - lo) * rng.uniform(0, 1, (N, 1))
     q[:, 23] = rng.uniform(-1, 7, N)
     q, v, act = q.astype(np.float32), rng.normal(0, 1, (N, m.nv)).astype(np.float32), rng.uniform(0, 1, (N, m.nu)).astype(np.float32)
-    b = capi.HipBatch(hm, N)
+    b = capi.HipBatch(capi.HipModel(m.blob(), 0), N)
     _configure(b, m, goal_th=2 * np.pi)
     for f, x in ((capi.F_QPOS, q), (capi.F_QVEL, v), (capi.F_ACT, act)):
         b.write(f, x)
@@ -153,10 +140,7 @@ def test_site_positions_and_restatement(key):
     assert sx.shape == (N, 9) and obs.shape == (N, 93)
     o = Oracle(m.blob())
     for e in range(0, N, 8):
-        o.reset()
-        o.set_state(qpos=q[e])
-        o.forward()
-        assert np.abs(sx[e] - _sites(o, m)).max() < 5e-6, e
+        assert np.abs(sx[e] - H.site_xpos(H.forward_at(o, q[e]), m, SITES)).max() < 5e-6, e
     ro, rr, rd, rs = keyturn_restate(q, v, act, sx, 0.02, 2 * np.pi)
     assert np.abs(obs - ro).max() < 1e-5
     assert np.abs(rew[:, 0] - rr).max() < 1e-3 * max(1.0, np.abs(rr).max())
@@ -168,33 +152,24 @@ def test_reset_draws_and_sharding():
     import myosuite_mjx_amd as myo
     from myosuite_mjx_amd import capi
     B = 4096
-    env = myo.make("myoHandKeyTurnRandom-v0", num_envs=B, seed=7, as_torch=False)
+
+    def make_env(n, seed, off):
+        return myo.make(ID, num_envs=n, seed=seed, env_offset=off, as_torch=False)
+
+    env = make_env(B, H.SEED, 0)
     env.reset()
     q, off, obs = env.batch.read(capi.F_QPOS), env.body_pos, env.batch.read(capi.F_OBS)
     key_q = q[:, -1]
     assert np.abs(q[:, :-1]).max() == 0                                 # fully open hand
     assert key_q.min() >= -np.pi / 2 and key_q.max() <= np.pi / 2
-    h = np.histogram(key_q, bins=8, range=(-np.pi / 2, np.pi / 2))[0]
-    assert np.abs(h - B / 8).max() < 5 * np.sqrt(B / 8)
+    H.assert_uniform(key_q, -np.pi / 2, np.pi / 2)
     assert np.abs(off).max() <= 0.01 and off.min(axis=0).max() < -0.0095 and off.max(axis=0).min() > 0.0095
     for k in range(3):
-        hk = np.histogram(off[:, k], bins=8, range=(-0.01, 0.01))[0]
-        assert np.abs(hk - B / 8).max() < 5 * np.sqrt(B / 8)
+        H.assert_uniform(off[:, k], -0.01, 0.01)
     assert np.allclose(obs[:, 46], key_q)
-    # deterministic per seed, different across seeds
-    env2 = myo.make("myoHandKeyTurnRandom-v0", num_envs=B, seed=7, as_torch=False)
-    env2.reset()
-    assert np.array_equal(env2.batch.read(capi.F_QPOS), q) and np.array_equal(env2.body_pos, off)
-    env2.reset(seed=8)
-    assert not np.array_equal(env2.body_pos, off)
-    # two shards (env_offset 0 and B / 2) reproduce the single batch
-    for off_e in (0, B // 2):
-        s = myo.make("myoHandKeyTurnRandom-v0", num_envs=B // 2, seed=7, env_offset=off_e, as_torch=False)
-        s.reset()
-        assert np.array_equal(s.batch.read(capi.F_QPOS), q[off_e:off_e + B // 2])
-        assert np.array_equal(s.body_pos, off[off_e:off_e + B // 2])
+    H.assert_deterministic_and_sharded(make_env, lambda e: (e.batch.read(capi.F_QPOS), e.body_pos), B, (q, off))
     # the Fixed variant: key at 0, no offset started
-    f = myo.make("myoHandKeyTurnFixed-v0", num_envs=64, seed=7, as_torch=False)
+    f = myo.make("myoHandKeyTurnFixed-v0", num_envs=64, seed=H.SEED, as_torch=False)
     f.reset()
     assert not f.batch.read(capi.F_QPOS).any() and not f.body_pos.any() and not f.batch.read(capi.F_BODYPOS_RANGE).any()
 
@@ -213,25 +188,19 @@ def test_key_offset_against_moved_blob(key, nsub):
     d = rng.uniform(-0.01, 0.01, (N, 3)).astype(np.float32)
     b = capi.HipBatch(hm, N)
     _configure(b, m)
-    for f, x in ((capi.F_QPOS, q), (capi.F_QVEL, v), (capi.F_ACT, act), (capi.F_BODYPOS, d)):
-        b.write(f, x)
     ctrl = (1 / (1 + np.exp(-5 * (a - 0.5)))).astype(np.float32)
-    b.write(capi.F_CTRL, ctrl)
-    b.step(None, capi.ACTMAP_NONE, nsub)
-    b.obs()
-    assert b.last_kernel_name() == TRK
-    gq, gv, sx, dg, fl = b.read(capi.F_QPOS), b.read(capi.F_QVEL), b.read(capi.F_SITEXPOS), b.read(capi.F_DIAG), b.status()
     kb = m.name2id("body", "key")
-    eq, ev, es, same = np.zeros(N), np.zeros(N), np.zeros(N), np.zeros(N, bool)
-    for e in range(N):
-        mm = m.with_body_pos(kb, m.body_pos[kb] + d[e].astype(np.float64))
-        o = Oracle(mm.blob())
-        o.set_state(qpos=q[e], qvel=v[e], act=act[e], ctrl=ctrl[e])
-        assert o.step(nsub) == 0
-        same[e] = fl[e] == 0 and dg[e, 1] == o.ncon         # contacts of the last substep, before the post-step forward pass
+    osx = np.zeros((N, 9))
+
+    def sites_after_forward(e, o):       # (the contacts were counted after the last substep, before this forward pass)
         o.forward()
-        eq[e], ev[e] = np.abs(gq[e] - o.field("qpos")).max(), np.abs(gv[e] - o.field("qvel")).max()
-        es[e] = np.abs(sx[e] - _sites(o, m)).max()
+        osx[e] = H.site_xpos(o, m, SITES)
+
+    eq, ev, nc, dg, fl, same = H.step_and_compare_with_oracle(
+        m, b, {capi.F_QPOS: q, capi.F_QVEL: v, capi.F_ACT: act, capi.F_BODYPOS: d, capi.F_CTRL: ctrl}, nsub,
+        lambda e: Oracle(m.with_body_pos(kb, m.body_pos[kb] + d[e].astype(np.float64)).blob()), sites_after_forward)
+    b.obs()
+    gq, es = b.read(capi.F_QPOS), np.abs(b.read(capi.F_SITEXPOS) - osx).max(axis=1)
     tq, tv = (2e-5, 2e-2) if nsub == 1 else (2e-3, 0.2)
     assert same.mean() > 0.8 and eq[same].max() < tq and ev[same].max() < tv, (eq[same].max(), ev[same].max())
     assert es[same].max() < (1e-5 if nsub == 1 else 5e-4)
@@ -269,47 +238,19 @@ def test_offset_on_with_zero_offsets_is_offset_off(key):
 
 def test_fused_bench_epilogue_equals_step_obs_autoreset(key):
     """myo_bench_rollout's one-launch epilogue (keyturn_post_kernel) = step, myo_obs, myo_autoreset, myo_obs_reset_only."""
-    import myosuite_mjx_amd as myo
-    from myosuite_mjx_amd import capi
-    B, seed, T = 512, 3, 5
-    envs = [myo.make("myoHandKeyTurnRandom-v0", num_envs=B, seed=1, as_torch=False) for _ in range(2)]
-    for e in envs:
-        e.reset()
-    a, r = envs
-    a.batch.bench_rollout(T, 10, seed=seed, mode=capi.BENCH_OBS | capi.BENCH_FRESH_ACTIONS | capi.BENCH_AUTORESET, max_episode_steps=2)
-    ptr = r.batch.field_ptr(capi.F_ACTION)[0]
-    for t in range(T):
-        r.batch.random_action(ptr, seed, t)
-        r.batch.step(ptr, capi.ACTMAP_MUSCLE_SIGMOID, 10)
-        r.batch.obs()
-        r.batch.autoreset(2, seed)
-        r.batch.obs_reset_only()
-    for f in (capi.F_QPOS, capi.F_QVEL, capi.F_ACT, capi.F_OBS, capi.F_REWARD, capi.F_DONE, capi.F_SOLVED, capi.F_ELAPSED, capi.F_SITEXPOS,
-              capi.F_BODYPOS):
-        assert np.array_equal(a.batch.read(f), r.batch.read(f)), f
-    assert a.batch.read(capi.F_ELAPSED).max() <= 2
+    H.fused_epilogue_equals_stepwise(CASE)
 
 
-@pytest.mark.parametrize("env_id", ["myoSarcHandKeyTurnFixed-v0", "myoFatiHandKeyTurnRandom-v0", "myoReafHandKeyTurnRandom-v0"])
+@pytest.mark.parametrize("env_id", CASE.env_ids)
 def test_muscle_condition_variants_step(env_id):
-    import myosuite_mjx_amd as myo
-    from myosuite_mjx_amd import capi
-    env = myo.make(env_id, num_envs=256, seed=2, as_torch=False)
-    obs = env.reset()
-    assert obs.shape == (256, 93)
-    rng = np.random.default_rng(0)
-    for _ in range(5):
-        obs, rew, term, trunc, info = env.step(rng.uniform(-1, 1, (256, 39)).astype(np.float32))
-        assert np.isfinite(obs).all() and np.isfinite(rew).all()
-    assert env.batch.last_kernel_name() == TRK and not env.status().any()
-    assert np.abs(env.batch.read(capi.F_ACT)).max() > 0
+    H.every_id_steps(CASE, env_id)
 
 
 def test_env_api_matches_restatement():
     """A few env steps through the gym API: the returned rows are the restatement of the stepped state (envs not reset in between)."""
     import myosuite_mjx_amd as myo
     from myosuite_mjx_amd import capi
-    env = myo.make("myoHandKeyTurnRandom-v0", num_envs=1024, seed=4, as_torch=False, autoreset=False)
+    env = myo.make(ID, num_envs=1024, seed=4, as_torch=False, autoreset=False)
     env.reset()
     rng = np.random.default_rng(1)
     for _ in range(3):
@@ -349,11 +290,4 @@ def test_refusals(key):
 
 
 def test_guard_poisoned_build():
-    """This file once more against libmyo_hip_poison.so (NaN-filled LDS, scratch and registers before every step launch)."""
-    lib = os.path.join(ROOT, "myosuite_mjx_amd", "libmyo_hip_poison.so")
-    assert os.path.exists(lib), "libmyo_hip_poison.so is missing: run __graft_entry__.build()"
-    env = dict(os.environ, MYO_HIP_LIB=lib)
-    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider", "-k", "not guard",
-                        "tests/test_gpu_keyturn.py"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
-    assert " passed" in r.stdout
+    H.rerun_file_against_poison_build(__file__, timeout=900)

@@ -8,20 +8,17 @@ MyoHand + a free pen (a condim-4 cylinder) + a world-welded target cylinder whos
     device euler2quat against the reference's; determinism and sharding; orientation started with the compiled quaternion = off; the
     fused bench epilogue; the muscle-condition variants; refusals; the same file against the NaN-poisoned build."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import hand_task_checks as H
 from pen_ref import euler2quat, pen_restate
-from pen_states import branch_states, floor_qpos
+from pen_states import branch_states
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TRK = "step_kernel_w<36,20,32,2,2,false,0,false,true>"
 SITES = ("object_top", "object_bottom", "target_top", "target_bottom", "eps_ball")
-IDS = [f"myo{c}HandPenTwirl{v}-v0" for c in ("", "Sarc", "Fati", "Reaf") for v in ("Fixed", "Random")]
+ID = "myoHandPenTwirlRandom-v0"
 
 
 @pytest.fixture(scope="module")
@@ -43,6 +40,10 @@ def _configure(b, m):
     b.configure(task=capi.TASK_PEN, frame_skip=5, tip_sites=[m.name2id("site", n) for n in SITES],
                 tip_lpos=tuple(np.asarray(m.hip_body_lpos).reshape(-1, 3)[ob]), pose_thd=0.95, far_th=0.075,
                 w_pose=1.0, w_reach=1.0, w_act_reg=5.0, w_bonus=10.0, w_penalty=5.0, init_qpos=np.zeros(m.nq), quat_body=m.name2id("body", "target"))
+
+
+CASE = H.TaskCase(stem="myohand_pen", task="pen", bench_id=ID, obs_dim=83, nsub=5, configure=_configure, extra_fields=("F_BODYQUAT",),
+                  env_ids=tuple(f"myo{c}HandPenTwirl{v}-v0" for c in ("", "Sarc", "Fati", "Reaf") for v in ("Fixed", "Random")))
 
 
 _ROT = {}
@@ -99,10 +100,7 @@ def _states(m, kind, N, seed):
                 q[-6:-3] = Ry.T @ d
                 q[-3:] = rng.uniform(-1, 1, 3)
                 oo = Oracle(blob)
-        oo.reset()
-        oo.set_state(qpos=q)
-        oo.forward()
-        cs = oo.contacts()
+        cs = H.forward_at(oo, q).contacts()
         pairs = {frozenset((int(c[7]), int(c[8]))) for c in cs}
         if not cs or min(c[0] for c in cs) < -0.004 and kind != "floor":
             continue
@@ -128,25 +126,16 @@ def test_contact_parity(pen, kind, nsub, tq, tv):
     ob, tb, pg, tg = _bodies(m)
     N = 48
     q, quat, v, act, a, tags = _states(m, kind, N, {"floor": 1, "finger": 2, "target": 3}[kind])
-    hm = capi.HipModel(m.blob(), 0)
-    b = capi.HipBatch(hm, N)
-    _configure(b, m)
-    for f, x in ((capi.F_QPOS, q), (capi.F_QVEL, v), (capi.F_ACT, act), (capi.F_ACTION, a)):
-        b.write(f, x)
+    b = H.new_batch(CASE, m, N)
+    state = {capi.F_QPOS: q, capi.F_QVEL: v, capi.F_ACT: act, capi.F_ACTION: a}
     if kind == "target":
-        b.write(capi.F_BODYQUAT, quat)
-    b.step(b.field_ptr(capi.F_ACTION)[0], capi.ACTMAP_MUSCLE_SIGMOID, nsub)
-    assert b.last_kernel_name() == TRK
-    gq, gv, ctrl, dg, fl = b.read(capi.F_QPOS), b.read(capi.F_QVEL), b.read(capi.F_CTRL), b.read(capi.F_DIAG), b.status()
+        state[capi.F_BODYQUAT] = quat
     o0 = Oracle(m.blob())
-    eq, ev, nc = np.zeros(N), np.zeros(N), np.zeros(N, int)
-    for e in range(N):
-        oe = o0 if kind != "target" else Oracle(next(bl for qq, bl in _ROT.values() if np.allclose(qq, quat[e], atol=1e-6)))
-        oe.reset()
-        oe.set_state(qpos=q[e], qvel=v[e], act=act[e], ctrl=ctrl[e])
-        assert oe.step(nsub) == 0
-        eq[e], ev[e], nc[e] = np.abs(gq[e] - oe.field("qpos")).max(), np.abs(gv[e] - oe.field("qvel")).max(), oe.ncon
-    same = (fl == 0) & (dg[:, 1] == nc)
+
+    def oracle_for_env(e):
+        return o0 if kind != "target" else Oracle(next(bl for qq, bl in _ROT.values() if np.allclose(qq, quat[e], atol=1e-6)))
+
+    eq, ev, nc, dg, fl, same = H.step_and_compare_with_oracle(m, b, state, nsub, oracle_for_env)
     if kind == "floor" and nsub > 1:
         # the pen resting on its cap: the oracle skips a cylinder pair whose other geom's centre lies beyond the cylinder's cap planes
         # along its axis (its cap filter, with the plane's bounding radius 0), which drops the resting contacts of a tilted pen whose
@@ -158,7 +147,7 @@ def test_contact_parity(pen, kind, nsub, tq, tv):
     if kind == "floor" and nsub == 1:
         for k, n in enumerate((1, 2, 3, 4)):         # every branch among the compared states
             assert any(same[e] for e in range(k, N, 4)), n
-    assert np.abs(gq - q).max() > 1e-5
+    assert np.abs(b.read(capi.F_QPOS) - q).max() > 1e-5
 
 
 def test_site_positions_and_restatement(pen):
@@ -180,8 +169,7 @@ def test_site_positions_and_restatement(pen):
     pick = rng.integers(-8, 8, N)                                       # half of them at the compiled orientation
     quat = np.array([_rotated(m, k)[0] if k >= 0 else [1.0, 0, 0, 0] for k in pick]).astype(np.float32)
     q, v, act = q.astype(np.float32), rng.normal(0, 1, (N, m.nv)).astype(np.float32), rng.uniform(0, 1, (N, m.nu)).astype(np.float32)
-    b = capi.HipBatch(capi.HipModel(m.blob(), 0), N)
-    _configure(b, m)
+    b = H.new_batch(CASE, m, N)
     for f, x in ((capi.F_QPOS, q), (capi.F_QVEL, v), (capi.F_ACT, act), (capi.F_BODYQUAT, quat)):
         b.write(f, x)
     b.obs()
@@ -191,11 +179,8 @@ def test_site_positions_and_restatement(pen):
     for e in range(N):
         if e % 16 == 0:
             o = Oracle(_rotated(m, pick[e])[1] if pick[e] >= 0 else m.blob())
-            o.reset()
-            o.set_state(qpos=q[e])
-            o.forward()
-            x = o.field("site_xpos").reshape(-1, 3)
-            assert np.abs(sx[e] - np.concatenate([x[m.name2id("site", n)] for n in SITES])).max() < 5e-6, e
+            H.forward_at(o, q[e])
+            assert np.abs(sx[e] - H.site_xpos(o, m, SITES)).max() < 5e-6, e
             assert np.abs(obs[e, 23:26] - o.field("xpos").reshape(-1, 3)[ob]).max() < 5e-6
         xp[e] = obs[e, 23:26]
     ro, rr, rd, rs = pen_restate(q, v, act, sx, xp, 0.01)
@@ -209,7 +194,11 @@ def test_reset_draws_and_sharding():
     import myosuite_mjx_amd as myo
     from myosuite_mjx_amd import capi
     B = 4096
-    env = myo.make("myoHandPenTwirlRandom-v0", num_envs=B, seed=7, as_torch=False)
+
+    def make_env(n, seed, off):
+        return myo.make(ID, num_envs=n, seed=seed, env_offset=off, as_torch=False)
+
+    env = make_env(B, H.SEED, 0)
     obs = env.reset()
     m = env.mjmodel
     q, quat = env.batch.read(capi.F_QPOS), env.body_quat
@@ -222,19 +211,10 @@ def test_reset_draws_and_sharding():
     assert np.abs(euler2quat(np.stack([ex, ey, np.zeros(B)], 1)) - quat).max() < 2e-6
     for a in (ex, ey):
         assert a.min() >= -1 - 1e-5 and a.max() <= 1 + 1e-5
-        h = np.histogram(a, bins=8, range=(-1, 1))[0]
-        assert np.abs(h - B / 8).max() < 5 * np.sqrt(B / 8)
+        H.assert_uniform(a, -1, 1)
     assert np.abs(obs[:, 35:38] - env.batch.read(capi.F_SITEXPOS)[:, 6:9] / 0.13 + env.batch.read(capi.F_SITEXPOS)[:, 9:12] / 0.13).max() < 1e-5
-    env2 = myo.make("myoHandPenTwirlRandom-v0", num_envs=B, seed=7, as_torch=False)
-    env2.reset()
-    assert np.array_equal(env2.body_quat, quat)
-    env2.reset(seed=8)
-    assert not np.array_equal(env2.body_quat, quat)
-    for off in (0, B // 2):
-        s = myo.make("myoHandPenTwirlRandom-v0", num_envs=B // 2, seed=7, env_offset=off, as_torch=False)
-        s.reset()
-        assert np.array_equal(s.body_quat, quat[off:off + B // 2])
-    f = myo.make("myoHandPenTwirlFixed-v0", num_envs=64, seed=7, as_torch=False)
+    H.assert_deterministic_and_sharded(make_env, lambda e: (e.body_quat,), B, (quat,))
+    f = myo.make("myoHandPenTwirlFixed-v0", num_envs=64, seed=H.SEED, as_torch=False)
     f.reset()
     assert np.array_equal(f.body_quat, np.tile([1, 0, 0, 0], (64, 1)).astype(np.float32))
     assert not f.batch.read(capi.F_BODYQUAT_RANGE).any()
@@ -243,11 +223,10 @@ def test_reset_draws_and_sharding():
 def test_device_euler2quat_matches_reference(pen):
     """Ranges of zero width around the reference's test angles: the quaternions drawn at reset are the reference's euler2quat."""
     from myosuite_mjx_amd import capi
-    g = np.load(os.path.join(ROOT, "tests", "golden", "ref_quat_math.npz"))
+    g = np.load(os.path.join(H.ROOT, "tests", "golden", "ref_quat_math.npz"))
     eul = g["euler"].astype(np.float32)
     n = len(eul)
-    b = capi.HipBatch(capi.HipModel(pen.blob(), 0), n)
-    _configure(b, pen)
+    b = H.new_batch(CASE, pen, n)
     b.set_body_quat_range(eul, np.nextafter(eul, np.float32(np.inf)))
     b.reset(seed=1)
     assert np.abs(b.read(capi.F_BODYQUAT) - g["euler2quat"]).max() < 2e-6
@@ -276,46 +255,18 @@ def test_override_with_compiled_quat_is_override_off(pen):
 
 
 def test_fused_bench_epilogue_equals_step_obs_autoreset():
-    import myosuite_mjx_amd as myo
-    from myosuite_mjx_amd import capi
-    B, seed, T = 512, 3, 5
-    envs = [myo.make("myoHandPenTwirlRandom-v0", num_envs=B, seed=1, as_torch=False) for _ in range(2)]
-    for e in envs:
-        e.reset()
-    a, r = envs
-    a.batch.bench_rollout(T, 5, seed=seed, mode=capi.BENCH_OBS | capi.BENCH_FRESH_ACTIONS | capi.BENCH_AUTORESET, max_episode_steps=2)
-    ptr = r.batch.field_ptr(capi.F_ACTION)[0]
-    for t in range(T):
-        r.batch.random_action(ptr, seed, t)
-        r.batch.step(ptr, capi.ACTMAP_MUSCLE_SIGMOID, 5)
-        r.batch.obs()
-        r.batch.autoreset(2, seed)
-        r.batch.obs_reset_only()
-    for f in (capi.F_QPOS, capi.F_QVEL, capi.F_ACT, capi.F_OBS, capi.F_REWARD, capi.F_DONE, capi.F_SOLVED, capi.F_ELAPSED, capi.F_SITEXPOS,
-              capi.F_BODYQUAT):
-        assert np.array_equal(a.batch.read(f), r.batch.read(f)), f
-    assert a.batch.read(capi.F_ELAPSED).max() <= 2
+    H.fused_epilogue_equals_stepwise(CASE)
 
 
-@pytest.mark.parametrize("env_id", IDS)
+@pytest.mark.parametrize("env_id", CASE.env_ids)
 def test_every_id_steps(env_id):
-    import myosuite_mjx_amd as myo
-    from myosuite_mjx_amd import capi
-    env = myo.make(env_id, num_envs=256, seed=2, as_torch=False)
-    obs = env.reset()
-    assert obs.shape == (256, 83)
-    rng = np.random.default_rng(0)
-    for _ in range(5):
-        obs, rew, term, trunc, info = env.step(rng.uniform(-1, 1, (256, 39)).astype(np.float32))
-        assert np.isfinite(obs).all() and np.isfinite(rew).all()
-    assert env.batch.last_kernel_name() == TRK and not env.status().any()
-    assert np.abs(env.batch.read(capi.F_ACT)).max() > 0
+    H.every_id_steps(CASE, env_id)
 
 
 def test_env_api_matches_restatement():
     import myosuite_mjx_amd as myo
     from myosuite_mjx_amd import capi
-    env = myo.make("myoHandPenTwirlRandom-v0", num_envs=1024, seed=4, as_torch=False, autoreset=False)
+    env = myo.make(ID, num_envs=1024, seed=4, as_torch=False, autoreset=False)
     env.reset()
     rng = np.random.default_rng(1)
     for _ in range(3):
@@ -358,11 +309,4 @@ def test_refusals(pen):
 
 
 def test_guard_poisoned_build():
-    """This file once more against libmyo_hip_poison.so (NaN-filled LDS, scratch and registers before every step launch)."""
-    lib = os.path.join(ROOT, "myosuite_mjx_amd", "libmyo_hip_poison.so")
-    assert os.path.exists(lib), "libmyo_hip_poison.so is missing: run __graft_entry__.build()"
-    env = dict(os.environ, MYO_HIP_LIB=lib)
-    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider", "-k", "not guard",
-                        "tests/test_gpu_pen.py"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
-    assert " passed" in r.stdout
+    H.rerun_file_against_poison_build(__file__, timeout=1500)

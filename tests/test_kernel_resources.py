@@ -57,3 +57,16 @@ def test_no_other_wave_instantiation_is_built(kernels):
     """Instantiations nobody can reach (round 2: a scheduled hand kernel with 86 spilled VGPRs, two 5-waves-per-SIMD experiments with 87-90) are gone."""
     built = sorted(k for k in kernels if k.startswith("void step_kernel_w<"))
     assert built == sorted(f"void step_kernel_w<{a}>" for a, _ in WAVE.values()), built
+
+
+def test_new_kernels_have_no_spill_and_no_scratch():
+    """The two die kernels, read from the code object's metadata the way the step kernels are read above (the `kernels` fixture keys
+    kernels by the demangled name up to the first parenthesis, which the function-pointer template argument of the task kernels cuts
+    short, so they are looked up by their mangled names here)."""
+    from myosuite_mjx_amd import capi
+    import kernel_resources
+    rs = [r for r in kernel_resources.resources(capi.LIB_PATH) if "die_obs_body" in r["name"]]
+    names = sorted(subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip() for r in rs)
+    assert len(rs) == 2 and names[0].startswith("void task_obs_kernel<StateObs<&(die_obs_body(") and names[1].startswith("void task_post_kernel<StateObs<&(die_obs_body("), names
+    for r in rs:
+        assert r["vgpr_spill"] == 0 and r["scratch"] == 0 and r["vgpr"] + r["agpr"] <= 128, r

@@ -1,17 +1,17 @@
 """CPU tests for myoHandKeyTurn{Fixed,Random}-v0 (envs/myo/myobase/key_turn_v0.py): registry entries and kwargs, the committed
-myohand_keyturn asset and its TrackEnv-class lowering, the appended ABI ids, the float64 restatement of the task's formulas
-(tests/keyturn_ref.py) on oracle states, Model.with_body_pos, and the lowered tables of every committed asset unchanged."""
-import glob
+myohand_keyturn asset and its TrackEnv-class lowering, the float64 restatement of the task's formulas
+(tests/keyturn_ref.py) on oracle states, and Model.with_body_pos.  (The ABI ids are pinned in tests/test_capi_host.py, the lowered tables
+of every committed asset in tests/test_compile_bytes.py.)"""
 import os
-import re
 
 import numpy as np
 import pytest
 
+import hand_task_checks as H
 from keyturn_ref import keyturn_restate
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IDS = ("myoHandKeyTurnFixed-v0", "myoHandKeyTurnRandom-v0")
+SITES = ("keyhead", "IFtip", "THtip")
 
 
 @pytest.fixture(scope="module")
@@ -28,11 +28,9 @@ def test_registry_entries_and_variants():
     assert f["goal_th"] == 3.14 and tuple(f["key_init_range"]) == (0.0, 0.0)
     assert r["goal_th"] == 2 * np.pi and tuple(r["key_init_range"]) == (-np.pi / 2, np.pi / 2)
     assert f["weights"] == dict(key_turn=1.0, IFtip_approach=10.0, THtip_approach=10.0, act_reg=1.0, bonus=4.0, penalty=25.0)
-    for i in IDS:                                      # register_env_with_variants (envs/myo/myobase/__init__.py:14-48)
-        for c, cond in (("Sarc", "sarcopenia"), ("Fati", "fatigue"), ("Reaf", "reafferentation")):
-            v = envs.REGISTRY[i[:3] + c + i[3:]]
-            assert v["muscle_condition"] == cond and v["task"] == "keyturn" and v["goal_th"] == envs.REGISTRY[i]["goal_th"]
-        assert i not in envs.UNSUPPORTED
+    for i in IDS:
+        for v in H.muscle_variants(i, H.CONDITIONS):
+            assert v["task"] == "keyturn" and v["goal_th"] == envs.REGISTRY[i]["goal_th"]
 
 
 def test_kwargs_are_key_turn_only():
@@ -68,25 +66,6 @@ def test_asset_loads_and_is_trk_class(key):
     assert m.site_bodyid[s] == kb and not np.asarray(m.hip_site_lpos[s]).any()
 
 
-def test_abi_ids_are_appended():
-    from myosuite_mjx_amd import capi
-    hdr = open(os.path.join(ROOT, "include", "myo_hip.h")).read()
-    body = hdr[hdr.index("typedef enum myo_field"):hdr.index("} myo_field;")]
-    names = re.findall(r"^\s*(MYO_F_[A-Z_]+)", re.sub(r"/\*.*?\*/", "", body, flags=re.S), flags=re.M)
-    assert names[-3:] == ["MYO_F_BODYMASS", "MYO_F_BODYMASS_RANGE", "MYO_F_COUNT"] and len(names) == 27
-    ext = hdr[hdr.index("} myo_field;"):hdr.index("MYO_FLAG_BAD_STATE")]
-    ext = re.findall(r"^\s*(MYO_F_[A-Z_]+(?: = MYO_F_COUNT)?)", re.sub(r"/\*.*?\*/", "", ext, flags=re.S), flags=re.M)
-    assert ext == ["MYO_F_BODYPOS = MYO_F_COUNT", "MYO_F_BODYPOS_RANGE"]          # the ids continue after the list
-    assert (capi.F_BODYMASS, capi.F_BODYMASS_RANGE, capi.F_BODYPOS, capi.F_BODYPOS_RANGE) == (24, 25, 26, 27)
-    assert "MYO_TASK_KEYTURN = 7" in hdr and capi.TASK_KEYTURN == 7
-    assert (capi.TASK_HOLD, capi.TASK_STAND, capi.TASK_TRACK) == (4, 5, 6)
-
-
-def _oracle_sites(o, m):
-    x = o.field("site_xpos").reshape(-1, 3)
-    return np.concatenate([x[m.name2id("site", n)] for n in ("keyhead", "IFtip", "THtip")])
-
-
 def test_restatement_on_oracle_states(key):
     """The restatement of key_turn_v0.py's formulas on oracle states: obs layout, the thresholds of bonus / penalty / done / solved."""
     from oracle.oracle import Oracle
@@ -94,10 +73,7 @@ def test_restatement_on_oracle_states(key):
     o = Oracle(m.blob())
     rng = np.random.default_rng(0)
     q0 = np.zeros(m.nq)
-    o.reset()
-    o.set_state(qpos=q0)
-    o.forward()
-    sites = _oracle_sites(o, m)
+    sites = H.site_xpos(H.forward_at(o, q0), m, SITES)
     assert np.allclose(sites[:3], m.body_pos[m.name2id("body", "key")])     # key head = key body origin
     act = rng.uniform(0, 1, (1, 39))
     qvel = rng.normal(0, 1, (1, 24))
@@ -115,10 +91,7 @@ def test_restatement_on_oracle_states(key):
     for kq, bonus, sol_fixed, sol_random in ((1.0, 0, False, False), (2.0, 1, False, False), (3.145, 2, True, False), (6.5, 2, True, True)):
         q = q0.copy()
         q[-1] = kq
-        o.reset()
-        o.set_state(qpos=q)
-        o.forward()
-        s = _oracle_sites(o, m)
+        s = H.site_xpos(H.forward_at(o, q), m, SITES)
         assert np.allclose(s[3:], sites[3:]) and np.allclose(s[:3], sites[:3])
         _, r, _, sf = keyturn_restate(q, np.zeros((1, 24)), np.zeros((1, 39)), s, 0.02, 3.14)
         _, _, _, sr = keyturn_restate(q, np.zeros((1, 24)), np.zeros((1, 39)), s, 0.02, 2 * np.pi)
@@ -130,10 +103,7 @@ def test_restatement_on_oracle_states(key):
         for n in ("mcp2_flexion", "pm2_flexion", "md2_flexion"):
             j = m.name2id("joint", n)
             q[j] = f * m.jnt_range[j, 1]
-        o.reset()
-        o.set_state(qpos=q)
-        o.forward()
-        s = _oracle_sites(o, m)
+        s = H.site_xpos(H.forward_at(o, q), m, SITES)
         ds.append(np.linalg.norm(s[:3] - s[3:6]))
     assert np.ptp(ds) > 0.01
 
@@ -158,23 +128,3 @@ def test_with_body_pos(key):
         m.with_body_pos("distph2", [0, 0, 0])                 # not a root body
     with pytest.raises(ValueError):
         m.with_body_pos("key", [np.nan, 0, 0])
-
-
-def test_lowered_tables_of_committed_assets_unchanged():
-    """Lowering the committed assets' compiled arrays again reproduces their committed hip_* tables byte for byte (the box / friction-loss
-    acceptance added for myohand_keyturn changes no other model).  The gzip-compressed MyoDM objects are covered by airplane and cup."""
-    from myosuite_mjx_amd import model as M
-    from myosuite_mjx_amd.lowering import lower
-    from myosuite_mjx_amd.mjcf import CompiledModel
-    stems = sorted(os.path.basename(p)[:-5] for p in glob.glob(os.path.join(M.ASSET_DIR, "*.myob")))
-    stems += sorted(os.path.basename(p)[:-8] for p in glob.glob(os.path.join(M.GOLDEN_DIR, "*.myob.gz")))
-    assert "myohand_keyturn" in stems and "myohand_object_airplane" in stems and len(stems) >= 11
-    for stem in stems:
-        m = M.load_asset(stem)
-        cm = CompiledModel(arrays={k: np.array(v, copy=True) for k, v in m.arrays.items() if not k.startswith("hip_")}, names=m.names)
-        lower(cm)
-        hip = {k: v for k, v in m.arrays.items() if k.startswith("hip_")}
-        assert sorted(k for k in cm.arrays if k.startswith("hip_")) == sorted(hip), stem
-        for k, v in hip.items():
-            a, b = np.asarray(cm.arrays[k]), np.asarray(v)
-            assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), (stem, k)

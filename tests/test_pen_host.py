@@ -1,17 +1,17 @@
 """CPU tests for myoHandPenTwirl{Fixed,Random}-v0 (envs/myo/myobase/pen_v0.py): registry entries, the committed myohand_pen fixture and
-its TrackEnv-class lowering with the plane - cylinder pair, the appended ABI ids, Model.with_body_quat, the float64 restatement of the
+its TrackEnv-class lowering with the plane - cylinder pair, Model.with_body_quat, the float64 restatement of the
 task's formulas (tests/pen_ref.py) on oracle states, its euler2quat against the reference's, and oracle states reaching one to four
 plane - cylinder contacts."""
 import os
-import re
 
 import numpy as np
 import pytest
 
+import hand_task_checks as H
+from hand_task_checks import ROOT
 from pen_ref import euler2quat, pen_restate
 from pen_states import branch_states
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IDS = ("myoHandPenTwirlFixed-v0", "myoHandPenTwirlRandom-v0")
 SITES = ("object_top", "object_bottom", "target_top", "target_bottom", "eps_ball")
 
@@ -33,7 +33,8 @@ def test_registry_entries_and_variants():
     for v in ids:
         assert envs.REGISTRY[v]["task"] == "pen" and v not in envs.UNSUPPORTED
     assert len(set(ids) | set(IDS)) == 8
-    assert {envs.REGISTRY[i[:3] + c + i[3:]]["muscle_condition"] for i in IDS for c in ("Sarc", "Fati", "Reaf")} == {"sarcopenia", "fatigue", "reafferentation"}
+    for i in IDS:
+        H.muscle_variants(i, H.CONDITIONS)
 
 
 def test_fixture_is_trk_class_with_plane_cylinder_pair(pen):
@@ -62,15 +63,6 @@ def test_plane_cylinder_refused_outside_trk_class(pen):
     a["geom_condim"] = np.where(a["geom_condim"] > 3, 3, a["geom_condim"])
     with pytest.raises(NotImplementedError, match="outside the TrackEnv"):
         lower(CompiledModel(arrays=a, names=pen.names))
-
-
-def test_abi_ids_are_appended():
-    from myosuite_mjx_amd import capi
-    hdr = open(os.path.join(ROOT, "include", "myo_hip.h")).read()
-    assert "MYO_F_BODYQUAT = MYO_F_BODYPOS_RANGE + 1" in hdr and re.search(r"^\s*MYO_F_BODYQUAT_RANGE,", hdr, flags=re.M)
-    assert (capi.F_BODYPOS_RANGE, capi.F_BODYQUAT, capi.F_BODYQUAT_RANGE) == (27, 28, 29)
-    assert "MYO_TASK_PEN = 8" in hdr and capi.TASK_PEN == 8
-    assert re.search(r"^\s*int quat_body;", hdr, flags=re.M) and capi.TaskConfig._fields_[-1] == ("quat_body", capi.C.c_int)
 
 
 def test_with_body_quat(pen):
@@ -104,8 +96,7 @@ def test_euler2quat_matches_reference():
 
 
 def _oracle_obs_inputs(o, m):
-    x = o.field("site_xpos").reshape(-1, 3)
-    sites = np.concatenate([x[m.name2id("site", n)] for n in SITES])
+    sites = H.site_xpos(o, m, SITES)
     xp = o.field("xpos").reshape(-1, 3)[m.name2id("body", "Object")]
     return sites, xp
 
@@ -117,10 +108,7 @@ def test_restatement_on_oracle_states(pen):
     q = np.array(m.qpos0, float)
     q[:-6] = 0
     q[0] = -1.5
-    o.reset()
-    o.set_state(qpos=q)
-    o.forward()
-    sites, xp = _oracle_obs_inputs(o, m)
+    sites, xp = _oracle_obs_inputs(H.forward_at(o, q), m)
     assert np.allclose(xp, m.body_pos[m.name2id("body", "Object")]) and np.allclose(sites[12:], xp)     # eps_ball = the pen's start
     rng = np.random.default_rng(0)
     act, v = rng.uniform(0, 1, (1, 39)), rng.normal(0, 1, (1, 29))
@@ -139,10 +127,7 @@ def test_restatement_on_oracle_states(pen):
     for dq, d_exp, s_exp in (((0, 0, 0, 0, -th0, 0), False, True), ((0.08, 0, 0, 0, -th0, 0), True, False)):
         qq = q.copy()
         qq[-6:] = dq
-        o.reset()
-        o.set_state(qpos=qq)
-        o.forward()
-        sites, xp = _oracle_obs_inputs(o, m)
+        sites, xp = _oracle_obs_inputs(H.forward_at(o, qq), m)
         obs, rew, done, solved = pen_restate(qq, np.zeros((1, 29)), np.zeros((1, 39)), sites, xp, 0.01)
         assert done[0] == d_exp and solved[0] == s_exp
         pa = np.linalg.norm(obs[0, 38:41])
@@ -155,8 +140,5 @@ def test_oracle_reaches_every_plane_cylinder_branch(pen):
     pg = [g for g in range(m.ngeom) if m.geom_bodyid[g] == m.name2id("body", "Object")][0]
     o = Oracle(m.blob())
     for name, q, n in branch_states(m):
-        o.reset()
-        o.set_state(qpos=q)
-        o.forward()
-        cs = [c for c in o.contacts() if {int(c[7]), int(c[8])} == {0, pg}]
+        cs = [c for c in H.forward_at(o, q).contacts() if {int(c[7]), int(c[8])} == {0, pg}]
         assert len(cs) == n, (name, len(cs))

@@ -395,6 +395,7 @@ int myo_policy_act(myo_policy*, const float* obs_dev, int B, float* action_dev, 
                    int env_offset, void* stream);
 
 #include "myo_hip_sensors.h"
+#include "myo_hip_rewards.h"
 
 #ifdef __cplusplus
 }

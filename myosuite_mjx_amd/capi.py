@@ -26,6 +26,10 @@ BENCH_OBS, BENCH_FRESH_ACTIONS, BENCH_AUTORESET = 1, 2, 4
 ACTMAP_NONE, ACTMAP_MUSCLE_SIGMOID, ACTMAP_SIGMOID_FATIGUE, ACTMAP_SIGMOID_REAFFERENTATION, ACTMAP_CTRLRANGE = 0, 1, 2, 3, 4
 TASK_NONE, TASK_POSE, TASK_REACH, TASK_WALK, TASK_HOLD, TASK_STAND, TASK_TRACK, TASK_KEYTURN, TASK_PEN, TASK_BAODING, TASK_DIE = range(11)
 FLAG_BAD_STATE, FLAG_BAD_QACC, FLAG_CONTACT_OVERFLOW, FLAG_CAND_OVERFLOW, FLAG_SCHED_TIMEOUT = 1, 2, 4, 8, 16
+# reward terms and episode statistics (include/myo_hip_rewards.h): what MYO_F_REWARD holds, and the ids of the episode buffers with their dtypes
+RWD_DENSE, RWD_SPARSE = 0, 1
+EP_RUNNING, EP_LAST, EP_FINISHED, EP_COUNT = range(4)
+_EP_DTYPE = {EP_RUNNING: np.float32, EP_LAST: np.float32, EP_FINISHED: np.uint8, EP_COUNT: np.int32}
 
 
 class Dims(C.Structure):
@@ -188,6 +192,17 @@ def lib():
         L.myo_batch_set_fatigue_reset.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.myo_batch_enable_sensors.argtypes = [C.c_void_p]
         L.myo_model_nsensor.argtypes = [C.c_void_p]
+        L.myo_batch_rwd_ncol.argtypes = [C.c_void_p]
+        L.myo_batch_rwd_name.argtypes = [C.c_void_p, C.c_int]
+        L.myo_batch_rwd_name.restype = C.c_char_p
+        L.myo_batch_enable_rewards.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int]
+        L.myo_batch_rwd_row.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.myo_batch_rwd_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.myo_batch_enable_episode_stats.argtypes = [C.c_void_p]
+        L.myo_batch_episode_buffer.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.myo_batch_episode_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+        L.myo_episode_update.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.myo_episode_clear.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -353,6 +368,46 @@ class HipBatch:
 
     def obs_reset_only(self, stream=None):
         _chk(lib().myo_obs_reset_only(self.h, stream))
+
+    # -- reward terms and episode statistics (include/myo_hip_rewards.h) --
+    def rwd_names(self):
+        """Column names of the configured task's term row, `dense` last (empty: the task has no row)."""
+        return tuple(lib().myo_batch_rwd_name(self.h, i).decode() for i in range(lib().myo_batch_rwd_ncol(self.h)))
+
+    def enable_rewards(self, weights, mode=RWD_DENSE):
+        """Turn the term row on: one weight per column except dense; MYO_F_REWARD becomes the row's dense (RWD_SPARSE: sparse) column."""
+        w = np.ascontiguousarray(weights, np.float32)
+        _chk(lib().myo_batch_enable_rewards(self.h, _ptr(w), w.size, int(mode)))
+
+    def rwd_row_ptr(self):
+        p, pitch, width = C.c_void_p(), C.c_size_t(), C.c_size_t()
+        _chk(lib().myo_batch_rwd_row(self.h, C.byref(p), C.byref(pitch), C.byref(width)))
+        return p.value, pitch.value, width.value
+
+    def read_rwd(self) -> np.ndarray:
+        out = np.empty((self.B, lib().myo_batch_rwd_ncol(self.h)), np.float32)
+        _chk(lib().myo_batch_rwd_read(self.h, out.ctypes.data, out.nbytes))
+        return out
+
+    def enable_episode_stats(self):
+        _chk(lib().myo_batch_enable_episode_stats(self.h))
+
+    def episode_ptr(self, which):
+        p, pitch, width = C.c_void_p(), C.c_size_t(), C.c_size_t()
+        _chk(lib().myo_batch_episode_buffer(self.h, int(which), C.byref(p), C.byref(pitch), C.byref(width)))
+        return p.value, pitch.value, width.value
+
+    def read_episode(self, which) -> np.ndarray:
+        """Host copy of an episode buffer: EP_RUNNING / EP_LAST [B, 4] float32, EP_FINISHED [B] uint8, EP_COUNT [B] int32."""
+        out = np.empty((self.B, 4) if which in (EP_RUNNING, EP_LAST) else (self.B,), _EP_DTYPE[which])
+        _chk(lib().myo_batch_episode_read(self.h, int(which), out.ctypes.data, out.nbytes))
+        return out
+
+    def episode_update(self, max_episode_steps, stream=None):
+        _chk(lib().myo_episode_update(self.h, int(max_episode_steps), stream))
+
+    def episode_clear(self, stream=None):
+        _chk(lib().myo_episode_clear(self.h, stream))
 
     def _set_range(self, field, width, lo, hi):
         lo, hi = (np.broadcast_to(np.asarray(a, np.float32), (self.B, width)) for a in (lo, hi))

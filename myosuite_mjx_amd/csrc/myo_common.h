@@ -159,6 +159,12 @@ struct DevBatch {
   float* sens;             // [B][ntouch] MYO_F_SENSORDATA: summed normal force of the contacts a touch sensor counts
   float* cfrc;             // [B][ntouch + 1][3] MYO_F_CFRC: their summed world force on the model; last row = all contacts against world-fixed geoms
   int ntouch;
+  // reward terms (myo_batch_enable_rewards): one row per env = the task's terms | sparse | solved | done | dense, in the order of the
+  // reference's rwd_dict, written by the launch that writes MYO_F_REWARD; NULL: off (the kernels keep their fixed-weight sums)
+  float* rwd;              // [B][rwd_n]
+  const float* rwd_w;      // [rwd_n - 1] weight of every column but dense (weighted_reward_keys; 0: not summed)
+  int rwd_n;               // columns of a row, dense included
+  int rwd_sparse;          // 1: MYO_F_REWARD = the sparse column (rwd_mode "sparse"), 0: dense
 };
 #define NCX 48      // overflow contact rows ALLOCATED per env; a kernel with NC LDS slots uses 64 - NC of them: 64 contacts in all
 #define NCX2 96     // TRK models: 128 contacts, 32 in LDS + 96 rows; rows of the second bank also hold that contact's solver state
@@ -273,6 +279,16 @@ template <int G> __device__ __forceinline__ int grp_maxi(int x) {
 #pragma unroll
   for (int m = G / 2; m >= 1; m >>= 1) x = max(x, __shfl_xor(x, m, G));
   return x;
+}
+// the term row of env e from its N columns before dense (t = terms | sparse | solved | done): dense = sum_k w_k t_k (env_base.py sums
+// rwd_keys_wt.items() the same way), MYO_F_REWARD = dense or sparse.  Called by one lane per env, only when Bt.rwd is set
+template <int N> __device__ __forceinline__ void rwd_row(const DevBatch& Bt, int e, const float (&t)[N]) {
+  float* r = Bt.rwd + (size_t)e * (N + 1);
+  float dense = 0.f;
+#pragma unroll
+  for (int k = 0; k < N; k++) { r[k] = t[k]; dense += Bt.rwd_w[k] * t[k]; }
+  r[N] = dense;
+  Bt.reward[e] = Bt.rwd_sparse ? t[N - 3] : dense;
 }
 #define SYNC() __syncthreads()
 // position of this lane among the set lanes of its G-lane group, and the group's set count

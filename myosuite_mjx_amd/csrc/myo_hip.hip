@@ -12,6 +12,7 @@
 //   myo_task_*.h        key-turn, pen, baoding, die, classic MyoDM: a task's observation body, its configure checks and its hook record
 //   myo_host_model.h    myo_model_load in pieces: blob view, table upload, packing of the per-lane records, kernel class
 //   myo_host_batch.h    batch creation, the per-env override records, the table of fields behind myo_batch_field / read / write
+//   myo_rewards.h       reward-term rows and episode statistics: column table per task, walk term kernel, statistics kernel, entry points
 //   myo_hip.hip         host side: task configuration, the table of step-kernel instantiations, launches, the task table, the extern "C" entry points
 //
 // Execution model: one environment = one wavefront = one workgroup; the whole working set of an env (link
@@ -36,6 +37,7 @@
 #include "myo_task_myodm.h"
 #include "myo_host_model.h"
 #include "myo_host_batch.h"
+#include "myo_rewards.h"
 
 extern "C" {
 
@@ -103,6 +105,7 @@ int myo_batch_configure(myo_batch* b, const myo_task_config* c) {
   if (c->ntarget > b->ntarget_alloc || c->ntip > 8) return fail(MYO_E_ARG, "myo_batch_configure: ntarget/ntip too large");
   if (c->quat_body > 0) { int rc = set_quat_body(b, c->quat_body); if (rc) return rc; }
   if (c->task == MYO_TASK_WALK) return fail(MYO_E_ARG, "use myo_batch_configure_walk for the walk task");
+  if (b->db.rwd && rwd_cols(c->task).n != b->db.rwd_n) return fail(MYO_E_ARG, "reward terms are enabled for a task with other columns");
   T.init_qvel = nullptr; T.rnd = nullptr;
   T.terrain = 0; T.hf_n = 0;
   for (int k = 0; k < 3; k++) T.tip_lpos[k] = c->tip_lpos[k];
@@ -156,6 +159,7 @@ int myo_batch_set_geom_override(myo_batch* b, int geom_id, const float* lo, cons
 int myo_batch_configure_walk(myo_batch* b, const myo_walk_config* c) {
   if (!b || !c) return fail(MYO_E_ARG, "myo_batch_configure_walk: null");
   if (b->bm_on) return fail(MYO_E_UNSUPPORTED, "per-env body masses: the walk task uses model-wide mass totals");
+  if (b->db.rwd && rwd_cols(MYO_TASK_WALK).n != b->db.rwd_n) return fail(MYO_E_ARG, "reward terms are enabled for a task with other columns");
   const myo_model* m = b->model;
   const DevModel& dm = m->dm;
   const int nq = m->nq, nv = dm.nv, nu = dm.nu, nb = (int)m->body_link.size();
@@ -435,6 +439,8 @@ static int launch_step(myo_batch* b, const float* action, int actmap, int nsub, 
     hipLaunchKernelGGL(k.fn, dim3(wgrid), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm, (const DevModelW*)m->d_dw, b->db, action, actmap,
                        nsub, st, order, wk, kflags, S);
     HIPCHK(hipGetLastError());
+    // walk task with the term row on: the row and MYO_F_REWARD of every launch whose fused pass wrote the reward
+    if (wk && b->db.rwd && !(kflags & KF_OBS_ONLY)) return walk_terms_launch(b, s);
     return MYO_OK;
   }
   if (G == 16) hipLaunchKernelGGL(step_kernel<16>, dim3(grid), dim3(64), lds, s, m->dm, b->db, action, actmap, nsub, st);

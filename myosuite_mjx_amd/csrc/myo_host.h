@@ -50,6 +50,10 @@ struct myo_model {
   std::vector<double> site_pos0;   // compiled site_pos (site in its body's frame): the baoding task's moving targets keep its z
 };
 
+// episode statistics (myo_batch_enable_episode_stats): running and last-finished rows [B][4] = dense return, sparse return, length, solved
+// steps; a byte per env raised by the update that ended its episode; episodes ended per env.  run == nullptr: off
+struct myo_episode { float *run = nullptr, *last = nullptr; uint8_t* finished = nullptr; int* count = nullptr; };
+
 struct myo_batch {
   const myo_model* model = nullptr;
   DevBatch db{};
@@ -77,6 +81,7 @@ struct myo_batch {
   bool bp_on = false;            // per-env root-body offset started (DevBatch.bpos / bpos_range allocated)
   int bq_body = -1;              // body of MYO_F_BODYQUAT (myo_task_config.quat_body; -1: none selected)
   bool sens_on = false;          // touch sensors / contact forces enabled (DevBatch.sens / cfrc allocated)
+  myo_episode episode;           // episode statistics (device buffers in dev_allocs)
   bool bq_on = false;            // per-env body orientation started (DevBatch.bquat / bquat_range / bq_c / bq_flag allocated)
   std::vector<hipEvent_t> kev;   // per-launch event pairs around the step kernel (bench only)
   int kev_pending = 0;           // pairs recorded by asynchronous bench calls and not collected yet

@@ -292,9 +292,11 @@ __device__ __forceinline__ void obs_body(const DevModel& M, const DevBatch& Bt, 
     if (lane == 0) {
       float bonus = (dist < T.pose_thd ? 1.f : 0.f) + (dist < 1.5f * T.pose_thd ? 1.f : 0.f);
       float pen = dist > T.far_th ? -1.f : 0.f;
-      Bt.reward[e] = T.w_pose * (-dist) + T.w_bonus * bonus + T.w_act_reg * (-actn) + T.w_penalty * pen;
-      Bt.solved[e] = dist < T.pose_thd ? 1.f : 0.f;
-      Bt.done[e] = dist > T.far_th ? 1.f : 0.f;
+      const float solved = dist < T.pose_thd ? 1.f : 0.f, done = dist > T.far_th ? 1.f : 0.f;
+      if (Bt.rwd) rwd_row(Bt, e, {-dist, bonus, pen, -actn, -dist, solved, done});        // pose_v0.py:118-135
+      else Bt.reward[e] = T.w_pose * (-dist) + T.w_bonus * bonus + T.w_act_reg * (-actn) + T.w_penalty * pen;
+      Bt.solved[e] = solved;
+      Bt.done[e] = done;
     }
   } else if (T.task == MYO_TASK_STAND) {
     // walk_v0.py:68-127 (ReachEnvV0 on the legs).  The tip site rides on the free root link: world position = root position + R(root quat) tip_lpos
@@ -321,8 +323,10 @@ __device__ __forceinline__ void obs_body(const DevModel& M, const DevBatch& Bt, 
       const float far_th = Bt.time[e] > 2.f * dt ? T.far_th : 1e30f;
       const float bonus = (dist < 2.f * T.near_th ? 1.f : 0.f) + (dist < T.near_th ? 1.f : 0.f);
       const float pen = dist > far_th ? 1.f : 0.f;
-      Bt.reward[e] = T.w_reach * (10.0f - dist - 10.0f * veld) + T.w_bonus * bonus + T.w_act_reg * (-100.0f * actn) + T.w_penalty * (-pen);
-      Bt.solved[e] = dist < T.near_th ? 1.f : 0.f;
+      const float solved = dist < T.near_th ? 1.f : 0.f;
+      if (Bt.rwd) rwd_row(Bt, e, {10.0f - dist - 10.0f * veld, bonus, -100.0f * actn, -pen, -dist, solved, pen});   // walk_v0.py:117-133
+      else Bt.reward[e] = T.w_reach * (10.0f - dist - 10.0f * veld) + T.w_bonus * bonus + T.w_act_reg * (-100.0f * actn) + T.w_penalty * (-pen);
+      Bt.solved[e] = solved;
       Bt.done[e] = pen;
     }
   } else if (T.task == MYO_TASK_TRACK) {
@@ -352,8 +356,10 @@ __device__ __forceinline__ void obs_body(const DevModel& M, const DevBatch& Bt, 
     if (lane == 0) {
       float bonus = (dist < 2.f * T.near_th ? 1.f : 0.f) + (dist < T.near_th ? 1.f : 0.f);
       float drop = dist > T.far_th ? 1.f : 0.f;
-      Bt.reward[e] = T.w_reach * (-dist) + T.w_bonus * bonus + T.w_act_reg * (-actn) + T.w_penalty * (-drop);
-      Bt.solved[e] = dist < T.near_th ? 1.f : 0.f;
+      const float solved = dist < T.near_th ? 1.f : 0.f;
+      if (Bt.rwd) rwd_row(Bt, e, {-dist, bonus, -actn, -drop, -dist, solved, drop});      // obj_hold_v0.py:102-117
+      else Bt.reward[e] = T.w_reach * (-dist) + T.w_bonus * bonus + T.w_act_reg * (-actn) + T.w_penalty * (-drop);
+      Bt.solved[e] = solved;
       Bt.done[e] = drop;
     }
   }
@@ -440,9 +446,11 @@ __global__ void __launch_bounds__(64) reach_obs_kernel(DevModel M, DevBatch Bt, 
       float near_th = T.near_th, far_th = Bt.time[env] > 2 * dt ? T.far_th : 1e30f;
       float bonus = (dist < 2 * near_th ? 1.f : 0.f) + (dist < near_th ? 1.f : 0.f);
       float pen = dist > far_th ? -1.f : 0.f;
-      Bt.reward[env] = T.w_reach * (-dist) + T.w_bonus * bonus + T.w_act_reg * (-actn) + T.w_penalty * pen;
-      Bt.solved[env] = dist < near_th ? 1.f : 0.f;
-      Bt.done[env] = dist > far_th ? 1.f : 0.f;
+      const float solved = dist < near_th ? 1.f : 0.f, done = dist > far_th ? 1.f : 0.f;
+      if (Bt.rwd) rwd_row(Bt, env, {-dist, bonus, -actn, pen, -dist, solved, done});      // reach_v0.py:126-141
+      else Bt.reward[env] = T.w_reach * (-dist) + T.w_bonus * bonus + T.w_act_reg * (-actn) + T.w_penalty * pen;
+      Bt.solved[env] = solved;
+      Bt.done[env] = done;
     }
   }
 }

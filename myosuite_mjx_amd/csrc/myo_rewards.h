@@ -1,0 +1,190 @@
+// myo_rewards.h -- reward-term rows and episode statistics (include/myo_hip_rewards.h): the column table per task, the walk task's term
+// kernel, the episode-statistics kernel and the host entry points.  The other tasks write their rows in their own observation kernels
+// (rwd_row, myo_common.h).  Included by myo_hip.hip after myo_host_batch.h.
+#ifndef MYO_REWARDS_H
+#define MYO_REWARDS_H
+
+// ---- columns: the keys of the reference's rwd_dict per env class, in its order; every row ends sparse, solved, done, dense
+#define RWD_TAIL "sparse", "solved", "done", "dense"
+static const char* const rwd_pose[] = {"pose", "bonus", "penalty", "act_reg", RWD_TAIL};                                        // pose_v0.py:118-135
+static const char* const rwd_reach[] = {"reach", "bonus", "act_reg", "penalty", RWD_TAIL};                                      // reach_v0.py:126-141, walk_v0.py:117-133
+static const char* const rwd_hold[] = {"goal_dist", "bonus", "act_reg", "penalty", RWD_TAIL};                                   // obj_hold_v0.py:102-117
+static const char* const rwd_keyturn[] = {"key_turn", "IFtip_approach", "THtip_approach", "act_reg", "bonus", "penalty", RWD_TAIL};   // key_turn_v0.py:134-152
+static const char* const rwd_pen[] = {"pos_align", "rot_align", "act_reg", "drop", "bonus", RWD_TAIL};                          // pen_v0.py:150-167
+static const char* const rwd_walk[] = {"vel_reward", "cyclic_hip", "ref_rot", "joint_angle_rew", "act_mag", RWD_TAIL};          // walk_v0.py:298-311
+static const char* const rwd_baoding[] = {"pos_dist_1", "pos_dist_2", "act_reg", RWD_TAIL};                                     // baoding_v1.py:239-262
+static const char* const rwd_die[] = {"pos_dist", "rot_dist", "bonus", "act_reg", "penalty", RWD_TAIL};                         // reorient_v0.py:148-176
+#undef RWD_TAIL
+struct RwdCols { const char* const* name; int n; };
+#define RWD_COLS(a) RwdCols{a, (int)(sizeof a / sizeof a[0])}
+static RwdCols rwd_cols(int task) {
+  switch (task) {
+    case MYO_TASK_POSE: return RWD_COLS(rwd_pose);
+    case MYO_TASK_REACH: case MYO_TASK_STAND: return RWD_COLS(rwd_reach);
+    case MYO_TASK_HOLD: return RWD_COLS(rwd_hold);
+    case MYO_TASK_KEYTURN: return RWD_COLS(rwd_keyturn);
+    case MYO_TASK_PEN: return RWD_COLS(rwd_pen);
+    case MYO_TASK_WALK: return RWD_COLS(rwd_walk);
+    case MYO_TASK_BAODING: return RWD_COLS(rwd_baoding);
+    case MYO_TASK_DIE: return RWD_COLS(rwd_die);
+    default: return RwdCols{nullptr, 0};   // no task, or the MyoDM track task (its terms are MYO_F_METRICS)
+  }
+}
+#undef RWD_COLS
+
+// ---- walk task: the step kernel's fused pass keeps its fixed-weight sum; with the term row on, this kernel follows every launch of it
+// that wrote MYO_F_REWARD and restates the terms from what that pass stored -- the observation row (qpos[2:], COM velocity, feet heights, COM
+// height, phase: the float32 values the fused pass computed its own terms from) -- plus the activations for act_mag.  One wave per env
+__global__ void __launch_bounds__(64) walk_terms_kernel(DevBatch Bt, const DevWalk* __restrict__ wk, int nq, int nv, int nu, int na) {
+  const int e = blockIdx.x, lane = threadIdx.x;
+  if (e >= Bt.B) return;
+  const float* a = Bt.act + (size_t)e * nu;
+  float act2 = 0.f;
+  for (int i = lane; i < nu; i += 64) { const float ai = a[i]; act2 += ai * ai; }
+  const float act_mag = sqrtf(wave_sum(act2)) / (float)(na > 0 ? na : 1);   // walk_v0.py:291-295 (0 without muscles: act stays zero)
+  if (lane != 0) return;
+  const float* o = Bt.obs + (size_t)e * wk->obs_dim;
+  auto qp = [&](int i) { return o[i - 2]; };    // qpos[i], i >= 2: the row starts with qpos_without_xy
+  const int sb = nq - 2 + nv;
+  const float cvx = o[sb], cvy = o[sb + 1], fl = o[sb + 6], fr = o[sb + 7], height = o[sb + 8], phase = o[sb + 15];
+  const float q[4] = {qp(3), qp(4), qp(5), qp(6)};
+  const float dvy = wk->target_y_vel - cvy, dvx = wk->target_x_vel - cvx;
+  const float vel_reward = expf(-dvy * dvy) + expf(-dvx * dvx);
+  const float d0 = 0.8f * cosf(phase * 6.283185307179586f + 3.141592653589793f) - qp(wk->qadr_hfl);
+  const float d1 = 0.8f * cosf(phase * 6.283185307179586f) - qp(wk->qadr_hfr);
+  const float cyclic = sqrtf(d0 * d0 + d1 * d1);
+  const float dq[4] = {q[0] - wk->target_rot[0], q[1] - wk->target_rot[1], q[2] - wk->target_rot[2], q[3] - wk->target_rot[3]};
+  const float ref_rot = expf(-5.0f * sqrtf(dq[0] * dq[0] + dq[1] * dq[1] + dq[2] * dq[2] + dq[3] * dq[3]));
+  const float mag = 0.25f * (fabsf(qp(wk->qadr_ja[0])) + fabsf(qp(wk->qadr_ja[1])) + fabsf(qp(wk->qadr_ja[2])) + fabsf(qp(wk->qadr_ja[3])));
+  const float ja = expf(-5.0f * mag);
+  const float r00 = 1.0f - 2.0f * (q[2] * q[2] + q[3] * q[3]) / (q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  float done = (height < wk->min_height || fabsf(r00) > wk->max_rot) ? 1.f : 0.f;
+  if (wk->knee_height > 0.f && height - 0.5f * (fl + fr) < wk->knee_height) done = 1.f;
+  rwd_row(Bt, e, {vel_reward, cyclic, ref_rot, ja, act_mag, vel_reward, vel_reward >= 1.0f ? 1.f : 0.f, done});
+}
+
+// ---- episode statistics: one thread per env, once per env step after the observation pass and before the auto-reset.  The running row
+// gains (dense, sparse, 1, solved); an env whose episode ends by reset_kernel's rule hands its row to `last`, raises its byte and starts anew
+__global__ void __launch_bounds__(256) episode_stats_kernel(DevBatch Bt, float4* __restrict__ run, float4* __restrict__ last, uint8_t* __restrict__ finished,
+                                                           int* __restrict__ count, int max_steps) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= Bt.B) return;
+  const float* r = Bt.rwd + (size_t)e * Bt.rwd_n;
+  float4 s = run[e];
+  s.x += r[Bt.rwd_n - 1]; s.y += r[Bt.rwd_n - 4]; s.z += 1.f; s.w += Bt.solved[e];
+  const bool end = Bt.done[e] > 0.f || Bt.elapsed[e] >= max_steps;
+  if (end) { last[e] = s; count[e] += 1; s = make_float4(0.f, 0.f, 0.f, 0.f); }
+  finished[e] = end ? 1 : 0;
+  run[e] = s;
+}
+
+// ---- host
+static int rewards_enable(myo_batch* b, const float* w, int nw, int mode) {
+  const RwdCols c = rwd_cols(b->task.task);
+  if (!c.n) return fail(MYO_E_UNSUPPORTED, "reward terms: no task with a term row is configured (the MyoDM track task reports MYO_F_METRICS)");
+  if (!w || nw != c.n - 1) return fail(MYO_E_ARG, "reward terms: one weight per column except dense");
+  if (mode != MYO_RWD_DENSE && mode != MYO_RWD_SPARSE) return fail(MYO_E_ARG, "reward terms: mode must be MYO_RWD_DENSE or MYO_RWD_SPARSE");
+  for (int k = 0; k < nw; k++) if (!std::isfinite(w[k])) return fail(MYO_E_ARG, "reward terms: weights must be finite");
+  if (b->task.task == MYO_TASK_WALK && g_lanes != 64) return fail(MYO_E_UNSUPPORTED, "reward terms: the walk task runs on the wave-per-env kernel only (lanes = 64)");
+  DevBatch& d = b->db;
+  if (d.rwd && d.rwd_n != c.n) return fail(MYO_E_ARG, "reward terms: enabled for another task");
+  HIPCHK(hipSetDevice(b->model->device));
+  int rc;
+  if (!d.rwd) {
+    float *row = nullptr, *wd = nullptr;
+    if ((rc = balloc(b, (void**)&row, (size_t)d.B * c.n * 4)) || (rc = balloc(b, (void**)&wd, (size_t)nw * 4))) return rc;
+    d.rwd = row; d.rwd_w = wd; d.rwd_n = c.n;
+  }
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy((void*)d.rwd_w, w, (size_t)nw * 4, hipMemcpyHostToDevice));
+  d.rwd_sparse = mode == MYO_RWD_SPARSE;
+  return MYO_OK;
+}
+
+static int walk_terms_launch(myo_batch* b, hipStream_t s) {
+  const myo_model* m = b->model;
+  hipLaunchKernelGGL(walk_terms_kernel, dim3(b->db.B), dim3(64), 0, s, b->db, (const DevWalk*)b->d_walk, m->nq, m->dm.nv, m->dm.nu, m->dm.na_obs);
+  HIPCHK(hipGetLastError());
+  return MYO_OK;
+}
+
+static int episode_enable(myo_batch* b) {
+  if (!b->db.rwd) return fail(MYO_E_ARG, "episode statistics: enable the reward terms first (myo_batch_enable_rewards)");
+  if (b->episode.run) return MYO_OK;
+  myo_episode ep;
+  const size_t B = b->db.B;
+  int rc;
+  HIPCHK(hipSetDevice(b->model->device));
+  if ((rc = balloc(b, (void**)&ep.run, B * 16)) || (rc = balloc(b, (void**)&ep.last, B * 16)) ||
+      (rc = balloc(b, (void**)&ep.finished, (B + 3) / 4 * 4)) || (rc = balloc(b, (void**)&ep.count, B * 4))) return rc;
+  b->episode = ep;
+  return MYO_OK;
+}
+
+int myo_batch_rwd_ncol(const myo_batch* b) { return b ? rwd_cols(b->task.task).n : 0; }
+const char* myo_batch_rwd_name(const myo_batch* b, int col) {
+  const RwdCols c = rwd_cols(b ? b->task.task : MYO_TASK_NONE);
+  return col >= 0 && col < c.n ? c.name[col] : nullptr;
+}
+int myo_batch_enable_rewards(myo_batch* b, const float* weights, int nweights, int mode) {
+  return b ? rewards_enable(b, weights, nweights, mode) : fail(MYO_E_ARG, "myo_batch_enable_rewards: null");
+}
+int myo_batch_rwd_row(myo_batch* b, void** dev_ptr, size_t* pitch, size_t* width) {
+  if (!b || !dev_ptr || !pitch || !width) return fail(MYO_E_ARG, "myo_batch_rwd_row: null");
+  if (!b->db.rwd) return fail(MYO_E_ARG, "reward terms are not enabled (myo_batch_enable_rewards)");
+  *dev_ptr = b->db.rwd; *pitch = *width = (size_t)b->db.rwd_n;
+  return MYO_OK;
+}
+static int host_copy(myo_batch* b, const void* dev, void* host, size_t nbytes, size_t want) {
+  if (!host || nbytes != want) return fail(MYO_E_ARG, "host copy: size mismatch");
+  HIPCHK(hipSetDevice(b->model->device));
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(host, dev, nbytes, hipMemcpyDeviceToHost));
+  return MYO_OK;
+}
+int myo_batch_rwd_read(myo_batch* b, void* host, size_t nbytes) {
+  void* p; size_t pitch, width;
+  const int rc = myo_batch_rwd_row(b, &p, &pitch, &width);
+  return rc ? rc : host_copy(b, p, host, nbytes, (size_t)b->db.B * width * 4);
+}
+int myo_batch_enable_episode_stats(myo_batch* b) { return b ? episode_enable(b) : fail(MYO_E_ARG, "myo_batch_enable_episode_stats: null"); }
+int myo_batch_episode_buffer(myo_batch* b, int which, void** dev_ptr, size_t* pitch, size_t* width) {
+  if (!b || !dev_ptr || !pitch || !width) return fail(MYO_E_ARG, "myo_batch_episode_buffer: null");
+  const myo_episode* ep = &b->episode;
+  if (!ep->run) return fail(MYO_E_ARG, "episode statistics are not enabled (myo_batch_enable_episode_stats)");
+  switch (which) {
+    case MYO_EP_RUNNING: *dev_ptr = ep->run; *width = 4; break;
+    case MYO_EP_LAST: *dev_ptr = ep->last; *width = 4; break;
+    case MYO_EP_FINISHED: *dev_ptr = ep->finished; *width = 1; break;
+    case MYO_EP_COUNT: *dev_ptr = ep->count; *width = 1; break;
+    default: return fail(MYO_E_ARG, "myo_batch_episode_buffer: unknown buffer");
+  }
+  *pitch = *width;
+  return MYO_OK;
+}
+int myo_batch_episode_read(myo_batch* b, int which, void* host, size_t nbytes) {
+  void* p; size_t pitch, width;
+  const int rc = myo_batch_episode_buffer(b, which, &p, &pitch, &width);
+  return rc ? rc : host_copy(b, p, host, nbytes, (size_t)b->db.B * width * (which == MYO_EP_FINISHED ? 1 : 4));
+}
+int myo_episode_update(myo_batch* b, int max_episode_steps, void* stream) {
+  if (!b || max_episode_steps <= 0) return fail(MYO_E_ARG, "myo_episode_update: bad arguments");
+  const myo_episode* ep = &b->episode;
+  if (!ep->run) return fail(MYO_E_ARG, "episode statistics are not enabled (myo_batch_enable_episode_stats)");
+  HIPCHK(hipSetDevice(b->model->device));
+  hipLaunchKernelGGL(episode_stats_kernel, dim3((b->db.B + 255) / 256), dim3(256), 0, (hipStream_t)stream, b->db, (float4*)ep->run, (float4*)ep->last,
+                     ep->finished, ep->count, max_episode_steps);
+  HIPCHK(hipGetLastError());
+  return MYO_OK;
+}
+int myo_episode_clear(myo_batch* b, void* stream) {
+  if (!b) return fail(MYO_E_ARG, "myo_episode_clear: null");
+  const myo_episode* ep = &b->episode;
+  if (!ep->run) return fail(MYO_E_ARG, "episode statistics are not enabled (myo_batch_enable_episode_stats)");
+  HIPCHK(hipSetDevice(b->model->device));
+  HIPCHK(hipMemsetAsync(ep->run, 0, (size_t)b->db.B * 16, (hipStream_t)stream));
+  HIPCHK(hipMemsetAsync(ep->finished, 0, (size_t)b->db.B, (hipStream_t)stream));
+  return MYO_OK;
+}
+
+#endif  // MYO_REWARDS_H

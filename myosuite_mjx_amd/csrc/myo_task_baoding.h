@@ -62,15 +62,25 @@ __device__ __forceinline__ void baoding_obs_body(const DevModel& M, const DevBat
   }
   for (int i = lane; i < nh; i += 64) o[i] = q[i];
   if (obs_only) return;
+  float actn = 0.f;
+  if (Bt.rwd) {   // act_reg (baoding_v1.py:220-222) is a column of the term row only: the registered reward does not weigh it
+    const int nu = M.nu;
+    const float* a = Bt.act + (size_t)e * nu;
+    float act2 = 0.f;
+    for (int i = lane; i < nu; i += 64) { const float ai = a[i]; if (M.act_obs[i] >= 0) act2 += ai * ai; }
+    actn = sqrtf(wave_sum(act2)) / (float)(M.na_obs > 0 ? M.na_obs : 1);
+  }
   if (lane == 0) {
     float d1[3], d2[3];
 #pragma unroll
     for (int c = 0; c < 3; c++) { d1[c] = x[2][c] - x[0][c]; d2[c] = x[3][c] - x[1][c]; }
     const float n1 = norm3(d1), n2 = norm3(d2);
     const bool fall = x[0][2] < T.far_th || x[1][2] < T.far_th;
-    Bt.reward[e] = T.w_pose * (-n1) + T.w_reach * (-n2);
-    Bt.solved[e] = (n1 < T.pose_thd && n2 < T.pose_thd && !fall) ? 1.f : 0.f;
-    Bt.done[e] = fall ? 1.f : 0.f;
+    const float solved = (n1 < T.pose_thd && n2 < T.pose_thd && !fall) ? 1.f : 0.f, done = fall ? 1.f : 0.f;
+    if (Bt.rwd) rwd_row(Bt, e, {-n1, -n2, -actn, -(n1 + n2), solved, done});               // baoding_v1.py:239-262
+    else Bt.reward[e] = T.w_pose * (-n1) + T.w_reach * (-n2);
+    Bt.solved[e] = solved;
+    Bt.done[e] = done;
   }
 }
 

@@ -97,9 +97,11 @@ __device__ __forceinline__ void die_obs_body(const DevModel& M, const DevBatch& 
     const float pos_dist = norm3(perr), rot_dist = norm3(rerr);
     const bool drop = pos_dist > T.far_th;
     const float bonus = (pos_dist < 2.f * T.near_th ? 1.f : 0.f) + (pos_dist < T.near_th ? 1.f : 0.f);
-    Bt.reward[e] = T.w_pose * (-pos_dist) + T.w_reach * (-rot_dist) + T.w_bonus * bonus + T.w_act_reg * (-actn) + T.w_penalty * (drop ? -1.f : 0.f);
-    Bt.solved[e] = (pos_dist < T.near_th && rot_dist < T.pose_thd && !drop) ? 1.f : 0.f;
-    Bt.done[e] = drop ? 1.f : 0.f;
+    const float solved = (pos_dist < T.near_th && rot_dist < T.pose_thd && !drop) ? 1.f : 0.f, done = drop ? 1.f : 0.f;
+    if (Bt.rwd) rwd_row(Bt, e, {-pos_dist, -rot_dist, bonus, -actn, -done, -rot_dist - 10.0f * pos_dist, solved, done});   // reorient_v0.py:148-176
+    else Bt.reward[e] = T.w_pose * (-pos_dist) + T.w_reach * (-rot_dist) + T.w_bonus * bonus + T.w_act_reg * (-actn) + T.w_penalty * (drop ? -1.f : 0.f);
+    Bt.solved[e] = solved;
+    Bt.done[e] = done;
   }
 }
 

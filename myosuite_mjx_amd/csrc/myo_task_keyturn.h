@@ -93,9 +93,11 @@ __device__ __forceinline__ void keyturn_obs_body(const DevModel& M, const DevBat
     const float key_q = q[nh];
     const float bonus = (key_q > 1.57079632679489662f ? 1.f : 0.f) + (key_q > 3.14159265358979324f ? 1.f : 0.f);
     const float pen = -(d_if > 0.5f * T.far_th ? 1.f : 0.f) - (d_th > 0.5f * T.far_th ? 1.f : 0.f);
-    Bt.reward[e] = T.w_pose * key_q + T.w_reach * (-d_if) + T.w_reach * (-d_th) + T.w_act_reg * (-actn) + T.w_bonus * bonus + T.w_penalty * pen;
-    Bt.solved[e] = key_q > T.pose_thd ? 1.f : 0.f;
-    Bt.done[e] = (d_if > T.far_th || d_th > T.far_th) ? 1.f : 0.f;
+    const float solved = key_q > T.pose_thd ? 1.f : 0.f, done = (d_if > T.far_th || d_th > T.far_th) ? 1.f : 0.f;
+    if (Bt.rwd) rwd_row(Bt, e, {key_q, -d_if, -d_th, -actn, bonus, pen, key_q, solved, done});   // key_turn_v0.py:134-152
+    else Bt.reward[e] = T.w_pose * key_q + T.w_reach * (-d_if) + T.w_reach * (-d_th) + T.w_act_reg * (-actn) + T.w_bonus * bonus + T.w_penalty * pen;
+    Bt.solved[e] = solved;
+    Bt.done[e] = done;
   }
 }
 

@@ -77,9 +77,11 @@ __device__ __forceinline__ void pen_obs_body(const DevModel& M, const DevBatch& 
     const bool dropped = pos_align > T.far_th;
     const float near = pos_align < T.far_th ? 1.f : 0.f;
     const float bonus = (rot_align > 0.9f ? 1.f : 0.f) * near + 5.f * (rot_align > 0.95f ? 1.f : 0.f) * near;
-    Bt.reward[e] = T.w_pose * (-pos_align) + T.w_reach * rot_align + T.w_act_reg * (-actn) + T.w_penalty * (dropped ? -1.f : 0.f) + T.w_bonus * bonus;
-    Bt.solved[e] = (rot_align > T.pose_thd && !dropped) ? 1.f : 0.f;
-    Bt.done[e] = dropped ? 1.f : 0.f;
+    const float solved = (rot_align > T.pose_thd && !dropped) ? 1.f : 0.f, done = dropped ? 1.f : 0.f;
+    if (Bt.rwd) rwd_row(Bt, e, {-pos_align, rot_align, -actn, -done, bonus, -pos_align + rot_align, solved, done});   // pen_v0.py:150-167
+    else Bt.reward[e] = T.w_pose * (-pos_align) + T.w_reach * rot_align + T.w_act_reg * (-actn) + T.w_penalty * (dropped ? -1.f : 0.f) + T.w_bonus * bonus;
+    Bt.solved[e] = solved;
+    Bt.done[e] = done;
   }
 }
 

@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import capi, tasks, track
+from . import capi, rewards, tasks, track
 from . import model as _model
 from .capi import _DevArray  # noqa: F401  (sim.py takes it from here)
 
@@ -252,6 +252,12 @@ class BatchedMyoEnv(capi.FieldViews):
     step(action[B, nu] in [-1, 1]) -> (obs[B, obs_dim] f32, reward[B], terminated[B] bool, truncated[B] bool, info)
     following envs/env_base.py:335-365.  Finished episodes (done, or max_episode_steps like gym's TimeLimit)
     are reset in place and the returned obs row is the first observation of the new episode.
+
+    rwd_dict=True (implied by weighted_reward_keys={key: weight}, rwd_mode="sparse" or episode_stats=True) adds the reference's reward
+    dictionary to info (env_base.py:559-570): info["rwd_dict"][key] for key in `rwd_keys`, info["rwd_dense"], info["rwd_sparse"]; the
+    weights re-weight or drop terms (None: the registered ones), rwd_mode picks the column step() returns.  episode_stats=True adds
+    info["episode"] = {"finished", "r", "r_sparse", "l", "solved"}: the statistics of each env's last finished episode, which the in-place
+    reset would otherwise wipe.  With the defaults nothing is allocated and no launch is added.
     """
 
     # env kwargs of the reference that gym.make forwards to the env class and that are honoured here (others raise): the task records' tables
@@ -260,7 +266,8 @@ class BatchedMyoEnv(capi.FieldViews):
     KEYTURN_KWARGS = tasks.TASKS["keyturn"].kwargs
     _target_jnt_range = staticmethod(tasks.target_jnt_range)
 
-    def __init__(self, env_id, num_envs=1, device=0, seed=0, env_offset=0, autoreset=True, as_torch=True, sensors=False, **env_kwargs):
+    def __init__(self, env_id, num_envs=1, device=0, seed=0, env_offset=0, autoreset=True, as_torch=True, sensors=False,
+                 rwd_dict=False, weighted_reward_keys=None, rwd_mode="dense", episode_stats=False, **env_kwargs):
         if env_id in UNSUPPORTED:
             raise NotImplementedError(f"{env_id}: {UNSUPPORTED[env_id]}")
         if env_id not in REGISTRY:
@@ -268,6 +275,9 @@ class BatchedMyoEnv(capi.FieldViews):
         self.id = env_id
         self.spec = spec = dict(REGISTRY[env_id])
         tasks.filter_kwargs(env_id, spec, env_kwargs)
+        # reward terms: any of the four parameters turns the term row on (rewards.resolve: KeyError / ValueError before anything is loaded)
+        self._rwd = rewards.resolve(env_id, spec, rwd_dict, weighted_reward_keys, rwd_mode, episode_stats)
+        self.rwd_dict, self.episode_stats, self.rwd_mode = self._rwd is not None, bool(episode_stats), rwd_mode
         self.num_envs, self.device, self.seed, self.autoreset, self.as_torch = int(num_envs), device, int(seed), autoreset, as_torch
         self.mjmodel = m = _model.load_asset(spec["model"])
         self.muscle_condition = spec.get("muscle_condition", "")
@@ -288,6 +298,12 @@ class BatchedMyoEnv(capi.FieldViews):
         if s.body_mass_range is not None:
             self.set_body_mass_range(*s.body_mass_range)
         self.obs_dim = s.obs_dim
+        if self.rwd_dict:      # nothing is allocated and no launch is added without it
+            keys, w, mode = self._rwd
+            assert self.batch.rwd_names() == keys, (self.batch.rwd_names(), keys)
+            self.batch.enable_rewards(w, capi.RWD_SPARSE if mode == "sparse" else capi.RWD_DENSE)
+            if self.episode_stats:
+                self.batch.enable_episode_stats()
         self._obs_in_step = s.call == "configure_walk"                 # the walk task's observation / reward pass is fused into the step kernel
         self._set_condition(m, spec)
         self.act_dim = m.nu
@@ -380,12 +396,66 @@ class BatchedMyoEnv(capi.FieldViews):
         v = self.view(capi.F_CFRC)
         return v.view(self.num_envs, -1, 3) if self.as_torch else v.reshape(self.num_envs, -1, 3)
 
+    # -- reward terms and episode statistics (make(..., rwd_dict=True / weighted_reward_keys= / rwd_mode= / episode_stats=True)) ---------
+    @property
+    def rwd_keys(self):
+        """Column names of the task's reward-term row, in the order of the reference's rwd_dict, `dense` last."""
+        return rewards.RWD_KEYS[self.spec["task"]]
+
+    @property
+    def rwd_weights(self):
+        """{key: weight} of the columns `dense` sums (the others have weight 0)."""
+        if not self.rwd_dict:
+            raise AttributeError(f"{self.id}: made without rwd_dict=True")
+        return {k: float(w) for k, w in zip(self.rwd_keys, self._rwd[1]) if w != 0}
+
+    def _dev_view(self, name, ptr, shape, typestr):
+        if name not in self._views:
+            self._views[name] = self._torch.as_tensor(capi._DevArray(ptr, shape, typestr, self.batch), device=f"cuda:{self.device}")
+        return self._views[name]
+
+    @property
+    def rwd_terms(self):
+        """[num_envs, len(rwd_keys)] term row of the last step: a torch view of the library's buffer (no copy); as_torch=False: a numpy copy."""
+        if not self.rwd_dict:
+            raise AttributeError(f"{self.id}: made without rwd_dict=True")
+        if self._torch is None:
+            return self.batch.read_rwd()
+        return self._dev_view("rwd", self.batch.rwd_row_ptr()[0], (self.num_envs, len(self.rwd_keys)), "<f4")
+
+    def _episode_buffer(self, which):
+        if self._torch is None:
+            return self.batch.read_episode(which)
+        shape = (self.num_envs, 4) if which in (capi.EP_RUNNING, capi.EP_LAST) else (self.num_envs,)
+        return self._dev_view(("episode", which), self.batch.episode_ptr(which)[0], shape, {capi.EP_FINISHED: "|u1", capi.EP_COUNT: "<i4"}.get(which, "<f4"))
+
+    @property
+    def episode_count(self):
+        """[num_envs] int32 episodes ended so far per env (episode_stats=True)."""
+        if not self.episode_stats:
+            raise AttributeError(f"{self.id}: made without episode_stats=True")
+        return self._episode_buffer(capi.EP_COUNT)
+
+    def _reward_info(self, info):
+        """info["rwd_dict"] / ["rwd_dense"] / ["rwd_sparse"] (env_base.py:559-570) from the term row: one column view per key."""
+        row = self.rwd_terms
+        info["rwd_dict"] = {k: row[:, i] for i, k in enumerate(self.rwd_keys)}
+        info["rwd_dense"], info["rwd_sparse"] = info["rwd_dict"]["dense"], info["rwd_dict"]["sparse"]
+
+    def _episode_info(self, info):
+        """info["episode"]: which envs' episodes the step ended and the statistics of each env's last finished episode."""
+        last, fin = self._episode_buffer(capi.EP_LAST), self._episode_buffer(capi.EP_FINISHED)
+        i32 = (lambda x: x.to(self._torch.int32)) if self._torch is not None else (lambda x: x.astype(np.int32))
+        info["episode"] = {"finished": fin > 0, "r": last[:, 0], "r_sparse": last[:, 1], "l": i32(last[:, 2]), "solved": i32(last[:, 3])}
+
     # -- gym API -------------------------------------------------------------------------------------------
     def reset(self, seed=None):
         if seed is not None:
             self._episode_seed = int(seed)
         s = self._stream()
         self.batch.reset(None, self._episode_seed, s)
+        if self.episode_stats:
+            self.batch.episode_clear(s)
         self.batch.obs(s)
         return self.view(capi.F_OBS)
 
@@ -413,10 +483,16 @@ class BatchedMyoEnv(capi.FieldViews):
             done = self.batch.read(capi.F_DONE)[:, 0] > 0
             truncated = (self.batch.read(capi.F_ELAPSED)[:, 0] >= self.max_episode_steps) & ~done
             solved = self.batch.read(capi.F_SOLVED)[:, 0] > 0
+        info = {"solved": solved}
+        if self.rwd_dict:
+            self._reward_info(info)
+        if self.episode_stats:     # after the observation pass, before the auto-reset clears done / elapsed
+            self.batch.episode_update(self.max_episode_steps, s)
+            self._episode_info(info)
         if self.autoreset:
             self.batch.autoreset(self.max_episode_steps, self._episode_seed, s)
             self.batch.obs_reset_only(s)
-        info = {"solved": solved, "time": self.view(capi.F_TIME)}
+        info["time"] = self.view(capi.F_TIME)
         return self.view(capi.F_OBS), reward, done, truncated, info
 
     # -- state access (env_base.py:643-705 get_env_state / set_env_state) ----------------------------------
@@ -442,7 +518,10 @@ def _enable_sensors(env_id, batch):
         raise NotImplementedError(f"{env_id}: sensors=True is not available: {e}") from None
 
 
-def _make_track(env_id, num_envs, reference=None, flavour="mjx", sensors=False, **kw):
+def _make_track(env_id, num_envs, reference=None, flavour="mjx", sensors=False, rwd_dict=False, episode_stats=False, **kw):
+    if rwd_dict or episode_stats:
+        raise NotImplementedError(f"{env_id}: rwd_dict / episode_stats are not offered for the MyoDM ids; their reward terms (pose, object, bonus, "
+                                  'penalty) are info["metrics"] of every step')
     if flavour not in ("mjx", "classic"):
         raise ValueError(f"{env_id}: flavour must be 'mjx' (mjx/myodm_v0.py, the default) or 'classic' (envs/myo/myodm/myodm_v0.py), got {flavour!r}")
     reference = _myodm_reference(env_id, reference)

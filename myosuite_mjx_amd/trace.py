@@ -51,8 +51,16 @@ def rollout(env, policy=None, horizon=100, seed=None, name=None) -> dict:
     obs = env.reset(seed=seed)
     rec = {k: [] for k in ("time", "observations", "actions", "rewards", "done", "env_infos/time", "env_infos/rwd_dense", "env_infos/solved",
                            "env_infos/done", *[f"env_infos/state/{k}" for k in STATE_KEYS])}
+    # an env made with its reward-term row also logs env_infos/rwd_sparse and env_infos/rwd_dict/<key> (env_base.py:559-570)
+    term_keys = tuple(env.rwd_keys) if getattr(env, "rwd_dict", False) else ()
+    terms = {k: np.zeros(B, np.float32) for k in term_keys}
+    rec.update({k: [] for k in (("env_infos/rwd_sparse",) if term_keys else ()) + tuple(f"env_infos/rwd_dict/{k}" for k in term_keys)})
 
     def log(obs, act, rwd, done, solved):
+        if term_keys:
+            rec["env_infos/rwd_sparse"].append(terms["sparse"])
+            for k in term_keys:
+                rec[f"env_infos/rwd_dict/{k}"].append(terms[k])
         st = env.get_env_state()
         t = st["time"].reshape(B)
         rec["time"].append(t); rec["observations"].append(host(obs)); rec["actions"].append(act)
@@ -69,6 +77,7 @@ def rollout(env, policy=None, horizon=100, seed=None, name=None) -> dict:
             break
         obs, r, d, trunc, info = env.step(env._torch.as_tensor(act, device=obs.device) if env.as_torch else act)
         rwd, solved = host(r).astype(np.float32), host(info["solved"]).astype(bool)
+        terms = {k: host(info["rwd_dict"][k]).astype(np.float32) for k in term_keys}
         done = done | host(d).astype(bool)
     log(obs, np.full((B, env.act_dim), np.nan, np.float32), rwd, done, solved)
     steps = {k: np.stack(v) for k, v in rec.items()}

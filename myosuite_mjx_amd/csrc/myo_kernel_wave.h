@@ -152,6 +152,19 @@ template <int NVT> __device__ __forceinline__ float chol_rows(float (&r)[NVT], i
   return invd;
 }
 #include "myo_ldl_mfma.h"
+// 0: the dynamics stage writes M symmetrically into the square buffer and every Newton refactor refills the buffer from the packed copy, the first
+// one of a substep included (A/B builds differ only in this switch)
+#ifndef MYO_MHL_A
+#define MYO_MHL_A 1
+#endif
+// 0: the packed copy of M is made one lane per row
+#ifndef MYO_MHL_B
+#define MYO_MHL_B 1
+#endif
+// 0: the later refactors of a substep refill the whole Hessian buffer from the packed copy, one lane per row
+#ifndef MYO_MHL_E
+#define MYO_MHL_E 1
+#endif
 // Dof trees of the size-specialised instantiations (parent dof of each dof; myo_model_load checks the model's dof_parentid against them
 // before it selects a specialised instantiation).  The mass matrix M and M + h D couple a dof only with its ancestors and descendants:
 // factorised LEAVES FIRST (lane i <-> dof nv - 1 - i) the Cholesky factor keeps exactly that pattern, no fill-in (Featherstone; MuJoCo's
@@ -222,6 +235,15 @@ template <int NVT> __device__ __forceinline__ float symv_lds(const float* Mp, fl
     s += mv * rdlane(x, k);
   }
   return s;
+}
+
+// The lower triangle of an NVT x NVT matrix (diagonal included, NVT even) spread over the lanes: rows p and NVT - 1 - p have NVT + 1 entries together,
+// so entry i of an NVT / 2 x (NVT + 1) grid is (row d, column k <= d) with no square root and no table; i = lane + 64 t covers TRI_N entries.
+template <int NVT> constexpr int TRI_N = (NVT / 2) * (NVT + 1);
+template <int NVT> __device__ __forceinline__ void tri_pair(int i, int& d, int& k) {
+  const int p = i / (NVT + 1), c = i - p * (NVT + 1);
+  d = c <= p ? p : NVT - 1 - p;
+  k = c <= p ? c : c - p - 1;
 }
 
 template <class LY> __device__ __forceinline__ void site_world_w(const DevModel& M, const LY& Y, const float* E, int s, float* out) {
@@ -493,6 +515,20 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
   // the small instantiation (hand / finger class) is compiled without the free-joint, equality, plane-contact and condim-1 code;
   // myo_model_load routes any model that needs one of those to the large instantiation
   constexpr bool FULL = NVT > 24;
+  // the lane's full row of the mass matrix stays in registers through the solver (see the row stage)
+#ifdef MYO_NO_MROW
+  constexpr bool MROW = false;
+#else
+  constexpr bool MROW = NVT > 24 && !RK4;      // (the Runge-Kutta twins keep four stage derivatives per lane: no room for the row)
+#endif
+  // the 24-dof kernels: the dynamics stage writes only the lower triangle of M into the square buffer (nothing reads the upper one without MROW),
+  // and the first Newton refactor of a substep builds H on that copy instead of refilling the buffer from the packed one
+  constexpr bool MHL_A = MYO_MHL_A && NVT <= 32 && !MROW && !RK4;
+  // ... and the later refactors of a substep refill only what L overwrote, with all 64 lanes
+  constexpr bool MHL_E = MYO_MHL_E && NVT <= 32 && !MROW && !RK4;
+  // ... and the packed copy of M is made by all 64 lanes
+  constexpr bool MHL_B = MYO_MHL_B && NVT <= 32 && !MROW && !RK4;
+  static_assert(!(MHL_E || MHL_B) || NVT % 2 == 0, "tri_pair needs an even NVT");
   const bool has_free = FULL && W.has_free;
   const int neq = FULL ? W.neq : 0;
   // tendon limits: never in the size-specialised and TRK instantiations (myo_model_load checks it), so their tendon lengths / velocities
@@ -1111,8 +1147,8 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
 #pragma unroll
         for (int k = 0; k < 6; k++) sdot += E[Y.cdof + 6 * a + k] * buf[k];
         if (a == d) sdot += my_arm;
-        E[Y.sq + d * (NVT + 1) + a] = sdot;   // full symmetric copy: (d,a) and (a,d)
-        E[Y.sq + a * (NVT + 1) + d] = sdot;
+        E[Y.sq + d * (NVT + 1) + a] = sdot;   // full symmetric copy: (d,a) and (a,d); a <= d, and only the MROW kernels read above the diagonal
+        if (!MHL_A) E[Y.sq + a * (NVT + 1) + d] = sdot;
       }
       smooth = -my_damp * E[Y.qvel + d] - bias + qfa;
     }
@@ -1988,18 +2024,21 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
     // address arithmetic (twice and a half per substep), and the Newton rows H = M + J^T D J start from it
     // (36-dof instantiations only: they run two waves per SIMD on a 256-register budget.  In the 24-dof kernels, at four waves per SIMD, the 24 extra
     // live registers spill -- 23 in the headline kernel -- so those keep reading the packed copy.)
-#ifdef MYO_NO_MROW
-    constexpr bool MROW = false;
-#else
-    constexpr bool MROW = NVT > 24 && !RK4;      // (the Runge-Kutta twins keep four stage derivatives per lane: no room for the row)
-#endif
+    // (MROW: with the kernel's constants)
     float mrow[MROW ? NVT : 1];
     if constexpr (MROW) {
       const int ml = lane < nv ? lane : 0;
 #pragma unroll
       for (int k = 0; k < NVT; k++) mrow[k] = lane < nv ? E[Y.sq + ml * (NVT + 1) + k] : 0.f;
     }
-    if (lane < nv) {
+    if constexpr (MHL_B) {      // the whole wave moves the triangle: 2 x 5 LDS instructions for 24 dofs where lane = row takes 2 x 24
+#pragma unroll
+      for (int i0 = 0; i0 < TRI_N<NVT>; i0 += 64) {
+        int d, k;
+        tri_pair<NVT>(i0 + lane, d, k);
+        if (i0 + lane < TRI_N<NVT> && d < nv) E[Y.Mp + (d * (d + 1)) / 2 + k] = E[Y.sq + d * (NVT + 1) + k];
+      }
+    } else if (lane < nv) {
       const int based = (lane * (lane + 1)) / 2;
 #pragma unroll
       for (int k = 0; k < NVT; k++) if (k <= lane) E[Y.Mp + based + k] = E[Y.sq + lane * (NVT + 1) + k];
@@ -2178,7 +2217,30 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
             f_fact++;
             // the Hessian buffer starts as M (lower rows; identity rows for the padding lanes) plus the limit / friction-loss diagonal, and the contact
             // blocks are added on top: the factorisation then reads finished rows instead of combining two LDS reads and three selects per entry
-            if (lane < NVT) {
+            // (MHL_A: at the first refactor of a substep the buffer still holds this substep's M -- lower rows, zeros above the diagonal and in
+            // the rows of the padding lanes; nothing has written it since the dynamics stage -- so only the diagonal term goes in)
+            if (MHL_A && first) {
+              if (lane < NVT) {
+                const float dg_ = (lane < nv) ? ((lact ? lD : 0.f) + (flquad ? flD : 0.f)) : 1.f;
+                const float mv_ = lane < nv ? E[Y.sq + lane * (NVT + 1) + lane] : 0.f;
+                E[Y.sq + lane * (NVT + 1) + lane] = mv_ + dg_;
+              }
+            } else if (MHL_E && !first) {      // (MYO_MHL_A=0: the first refactor takes the full refill below)
+              // a later refactor of the substep: the buffer holds L, i.e. exact zeros from the diagonal on, so only what lies below the diagonal
+              // comes back from the packed copy, and the whole wave moves it (tri_pair): 2 x 5 LDS instructions for 24 dofs where lane = row takes 2 x 24.
+              // The diagonal goes in as before, from the lane that owns the row's diagonal term.
+#pragma unroll
+              for (int i0 = 0; i0 < TRI_N<NVT>; i0 += 64) {
+                int d, k;
+                tri_pair<NVT>(i0 + lane, d, k);
+                if (i0 + lane < TRI_N<NVT> && k < d) E[Y.sq + d * (NVT + 1) + k] = d < nv ? Mp[(d * (d + 1)) / 2 + k] + 0.f : 0.f;
+              }
+              if (lane < NVT) {
+                const float dg_ = (lane < nv) ? ((lact ? lD : 0.f) + (flquad ? flD : 0.f)) : 1.f;
+                const float mv_ = lane < nv ? Mp[(lane * (lane + 1)) / 2 + lane] : 0.f;
+                E[Y.sq + lane * (NVT + 1) + lane] = mv_ + dg_;
+              }
+            } else if (lane < NVT) {
               const int dd_ = lane < nv ? lane : 0;
               const int based_ = (dd_ * (dd_ + 1)) / 2;
               const float dg_ = (lane < nv) ? ((lact ? lD : 0.f) + (flquad ? flD : 0.f)) : 1.f;

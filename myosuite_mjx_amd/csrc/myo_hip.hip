@@ -5,8 +5,12 @@
 //   myo_physics.h       tendon wrapping, muscle model, action map (+ muscle conditions), impedance, contact frames, MPR
 //   myo_task_track.h    MyoDM TrackEnv as a fused task of the TRK step kernel: reference lookup, reward / done, masked reset
 //   myo_kernel_lanes.h  step_kernel<G>: the first kernel, G = 16 / 32 / 64 lanes per env, all state in LDS (cross-check / fallback)
-//   myo_kernel_wave.h   step_kernel_w: one env per 64-lane wavefront (default), substep scheduler, size-specialised instantiations
-//   myo_ldl_mfma.h      dense LDL^T of the Newton Hessian on the FP32 matrix cores (included by myo_kernel_wave.h)
+//   myo_kernel_wave.h   step_kernel_w: one env per 64-lane wavefront (default): LDS layout, substep scheduler, size specialisations, the kernel body
+//   myo_wave_util.h     its cross-lane / register helpers, WaveCfg (what the template parameters imply), con_row, the stage context
+//   myo_wave_motion.h   its stages: state check, kinematics, tendons and muscles, CRB + RNE, integration
+//   myo_wave_collision.h   broad phase, narrow phase
+//   myo_wave_solver.h   constraint rows, packed mass matrix, sensor readout, task epilogues (the solver itself is inline in the kernel)
+//   myo_ldl_mfma.h      dense LDL^T of the Newton Hessian on the FP32 matrix cores (included by myo_wave_util.h)
 //   myo_kernels_aux.h   RNG, placement hint, random actions, policy inference, reset, state-only observations, task_obs_kernel / task_post_kernel
 //   myo_host.h          host records: myo_model, myo_batch, the per-task hook record (TaskHooks) and its generic launchers
 //   myo_task_*.h        key-turn, pen, baoding, die, classic MyoDM: a task's observation body, its configure checks and its hook record

@@ -14,5 +14,6 @@ from .envs import REGISTRY, UNSUPPORTED, BatchedMyoEnv, make  # noqa: F401
 from .policy import BraxPolicy  # noqa: F401
 from .sim import HipSimScene, get, make_data, put_model, set_, step  # noqa: F401
 from . import trace  # noqa: F401  (batched rollouts <-> the reference's Trace logger layout)
+from . import ppo  # noqa: F401  (PPO training on the device: ppo.train, the counterpart of mjx/ppo_continuous_action.py)
 
 __version__ = "0.1.0"

@@ -12,6 +12,7 @@
 //   myo_wave_solver.h   constraint rows, packed mass matrix, sensor readout, task epilogues (the solver itself is inline in the kernel)
 //   myo_ldl_mfma.h      dense LDL^T of the Newton Hessian on the FP32 matrix cores (included by myo_wave_util.h)
 //   myo_kernels_aux.h   RNG, placement hint, random actions, policy inference, reset, state-only observations, task_obs_kernel / task_post_kernel
+//   myo_kernels_ppo.h   PPO training: policy sampling with log-probabilities, GAE (include/myo_hip_ppo.h)
 //   myo_host.h          host records: myo_model, myo_batch, the per-task hook record (TaskHooks) and its generic launchers
 //   myo_task_*.h        key-turn, pen, baoding, die, classic MyoDM: a task's observation body, its configure checks and its hook record
 //   myo_host_model.h    myo_model_load in pieces: blob view, table upload, packing of the per-lane records, kernel class
@@ -33,6 +34,7 @@
 #include "myo_kernel_lanes.h"
 #include "myo_kernel_wave.h"
 #include "myo_kernels_aux.h"
+#include "myo_kernels_ppo.h"
 #include "myo_host.h"
 #include "myo_task_keyturn.h"
 #include "myo_task_pen.h"
@@ -748,6 +750,52 @@ int myo_policy_act(myo_policy* p, const float* obs_dev, int B, float* action_dev
   if (lds > 64 * 1024) return fail(MYO_E_UNSUPPORTED, "myo_policy_act: observation too wide for the LDS tile");
   hipLaunchKernelGGL(policy_kernel, dim3((B + POL_ENVS - 1) / POL_ENVS), dim3(POL_ENVS * POL_MAXW), lds, (hipStream_t)stream, p->pd, obs_dev, B,
                      action_dev, deterministic, seed, step, env_offset);
+  HIPCHK(hipGetLastError());
+  return MYO_OK;
+}
+
+// ---- PPO training (include/myo_hip_ppo.h; kernels in myo_kernels_ppo.h)
+int myo_policy_update(myo_policy* p, const float* obs_mean, const float* obs_std, const float* const* kernels, const float* const* biases,
+                      int src_is_device, void* stream) {
+  if (!p) return fail(MYO_E_ARG, "myo_policy_update: null policy");
+  HIPCHK(hipSetDevice(p->device));
+  const PolicyDev& P = p->pd;
+  const hipMemcpyKind kind = src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  auto put = [&](const float* dst, const float* src, size_t n) -> hipError_t {
+    return src ? hipMemcpyAsync(const_cast<float*>(dst), src, n * 4, kind, (hipStream_t)stream) : hipSuccess;
+  };
+  HIPCHK(put(P.mean, obs_mean, P.obs_dim));
+  HIPCHK(put(P.std, obs_std, P.obs_dim));
+  int nin = P.obs_dim;
+  for (int l = 0; l < P.nlayers; l++) {
+    if (kernels) HIPCHK(put(P.W[l], kernels[l], (size_t)nin * P.width[l]));
+    if (biases) HIPCHK(put(P.b[l], biases[l], P.width[l]));
+    nin = P.width[l];
+  }
+  if (!src_is_device) HIPCHK(hipStreamSynchronize((hipStream_t)stream));      // the caller may free its host arrays on return
+  return MYO_OK;
+}
+
+int myo_policy_sample(myo_policy* p, const float* obs_dev, int B, float* action_dev, float* raw_dev, float* logp_dev, uint64_t seed,
+                      uint64_t step, int env_offset, void* stream) {
+  if (!p || !obs_dev || !action_dev || !raw_dev || !logp_dev || B <= 0) return fail(MYO_E_ARG, "myo_policy_sample: bad arguments");
+  HIPCHK(hipSetDevice(p->device));
+  int stride = p->pd.obs_dim > POL_MAXW ? p->pd.obs_dim : POL_MAXW;
+  for (int l = 0; l < p->pd.nlayers; l++) if (p->pd.width[l] > stride) stride = p->pd.width[l];
+  size_t lds = (size_t)2 * POL_ENVS * stride * 4;
+  if (lds > 64 * 1024) return fail(MYO_E_UNSUPPORTED, "myo_policy_sample: observation too wide for the LDS tile");
+  hipLaunchKernelGGL(policy_sample_kernel, dim3((B + POL_ENVS - 1) / POL_ENVS), dim3(POL_ENVS * POL_MAXW), lds, (hipStream_t)stream, p->pd, obs_dev, B,
+                     action_dev, raw_dev, logp_dev, seed, step, env_offset);
+  HIPCHK(hipGetLastError());
+  return MYO_OK;
+}
+
+int myo_ppo_gae(const float* rewards, const float* values, const float* bootstrap, const float* termination, const float* truncation,
+                int T, int B, float discount, float lambda, float* vs_out, float* adv_out, void* stream) {
+  if (!rewards || !values || !bootstrap || !termination || !truncation || !vs_out || !adv_out || T <= 0 || B <= 0)
+    return fail(MYO_E_ARG, "myo_ppo_gae: bad arguments");
+  hipLaunchKernelGGL(ppo_gae_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, rewards, values, bootstrap, termination, truncation,
+                     T, B, discount, lambda, vs_out, adv_out);
   HIPCHK(hipGetLastError());
   return MYO_OK;
 }

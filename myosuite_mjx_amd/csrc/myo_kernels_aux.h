@@ -59,7 +59,7 @@ __global__ void random_action_kernel(float* action, int B, int nu, uint64_t seed
 }
 
 // ------------------------------------------------------------------------------------------------
-// policy inference (brax PPO network family): 8 envs per 256-thread workgroup, thread = (env, hidden unit); activations ping-pong
+// policy inference (brax PPO network family): 8 envs per 512-thread workgroup, thread = (env, hidden unit); activations ping-pong
 // through LDS, weights are read coalesced across units and shared by the 8 envs through the cache.  ~13 kMAC per env for
 // the hand observation: negligible next to the physics step, so plain FMAs (no MFMA)
 #define POL_ENVS 8
@@ -71,11 +71,9 @@ struct PolicyDev {
   const float* b[8];
   const float *mean, *std;
 };
-__global__ void __launch_bounds__(POL_ENVS * POL_MAXW) policy_kernel(PolicyDev P, const float* __restrict__ obs, int B, float* __restrict__ action,
-                                                                     int deterministic, uint64_t seed, uint64_t step, int env_offset) {
-  extern __shared__ float sh[];                       // [POL_ENVS][max(obs_dim, POL_MAXW)] x 2
-  const int j = threadIdx.x % POL_MAXW, le = threadIdx.x / POL_MAXW;
-  const int e = blockIdx.x * POL_ENVS + le;
+// The forward pass, shared by policy_kernel and policy_sample_kernel (myo_kernels_ppo.h): one env = one wavefront (lane j of wave le);
+// returns the env's head row in LDS, [loc[act_dim], raw[act_dim]].  Every thread of the workgroup calls it (it holds the barriers)
+__device__ __forceinline__ const float* policy_forward(const PolicyDev& P, const float* __restrict__ obs, int B, float* sh, const int j, const int le, const int e) {
   int stride = max(P.obs_dim, POL_MAXW);
   for (int l = 0; l < P.nlayers; l++) stride = max(stride, P.width[l]);
   float* xin = sh + le * stride;
@@ -98,16 +96,25 @@ __global__ void __launch_bounds__(POL_ENVS * POL_MAXW) policy_kernel(PolicyDev P
     float* t = xin; xin = xout; xout = t;
     nin = nout;
   }
+  return xin;
+}
+// the tanh-normal head's draw for action jj of global env ge: u = loc + scale * eps, scale = softplus(raw) + 0.001, eps by Box-Muller
+__device__ __forceinline__ float policy_draw(float loc, float raw, uint64_t seed, uint64_t step, uint64_t ge, int jj, float* scale_out) {
+  float scale = (raw > 20.f ? raw : log1pf(expf(raw))) + 0.001f;
+  float u1 = fmaxf(u01(seed ^ 0x5851F42D4C957F2Dull, ge * 1024 + jj, step), 1e-7f), u2 = u01(seed ^ 0x14057B7EF767814Full, ge * 1024 + jj, step);
+  *scale_out = scale;
+  return loc + scale * sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);   // Box-Muller
+}
+__global__ void __launch_bounds__(POL_ENVS * POL_MAXW) policy_kernel(PolicyDev P, const float* __restrict__ obs, int B, float* __restrict__ action,
+                                                                     int deterministic, uint64_t seed, uint64_t step, int env_offset) {
+  extern __shared__ float sh[];                       // [POL_ENVS][max(obs_dim, POL_MAXW)] x 2
+  const int j = threadIdx.x % POL_MAXW, le = threadIdx.x / POL_MAXW;
+  const int e = blockIdx.x * POL_ENVS + le;
+  const float* head = policy_forward(P, obs, B, sh, j, le, e);
   if (e < B) {
     for (int jj = j; jj < P.act_dim; jj += POL_MAXW) {
-      float loc = xin[jj], a = loc;
-      if (!deterministic) {
-        float raw = xin[P.act_dim + jj];
-        float scale = (raw > 20.f ? raw : log1pf(expf(raw))) + 0.001f;
-        uint64_t ge = (uint64_t)(e + env_offset);
-        float u1 = fmaxf(u01(seed ^ 0x5851F42D4C957F2Dull, ge * 1024 + jj, step), 1e-7f), u2 = u01(seed ^ 0x14057B7EF767814Full, ge * 1024 + jj, step);
-        a = loc + scale * sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);   // Box-Muller
-      }
+      float a = head[jj], scale;
+      if (!deterministic) a = policy_draw(a, head[P.act_dim + jj], seed, step, (uint64_t)(e + env_offset), jj, &scale);
       action[(size_t)e * P.act_dim + jj] = tanhf(a);
     }
   }

@@ -29,6 +29,8 @@ class BraxPolicy:
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         L.myo_policy_free.argtypes = [C.c_void_p]
         L.myo_policy_act.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
+        L.myo_policy_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_void_p]
+        L.myo_policy_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
         self.kernels = [_f32(k) for k in kernels]
         self.biases = [_f32(b) for b in biases]
         self.obs_mean, self.obs_std = _f32(obs_mean), _f32(obs_std)
@@ -53,6 +55,54 @@ class BraxPolicy:
     def act(self, obs_ptr, B, action_ptr, deterministic=True, seed=0, step=0, env_offset=0, stream=None):
         """obs_ptr / action_ptr: device pointers (int) of [B, obs_dim] / [B, act_dim] float32 buffers."""
         capi._chk(capi.lib().myo_policy_act(self.h, obs_ptr, int(B), action_ptr, int(bool(deterministic)), seed, step, env_offset, stream))
+
+    def sample(self, obs_ptr, B, action_ptr, raw_ptr, logp_ptr, seed, step, env_offset=0, stream=None):
+        """`act(deterministic=False)` for a learner (include/myo_hip_ppo.h): the same action, bit for bit, plus raw_ptr [B, act_dim] = u, the
+        pre-tanh sample, and logp_ptr [B] = the action's log-probability under the tanh-normal.  All pointers are device pointers (int)."""
+        capi._chk(capi.lib().myo_policy_sample(self.h, obs_ptr, int(B), action_ptr, raw_ptr, logp_ptr, seed, step, env_offset, stream))
+
+    def update(self, obs_mean=None, obs_std=None, kernels=None, biases=None, stream=None):
+        """New weights in place, without reloading (myo_policy_update).  None, also as an entry of kernels / biases, keeps that buffer.  The
+        arguments are either numpy arrays (host path: copied before the call returns, the host copies `obs_mean`, `kernels`, ... follow) or
+        CUDA torch tensors (device path: device-to-device copies queued on `stream`, by default torch's current stream, no host
+        synchronisation; the host copies are left as they were).  Shapes are those of the loaded network; float32, contiguous."""
+        n = len(self.kernels)
+        kernels = [None] * n if kernels is None else list(kernels)
+        biases = [None] * n if biases is None else list(biases)
+        if len(kernels) != n or len(biases) != n:
+            raise ValueError(f"update: the policy has {n} layers")
+        shapes = [(self.obs_dim,)] * 2 + [k.shape for k in self.kernels] + [b.shape for b in self.biases]
+        given = [obs_mean, obs_std, *kernels, *biases]
+        on_dev = {hasattr(a, "data_ptr") for a in given if a is not None}
+        if len(on_dev) > 1:
+            raise ValueError("update: numpy arrays or CUDA tensors, not both in one call")
+        dev = on_dev == {True}
+        ptrs, keep = [], []
+        for a, shape in zip(given, shapes):
+            if a is None:
+                ptrs.append(None)
+                continue
+            if dev:
+                import torch
+                if not a.is_cuda or a.dtype != torch.float32 or not a.is_contiguous():
+                    raise ValueError("update: device arguments must be contiguous float32 CUDA tensors")
+                a = a.detach()
+            else:
+                a = _f32(a)
+            if tuple(a.shape) != tuple(shape):
+                raise ValueError(f"update: shape {tuple(a.shape)} given, the policy holds {tuple(shape)}")
+            keep.append(a)
+            ptrs.append(a.data_ptr() if dev else a.ctypes.data)
+        if dev and stream is None:
+            import torch
+            stream = torch.cuda.current_stream().cuda_stream
+        kp, bp = (C.c_void_p * n)(*ptrs[2:2 + n]), (C.c_void_p * n)(*ptrs[2 + n:])
+        capi._chk(capi.lib().myo_policy_update(self.h, ptrs[0], ptrs[1], kp, bp, int(dev), stream))
+        if not dev:
+            self.obs_mean = self.obs_mean if obs_mean is None else _f32(obs_mean)
+            self.obs_std = self.obs_std if obs_std is None else _f32(obs_std)
+            self.kernels = [k0 if k is None else _f32(k) for k0, k in zip(self.kernels, kernels)]
+            self.biases = [b0 if b is None else _f32(b) for b0, b in zip(self.biases, biases)]
 
     def __del__(self):
         try:

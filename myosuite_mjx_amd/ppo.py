@@ -1,0 +1,364 @@
+"""PPO training on the device: the native counterpart of the reference's `mjx/ppo_continuous_action.py`, which builds a `TrackEnv`
+and hands it to brax's `ppo.train`.  brax and jax are absent here, so the algorithm is restated from brax's documentation
+-- parity with brax itself is unpinned, as for `policy.BraxPolicy`.
+
+What runs where.  HIP (include/myo_hip_ppo.h): the rollout's action sampling with log-probabilities (`myo_policy_sample`, one launch per
+env step next to the env's own), the advantage recurrence (`myo_ppo_gae`, one launch per SGD step where a torch loop takes six or more per
+time step) and the refresh of the device policy's weights (`myo_policy_update`, device to device).  torch: the two networks' forward and
+backward passes, Adam, and a handful of reductions (running observation statistics, metrics).
+
+Every function below dispatches on where its tensors live: CUDA tensors go to the HIP kernel, CPU tensors to a plain torch statement of
+the same formula, which is also what a CPU-only training run (`backend="torch"`, or an env whose observations are CPU tensors) uses.
+
+Formulas (brax's, restated):
+    scale = softplus(raw) + 0.001;  u = loc + scale * eps;  action = tanh(u)
+    log pi(u) = sum_j [ log N(u_j; loc_j, scale_j) - 2 (log 2 - u_j - softplus(-2 u_j)) ]
+    entropy   = sum_j [ 1/2 + 1/2 log(2 pi) + log scale_j + 2 (log 2 - u_j - softplus(-2 u_j)) ]      (u: a fresh sample)
+    GAE: see `compute_gae`;  loss: see `loss`.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import time
+
+import numpy as np
+
+from . import capi
+
+_LOG2 = math.log(2.0)
+_HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
+# limits of the policy kernel (csrc/myo_kernels_aux.h): layer widths, layer count, and the LDS tile that holds two activation rows of 8 envs
+MAX_WIDTH, MAX_LAYERS, MAX_OBS_DIM = 512, 8, 64 * 1024 // (2 * 8 * 4)
+
+
+def _gae_lib():
+    L = capi.lib()
+    L.myo_ppo_gae.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    return L
+
+
+def _gae_torch(rewards, values, bootstrap, termination, truncation, discount, gae_lambda):
+    import torch
+    T = rewards.shape[0]
+    vs, adv = torch.empty_like(values), torch.empty_like(values)
+    v_next, vs_next, acc = bootstrap, bootstrap, torch.zeros_like(bootstrap)
+    for t in range(T - 1, -1, -1):
+        cont, mask = discount * (1.0 - termination[t]), 1.0 - truncation[t]
+        delta = (rewards[t] + cont * v_next - values[t]) * mask
+        acc = delta + cont * mask * gae_lambda * acc
+        vs[t] = acc + values[t]
+        adv[t] = (rewards[t] + cont * vs_next - values[t]) * mask
+        v_next, vs_next = values[t], vs[t]
+    return vs, adv
+
+
+def compute_gae(rewards, values, bootstrap, termination, truncation, discount, gae_lambda):
+    """Generalised advantage estimation, brax's compute_gae.  [T, B] float32 tensors (termination / truncation as 0 / 1), bootstrap [B]:
+        mask_t  = 1 - truncation_t;  v_next_t = values_{t+1} (bootstrap for t = T-1)
+        delta_t = (rewards_t + discount (1 - termination_t) v_next_t - values_t) mask_t
+        acc_t   = delta_t + discount (1 - termination_t) mask_t lambda acc_{t+1}                    (acc_T = 0)
+        vs_t    = acc_t + values_t
+        adv_t   = (rewards_t + discount (1 - termination_t) vs_{t+1} - values_t) mask_t             (vs_T = bootstrap)
+    Returns (vs, adv), without gradient.  CUDA tensors: one launch of myo_ppo_gae on torch's current stream."""
+    import torch
+    with torch.no_grad():
+        args = [torch.as_tensor(a, dtype=torch.float32).detach().contiguous() for a in (rewards, values, bootstrap, termination, truncation)]
+        r, v, boot = args[0], args[1], args[2]
+        if r.dim() != 2 or r.shape[0] < 1 or r.shape[1] < 1 or any(a.shape != r.shape for a in (v, args[3], args[4])) or boot.shape != r.shape[1:]:
+            raise ValueError("compute_gae: rewards, values, termination, truncation are [T, B] and bootstrap is [B], T, B >= 1")
+        if not r.is_cuda:
+            return _gae_torch(*args, float(discount), float(gae_lambda))
+        if any(a.device != r.device for a in args):
+            raise ValueError("compute_gae: all tensors must be on one device")
+        vs, adv = torch.empty_like(v), torch.empty_like(v)
+        with torch.cuda.device(r.device):
+            capi._chk(_gae_lib().myo_ppo_gae(*(a.data_ptr() for a in args), r.shape[0], r.shape[1], float(discount), float(gae_lambda),
+                                             vs.data_ptr(), adv.data_ptr(), torch.cuda.current_stream().cuda_stream))
+        return vs, adv
+
+
+def _log_det_tanh(u):
+    """log |d tanh(u) / du| = 2 (log 2 - u - softplus(-2 u)): finite where 1 - tanh(u)^2 underflows."""
+    import torch
+    return 2.0 * (_LOG2 - u - torch.nn.functional.softplus(-2.0 * u))
+
+
+def tanh_normal_log_prob(loc, scale, u):
+    """log-probability of the action tanh(u) under the tanh-squashed normal, summed over the last axis."""
+    import torch
+    z = (u - loc) / scale
+    return (-0.5 * z * z - torch.log(scale) - _HALF_LOG_2PI - _log_det_tanh(u)).sum(-1)
+
+
+def tanh_normal_entropy(loc, scale, u):
+    """brax's entropy estimate of the tanh-squashed normal: the normal's entropy plus the log-determinant at a sample u."""
+    import torch
+    return (0.5 + _HALF_LOG_2PI + torch.log(scale) + _log_det_tanh(u)).sum(-1)
+
+
+class RunningStats:
+    """brax's running observation statistics: count, mean, summed variance; std = clip(sqrt(max(summed_var / count, 0)), 1e-6, 1e6).
+    Before the first update mean = 0 and std = 1."""
+
+    def __init__(self, obs_dim, device="cpu"):
+        import torch
+        self.count = 0
+        self.mean = torch.zeros(obs_dim, dtype=torch.float32, device=device)
+        self.summed_var = torch.zeros(obs_dim, dtype=torch.float32, device=device)
+        self.std = torch.ones(obs_dim, dtype=torch.float32, device=device)
+
+    def update(self, x):
+        """x [N, obs_dim]: count' = count + N; d = x - mean; mean' = mean + sum(d) / count'; summed_var' = summed_var + sum(d (x - mean'))."""
+        import torch
+        with torch.no_grad():
+            x = x.reshape(-1, self.mean.shape[0]).to(self.mean.dtype)
+            self.count += x.shape[0]
+            d = x - self.mean
+            self.mean = self.mean + d.sum(0) / self.count
+            self.summed_var = self.summed_var + (d * (x - self.mean)).sum(0)
+            self.std = torch.clamp(torch.sqrt(torch.clamp(self.summed_var / self.count, min=0.0)), 1e-6, 1e6)
+
+
+def loss(loc, scale, values, bootstrap, u, logp_behaviour, rewards, termination, truncation, entropy_noise, *, discounting=0.95,
+         gae_lambda=0.95, clipping_epsilon=0.3, entropy_cost=1e-3, reward_scaling=5.0, normalize_advantage=True):
+    """brax's PPO loss on one minibatch of whole unrolls.  loc, scale, u, entropy_noise: [T, B, act_dim]; values, logp_behaviour, rewards,
+    termination, truncation: [T, B]; bootstrap [B] = the value of the observation after the unroll.
+        vs, A  = compute_gae(rewards * reward_scaling, values, bootstrap, ...), detached; A = (A - mean) / (std + 1e-8) if normalize_advantage (std over the minibatch, 1/N)
+        rho    = exp(log pi(u) - logp_behaviour)
+        policy = -mean(min(rho A, clip(rho, 1 - eps, 1 + eps) A));  value = 1/4 mean((vs - V)^2)
+        entropy = -entropy_cost mean(entropy at loc + scale * entropy_noise)
+    Returns (total, {"policy_loss", "value_loss", "entropy_loss"})."""
+    import torch
+    vs, adv = compute_gae(rewards * reward_scaling, values, bootstrap, termination, truncation, discounting, gae_lambda)
+    if normalize_advantage:
+        adv = (adv - adv.mean()) / (adv.std(unbiased=False) + 1e-8)
+    rho = torch.exp(tanh_normal_log_prob(loc, scale, u) - logp_behaviour)
+    policy_loss = -torch.minimum(rho * adv, torch.clamp(rho, 1.0 - clipping_epsilon, 1.0 + clipping_epsilon) * adv).mean()
+    value_loss = 0.25 * ((vs - values) ** 2).mean()
+    entropy_loss = -entropy_cost * tanh_normal_entropy(loc, scale, loc + scale * entropy_noise).mean()
+    return policy_loss + value_loss + entropy_loss, {"policy_loss": policy_loss.detach(), "value_loss": value_loss.detach(),
+                                                     "entropy_loss": entropy_loss.detach()}
+
+
+def _mlp(sizes, gen, device):
+    """A swish MLP as plain parameter lists, kernels [in, out] (the layout myo_policy_update takes), lecun-uniform kernels and zero biases
+    as in brax's networks."""
+    import torch
+    ws, bs = [], []
+    for nin, nout in zip(sizes[:-1], sizes[1:]):
+        lim = math.sqrt(3.0 / nin)
+        w = (torch.rand((nin, nout), generator=gen, dtype=torch.float32) * 2.0 - 1.0) * lim
+        ws.append(w.to(device).requires_grad_())
+        bs.append(torch.zeros(nout, dtype=torch.float32, device=device, requires_grad=True))
+    return ws, bs
+
+
+def init_networks(obs_dim, act_dim, policy_hidden, value_hidden, seed, device="cpu"):
+    """(policy kernels, policy biases, value kernels, value biases) as `train` starts from them: drawn on the host from `seed`, so the
+    same for every backend."""
+    import torch
+    gen = torch.Generator().manual_seed(int(seed))
+    pw, pb = _mlp([obs_dim, *policy_hidden, 2 * act_dim], gen, device)
+    vw, vb = _mlp([obs_dim, *value_hidden, 1], gen, device)
+    return pw, pb, vw, vb
+
+
+def mlp_forward(x, ws, bs):
+    import torch
+    for i, (w, b) in enumerate(zip(ws, bs)):
+        x = x @ w + b
+        if i + 1 < len(ws):
+            x = x * torch.sigmoid(x)
+    return x
+
+
+def policy_forward(obs, mean, std, ws, bs):
+    """(loc, scale) of the tanh-normal head for observations obs [..., obs_dim]: the network `BraxPolicy` runs, in torch."""
+    import torch
+    loc, raw = torch.chunk(mlp_forward((obs - mean) / std, ws, bs), 2, dim=-1)
+    return loc, torch.nn.functional.softplus(raw) + 0.001
+
+
+def _check(env, unroll_length, num_minibatches, action_repeat, policy_hidden, episode_length):
+    B = int(env.num_envs)
+    if num_minibatches < 1 or B % num_minibatches:
+        raise ValueError(f"num_envs = {B} is not a multiple of num_minibatches = {num_minibatches}")
+    if unroll_length < 1:
+        raise ValueError(f"unroll_length must be at least 1, got {unroll_length}")
+    if action_repeat < 1:
+        raise ValueError(f"action_repeat must be at least 1, got {action_repeat}")
+    if len(policy_hidden) + 1 > MAX_LAYERS:
+        raise ValueError(f"the policy kernel runs at most {MAX_LAYERS} layers, policy_hidden has {len(policy_hidden)} + the head")
+    if any(h < 1 or h > MAX_WIDTH for h in (*policy_hidden, 2 * int(env.act_dim))):
+        raise ValueError(f"the policy kernel's layers are 1..{MAX_WIDTH} wide, got {tuple(policy_hidden)} and a head of {2 * int(env.act_dim)}")
+    if int(env.obs_dim) > MAX_OBS_DIM:
+        raise ValueError(f"obs_dim = {env.obs_dim} is wider than the policy kernel's LDS tile ({MAX_OBS_DIM} floats)")
+    limit = getattr(env, "max_episode_steps", None)
+    if episode_length is not None and limit is not None and int(episode_length) != int(limit):
+        raise ValueError(f"episode_length = {episode_length}, but the env ends its episodes after {limit} steps: the time limit belongs to "
+                         "the env here, give it to make(..., max_episode_steps=...)")
+
+
+def params_dict(stats, pw, pb, vw, vb):
+    """The trainer's parameters as numpy arrays under the names `save` writes."""
+    out = {"obs_mean": stats.mean, "obs_std": stats.std}
+    out.update({f"w{i}": w for i, w in enumerate(pw)})
+    out.update({f"b{i}": b for i, b in enumerate(pb)})
+    out.update({f"vw{i}": w for i, w in enumerate(vw)})
+    out.update({f"vb{i}": b for i, b in enumerate(vb)})
+    out = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in out.items()}
+    out["obs_count"] = np.float32(stats.count)
+    return out
+
+
+def save(path, params):
+    """Writes the `.npz` that `BraxPolicy.from_npz` reads (obs_mean, obs_std, obs_count, w*, b*), the value network under vw* / vb*."""
+    np.savez(path, **{k: np.asarray(v, np.float32) for k, v in params.items()})
+
+
+def train(env, num_timesteps, episode_length=None, unroll_length=50, num_minibatches=32, num_updates_per_batch=8, discounting=0.95,
+          gae_lambda=0.95, learning_rate=3e-4, entropy_cost=1e-3, clipping_epsilon=0.3, reward_scaling=5.0, normalize_observations=True,
+          normalize_advantage=True, action_repeat=1, policy_hidden=(32, 32, 32, 32), value_hidden=(256,) * 5, seed=1, progress_fn=None,
+          backend=None, keep_first_rollout=False):
+    """PPO on a batched env; returns (BraxPolicy or None, params, metrics).  The argument names and defaults are those of the reference's
+    `mjx/ppo_continuous_action.py`, with brax's defaults for what that script leaves unset.
+
+    env: any object with num_envs, obs_dim, act_dim, reset(seed) -> obs [B, obs_dim] and a gym-order step(action) -> (obs, reward,
+    terminated, truncated, info) that resets finished episodes in place (`BatchedMyoEnv`, `make(<MyoDM id>, autoreset=True)`; terminated
+    and truncated are cast to bool).  backend: "hip" (CUDA observations: sampling, GAE and the weight refresh are HIP kernels and a
+    `BraxPolicy` is returned), "torch" (everything in torch on the observations' device; returns None for the policy), None: "hip" when
+    the env's observations are CUDA tensors.
+
+    One iteration: (1) unroll_length steps, each one sample launch, one env.step and copies into preallocated [T(+1), B, ...] buffers, with
+    no host synchronisation; (2) the running observation statistics take the T * B observations and go to the device policy; (3)
+    num_updates_per_batch epochs, each a fresh permutation of the B unrolls into num_minibatches groups, one Adam step per group on
+    `loss`; (4) the policy's parameters go to the device policy.  num_timesteps is rounded up to whole iterations of
+    num_envs * unroll_length * action_repeat env steps.
+
+    action_repeat = k: k env steps on one action; rewards are summed up to and including the first step that ends the episode,
+    termination and truncation are OR-ed.  brax's wrappers reset outside the repeat; here the env has already reset in place, so the
+    remaining k - 1 steps run in the new episode and are not counted.
+    episode_length: the env's own time limit is what ends episodes; a different value here is refused.
+
+    Not taken: batch_size (it is num_envs / num_minibatches here: every iteration uses all envs), num_evals (episode statistics come from
+    the training rollouts, through progress_fn), max_devices_per_host (one GPU; sharding a learner is out of scope).
+
+    progress_fn(num_steps, metrics) is called once per iteration, like the reference's callback; metrics holds "eval/episode_reward"
+    and "eval/episode_length" (means over the episodes that ended in the iteration, nan when none did), "episodes", "policy_loss",
+    "value_loss", "entropy_loss", "steps_per_s", "rollout_s" and "update_s".  The list of all of them is returned.
+    keep_first_rollout adds host copies of the first unroll's buffers (obs, u, logp, reward) to the first metrics record."""
+    import torch
+    _check(env, unroll_length, num_minibatches, action_repeat, policy_hidden, episode_length)
+    B, D, A, T = int(env.num_envs), int(env.obs_dim), int(env.act_dim), int(unroll_length)
+    obs = torch.as_tensor(env.reset(seed=seed))
+    dev = obs.device
+    if backend is None:
+        backend = "hip" if obs.is_cuda else "torch"
+    if backend not in ("hip", "torch") or (backend == "hip" and not obs.is_cuda):
+        raise ValueError(f"backend {backend!r}: 'hip' needs an env whose observations are CUDA tensors, else 'torch'")
+    hip = backend == "hip"
+    dgen = torch.Generator(device=dev).manual_seed(int(seed))       # permutations, entropy noise, the torch backend's action noise
+    pw, pb, vw, vb = init_networks(D, A, policy_hidden, value_hidden, seed, dev)
+    stats = RunningStats(D, dev)
+    opt = torch.optim.Adam([*pw, *pb, *vw, *vb], lr=learning_rate)
+    pol = None
+    if hip:
+        from .policy import BraxPolicy
+        pol = BraxPolicy(stats.mean.cpu().numpy(), stats.std.cpu().numpy(), [w.detach().cpu().numpy() for w in pw],
+                         [b.detach().cpu().numpy() for b in pb], device=dev.index or 0)
+    f32 = dict(dtype=torch.float32, device=dev)
+    obs_buf, u_buf, logp_buf = torch.empty((T + 1, B, D), **f32), torch.empty((T, B, A), **f32), torch.empty((T, B), **f32)
+    rew_buf, term_buf, trunc_buf = torch.empty((T, B), **f32), torch.empty((T, B), **f32), torch.empty((T, B), **f32)
+    act_buf = torch.empty((B, A), **f32)
+    ep_ret, ep_len = torch.zeros(B, **f32), torch.zeros(B, **f32)
+    mb = B // num_minibatches
+    steps_per_iter = B * T * action_repeat
+    iterations = max(1, -(-int(num_timesteps) // steps_per_iter))
+    metrics, draws = [], 0
+    sync = torch.cuda.synchronize if obs.is_cuda else (lambda: None)
+
+    for it in range(iterations):
+        sync()
+        t0 = time.perf_counter()
+        done_ret, done_len, done_n = torch.zeros((), **f32), torch.zeros((), **f32), torch.zeros((), **f32)
+        # (1) the unroll
+        for t in range(T):
+            obs_buf[t].copy_(obs)
+            if hip:
+                pol.sample(obs_buf[t].data_ptr(), B, act_buf.data_ptr(), u_buf[t].data_ptr(), logp_buf[t].data_ptr(), int(seed), draws,
+                           stream=torch.cuda.current_stream().cuda_stream)
+            else:
+                with torch.no_grad():
+                    loc, scale = policy_forward(obs_buf[t], stats.mean, stats.std, pw, pb)
+                    u_buf[t] = loc + scale * torch.randn(loc.shape, generator=dgen, **f32)
+                    logp_buf[t] = tanh_normal_log_prob(loc, scale, u_buf[t])
+                    act_buf.copy_(torch.tanh(u_buf[t]))
+            draws += 1
+            for k in range(action_repeat):
+                obs, r, term, trunc, _ = env.step(act_buf)
+                term, trunc = torch.as_tensor(term).to(torch.bool), torch.as_tensor(trunc).to(torch.bool)
+                if k == 0:
+                    rew_buf[t].copy_(r)
+                    term_buf[t].copy_(term)
+                    trunc_buf[t].copy_(trunc)
+                    ep_len += 1
+                else:
+                    live = 1.0 - torch.maximum(term_buf[t], trunc_buf[t])      # envs whose episode has not ended within this repeat
+                    rew_buf[t] += r * live
+                    term_buf[t] = torch.maximum(term_buf[t], term * live)
+                    trunc_buf[t] = torch.maximum(trunc_buf[t], trunc * live)
+                    ep_len += live
+            ep_ret += rew_buf[t]
+            done = torch.maximum(term_buf[t], trunc_buf[t])
+            done_ret += (ep_ret * done).sum()
+            done_len += (ep_len * done).sum()
+            done_n += done.sum()
+            ep_ret *= 1.0 - done
+            ep_len *= 1.0 - done
+        obs = torch.as_tensor(obs)
+        obs_buf[T].copy_(obs)
+        sync()
+        t1 = time.perf_counter()
+        # (2) observation statistics
+        if normalize_observations:
+            stats.update(obs_buf[:T])
+            if hip:
+                pol.update(obs_mean=stats.mean.contiguous(), obs_std=stats.std.contiguous())
+        # (3) SGD
+        sums = {k: torch.zeros((), **f32) for k in ("policy_loss", "value_loss", "entropy_loss")}
+        for _ in range(num_updates_per_batch):
+            perm = torch.randperm(B, generator=dgen, device=dev)
+            for g in range(num_minibatches):
+                idx = perm[g * mb:(g + 1) * mb]
+                o = obs_buf[:, idx]
+                loc, scale = policy_forward(o[:T], stats.mean, stats.std, pw, pb)
+                v = mlp_forward((o - stats.mean) / stats.std, vw, vb).squeeze(-1)
+                noise = torch.randn((T, mb, A), generator=dgen, **f32)
+                total, terms = loss(loc, scale, v[:T], v[T], u_buf[:, idx], logp_buf[:, idx], rew_buf[:, idx], term_buf[:, idx],
+                                    trunc_buf[:, idx], noise, discounting=discounting, gae_lambda=gae_lambda,
+                                    clipping_epsilon=clipping_epsilon, entropy_cost=entropy_cost, reward_scaling=reward_scaling,
+                                    normalize_advantage=normalize_advantage)
+                opt.zero_grad(set_to_none=True)
+                total.backward()
+                opt.step()
+                for k2 in sums:
+                    sums[k2] += terms[k2]
+        # (4) the new weights go to the device policy
+        if hip:
+            pol.update(kernels=[w.data for w in pw], biases=[b.data for b in pb])
+        # one read of the iteration's numbers
+        nsgd = num_updates_per_batch * num_minibatches
+        host = torch.stack([done_ret, done_len, done_n, *(sums[k2] / nsgd for k2 in sums)]).cpu().tolist()
+        t2 = time.perf_counter()
+        n = host[2]
+        m = {"eval/episode_reward": host[0] / n if n else float("nan"), "eval/episode_length": host[1] / n if n else float("nan"),
+             "episodes": int(n), "policy_loss": host[3], "value_loss": host[4], "entropy_loss": host[5],
+             "steps_per_s": steps_per_iter / (t2 - t0), "rollout_s": t1 - t0, "update_s": t2 - t1}
+        if it == 0 and keep_first_rollout:     # host copies of the first unroll, for reproducibility checks
+            m["first_rollout"] = {"obs": obs_buf.cpu().numpy(), "u": u_buf.cpu().numpy(), "logp": logp_buf.cpu().numpy(),
+                                  "reward": rew_buf.cpu().numpy()}
+        metrics.append(m)
+        if progress_fn is not None:
+            progress_fn((it + 1) * steps_per_iter, m)
+    return pol, params_dict(stats, pw, pb, vw, vb), metrics

@@ -110,6 +110,23 @@ enum {
 
 enum { MYO_FLAG_BAD_STATE = 1, MYO_FLAG_BAD_QACC = 2, MYO_FLAG_CONTACT_OVERFLOW = 4, MYO_FLAG_CAND_OVERFLOW = 8,
        MYO_FLAG_SCHED_TIMEOUT = 16 /* opt-in substep scheduler gave up waiting (raised on env 0); the step is incomplete */ };
+/* A bad env (mj_checkPos / mj_checkVel / mj_checkAcc and DMSimScene.advance's reset, physics/mj_sim_scene.py:54-61).  An env is bad when, at
+ * the start of a substep, an entry of its qpos or qvel is non-finite or larger than 1e10 in magnitude (MYO_FLAG_BAD_STATE), or when that
+ * substep's qacc is (MYO_FLAG_BAD_QACC).  myo_step resets it like mj_resetData at that substep and runs no further substep of it in that
+ * launch; the other envs of the launch are untouched, bit for bit.  After the launch, for a bad env:
+ *   MYO_F_QPOS = qpos0; MYO_F_QVEL, ACT, CTRL, WARMSTART, QACC and TIME are exactly zero; the flag bit is set (until myo_status clears it);
+ *   MYO_F_TENLEN, ACTFORCE, LINKX, SENSORDATA and CFRC are zeros; MYO_F_ELAPSED counts on (sim.reset() does not end the gym episode).
+ * One deliberate exception to "a NaN in is a bad env": under MYO_ACTMAP_SIGMOID_FATIGUE the fatigue model's clip (np.clip in
+ * envs/myo/fatigue.py, which would keep the NaN in MA / MR / MF for good) is fminf / fmaxf here, so a NaN action drives the muscle with the
+ * clip's lower bound, the compartments stay finite and the env is not flagged: mj_resetData does not touch the compartments, so a NaN
+ * there would outlive every reset of the env.
+ * Every float field myo_batch_read returns is finite for every env.  None of this depends on the kernel that ran: lanes, size
+ * specialisation, integrator, substep scheduler, placement.
+ * Tasks.  Where the observation is a pass of its own (myo_obs, or the one-launch epilogue of myo_bench_rollout), MYO_F_OBS / REWARD / DONE /
+ * SOLVED / SITEXPOS and the reward-term row of a bad env are those of the reset state.  The walk / stand pass fused into myo_step writes what
+ * myo_obs would write right after the launch.  The fused TrackEnv step (MYO_TASK_TRACK with MYO_ACTMAP_CTRLRANGE), whose MJX reference has no
+ * error path, ends the episode of a bad env, with or without `autoreset`: MYO_F_DONE = 1, REWARD = 0, METRICS = 0, SOLVED = 0, the state of
+ * TrackEnv.reset (init_qpos; zero velocity, activation, control, warm start and time), MYO_F_ELAPSED = 0, MYO_F_OBS = [init_qpos, 0]. */
 
 /* per-env orientation of one world-welded body (ids continue after MYO_F_BODYPOS_RANGE) */
 enum {

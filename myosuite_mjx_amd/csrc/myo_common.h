@@ -122,7 +122,7 @@ struct DevBatch {
   int B;
   float *qpos, *qvel, *act, *ctrl, *warm, *time, *target, *obs, *reward, *done, *solved, *qacc, *tenlen, *actforce, *sitexpos;
   int *flags, *diag, *elapsed, *episode;
-  int* mprw;   // [B][64] MPR warm-start table carried between the substep tasks of the scheduler (word 63: entry count)
+  int* mprw;   // [B][64] MPR warm-start table carried between the substep tasks of the scheduler (word 63: entry count; word 62: nonzero when a substep of the running launch found the env bad and reset it)
   float* fatigue;          // [B][3][nu]: MA, MR, MF of the 3CC-r fatigue model (muscle condition "fatigue")
   float fat_dt;            // its time step = frame_skip * timestep
   int reaf_epl, reaf_eip;  // actuator ids of the EIP -> EPL tendon transfer (muscle condition "reafferentation")
@@ -219,6 +219,9 @@ __device__ __forceinline__ float normalize3(float* a) {
   return n;
 }
 __device__ __forceinline__ float clipf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
+// mju_clip on a control: the same value for every number, and a NaN stays a NaN (fminf / fmaxf would drop it and the env would step on as if
+// the control were at its lower bound: with mju_clip the activation, then qacc, goes non-finite and the env is found bad and reset)
+__device__ __forceinline__ float clip_ctrlf(float x, float lo, float hi) { return x == x ? clipf(x, lo, hi) : x; }
 __device__ __forceinline__ void quat2mat(float* R, const float* q) {
   float w = q[0], x = q[1], y = q[2], z = q[3];
   R[0] = w * w + x * x - y * y - z * z; R[1] = 2 * (x * y - w * z); R[2] = 2 * (x * z + w * y);

@@ -788,6 +788,12 @@ __global__ void __launch_bounds__(64) step_kernel(DevModel M, DevBatch Bt, const
     GFOR(i, nv) E[Y.Hp + tri(i, i)] += h * M.dof_damping[i];
     chol_packed<G>(E + Y.Hp, nv, sub);
     chol_solve<G>(E + Y.Hp, E + Y.search, nv, sub);
+    {  // (mj_checkAcc, second half: the solver may have kept a finite warm start where the forces, and so this acceleration, are not finite)
+      int bad = 0;
+      GFOR(i, nv) { float a = E[Y.search + i]; if (!(a == a) || fabsf(a) > MAXVALF) bad = 1; }
+      bad = grp_maxi<G>(bad);
+      if (bad && alive) { flags |= MYO_FLAG_BAD_QACC; alive = false; }
+    }
     if (alive) {
       GFOR(i, nu) E[Y.act + i] += h * E[Y.actdot + i];
       GFOR(i, nv) { float v = E[Y.qvel + i] + h * E[Y.search + i]; E[Y.qvel + i] = v; E[Y.qpos + i] += h * v; }
@@ -796,10 +802,11 @@ __global__ void __launch_bounds__(64) step_kernel(DevModel M, DevBatch Bt, const
     SYNC();
     STAMP(8);
   }
-  // a bad env is reset like mj_resetData (mj_sim_scene.py:56-61)
+  // a bad env is reset like mj_resetData (mj_sim_scene.py:56-61); its diagnostic rows (qacc, actuator lengths and forces) read zeros, as
+  // in the wave kernel.  (Its lanes ran the stages to the end of the launch next to the wave's other envs; only what is stored changes)
   if (!alive) {
-    GFOR(i, nv) { E[Y.qpos + i] = M.qpos0[i]; E[Y.qvel + i] = 0; E[Y.warm + i] = 0; }
-    GFOR(i, nu) { E[Y.act + i] = 0; E[Y.ctrl + i] = 0; }
+    GFOR(i, nv) { E[Y.qpos + i] = M.qpos0[i]; E[Y.qvel + i] = 0; E[Y.warm + i] = 0; E[Y.qacc + i] = 0; }
+    GFOR(i, nu) { E[Y.act + i] = 0; E[Y.ctrl + i] = 0; E[Y.tlen + i] = 0; E[Y.tforce + i] = 0; }
     time = 0;
   }
   SYNC();

@@ -15,7 +15,7 @@
 // ================================================================================================
 #define NCONW 32
 #define MPRW 14    // entries of the MPR warm-start table (pair id + normal): 224 B, the hand slice stays within 10 240 B = 16 waves per CU
-static_assert(4 * MPRW <= 63, "the scheduler carries the table in a 64-word row (word 63 = entry count)");
+static_assert(4 * MPRW <= 62, "the scheduler carries the table in a 64-word row (word 63 = entry count, word 62 = env reset in this launch)");
 struct LayW {
   int qpos, qvel, act, ctrl, lpos, lmat, axis, anchor, xv, qfc, sq, mprw, X;
   int tJ, tlen, tforce;                           // region X, tendon phase
@@ -293,9 +293,6 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
     E[Y.ctrl + i] = c;
   }
   float time = uniformf(ldstate<SCHED>(Bt.time + env));
-  if constexpr (SCHED && FULL && !TRK && !RK4) {   // sensors under the scheduler: the first substep's wave clears the env's "reset in this launch" mark
-    if (Bt.sens && s0 == 0 && lane_id == 0) Bt.sens[(size_t)env * Bt.ntouch] = 0.f;
-  }
   // MYO_TASK_TRACK (TRK models): this launch is a whole TrackEnv.step -- reference row of the pre-step time now, reward / done / reset at the end
   const bool track_on = TRK && Bt.track != nullptr && action != nullptr && actmap == MYO_ACTMAP_CTRLRANGE && nsub > 0;
   if constexpr (TRK) { if (track_on) track_lookup(*Bt.track, env, env + Bt.env_offset, time, Bt.elapsed[env], lane_id); }
@@ -316,14 +313,22 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
   const WaveCtx<LY> X{M, W, Y, Bt, wk, env, nv, nu, nq, nl_, nlevel_, maxnnz_, ngt_, nseg_, ncg_, npair_, has_free, neq, has_tl, h, nsub, kflags, ovf_env, ovf_row, nct, ovf_cand};
   bool alive = true;
   int n_mprw = 0;   // MPR warm-start table (pair id + last contact normal in geom 1's frame): entries of the previous substep
+  bool gone = false;   // scheduler: a wave of an earlier substep of this launch found the env bad and reset it (word 62 of the table row, which
+                       // the first substep's wave clears): the env's remaining substeps are no-ops, as in the one-wave-per-env launch
   if (SCHED && s0 > 0) {   // ... which another wave ran: the table travels through the batch like the state rows, so that a scheduled
     // launch computes exactly what the one-wave-per-env launch does
     const int* Wt = Bt.mprw + (size_t)env * 64;
     n_mprw = __builtin_amdgcn_readfirstlane(ldstatei<SCHED>(Wt + 63));
+    gone = __builtin_amdgcn_readfirstlane(ldstatei<SCHED>(Wt + 62)) != 0;
     if (lane_id < 4 * n_mprw) ((int*)(E + Y.mprw))[lane_id] = ldstatei<SCHED>(Wt + lane_id);
   }
   SYNC();
-  for (int step = s0; step < s1; step++) {
+  // How a bad env leaves this loop (`leave_substeps` below): step = nsub - 1; continue.  The increment makes step = nsub, which is the walk
+  // task's observation pass where this wave runs one (no scheduler: s1 = nsub + 1) and the end of the loop everywhere else (no walk task:
+  // s1 = nsub; scheduler: s1 = s0 + 1 <= nsub, the observation pass is a task of its own and finds the reset rows).  A `gone` env's physics
+  // tasks (s0 < nsub) start at s1, i.e. run nothing; its observation task (s0 == nsub) runs as usual
+#define leave_substeps() { step = nsub - 1; continue; }
+  for (int step = (gone && s0 < nsub) ? s1 : s0; step < s1; step++) {
     const bool op = walk && step == nsub;   // observation pass: position / velocity stages at the post-step state, then out
     // RK4 state of this substep (dead code otherwise): X0 and the weighted sums of the stage derivatives
     RkAcc<NTR> rk{0.f, 0.f, 0.f, 0.f, 0.f, {1.f, 0.f, 0.f, 0.f}, {}, {}};
@@ -335,6 +340,9 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
     int lane;   // opaque per-iteration copy of the lane id: address arithmetic derived from it cannot be hoisted (and spilled)
     lane = wave_lane();
     w_check_state<C>(X, lane, op, flags, alive);
+    // a bad env (wave-uniform) is reset like mj_resetData on the spot and leaves the substep loop: no stage ever runs on a non-finite state.
+    // The walk task's observation pass, if there is one, then runs on the reset state
+    if (__builtin_expect(!alive && !op, 0)) { w_reset_bad<C>(X, warm_row, time); leave_substeps(); }
     STAMP(0);
     w_kinematics<C>(X, lane, step);
     STAMP(1);
@@ -812,28 +820,29 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
     STAMP(7);
     d_nefc = nefc; d_ncon = ncon_real; d_iter = max(d_iter, iters);
     f_ncon += ncon; f_iter += iters;
-    {  // mj_checkAcc
-      bool bad = lane < nv && (!(qacc == qacc) || fabsf(qacc) > MAXVALF);
-      if (__any(bad) && alive) { flags |= MYO_FLAG_BAD_QACC; alive = false; }
+    {  // mj_checkAcc.  Both accelerations: a line search that finds no descent on non-finite data keeps the (finite) warm start as qacc,
+       // while the Euler solve carries the non-finite forces into qaccE -- the env is bad in this substep, not by its velocities in the next
+      bool bad = lane < nv && !(fabsf(qacc) <= MAXVALF && fabsf(qaccE) <= MAXVALF);   // (a NaN fails the comparison)
+      if (__builtin_expect(__any(bad), 0)) { flags |= MYO_FLAG_BAD_QACC; alive = false; w_reset_bad<C>(X, warm_row, time); leave_substeps(); }   // (as above)
     }
     if (lane < nv) warm_row[lane] = qacc;
     if constexpr (FULL && !TRK && !RK4) {   // on the last substep of the launch only (under the scheduler: by the wave that runs it)
-      if (Bt.sens && step == nsub - 1) w_touch_sensors<C>(X, lane, s0, alive, ncon_real, con, cjar);
+      if (Bt.sens && step == nsub - 1) w_touch_sensors<C>(X, lane, ncon_real, con, cjar);
     }
     if constexpr (RK4) {
-      if (alive) w_integrate_rk4<C>(X, lane, rk_stage, rk, actdot, qaccE, time);
+      w_integrate_rk4<C>(X, lane, rk_stage, rk, actdot, qaccE, time);
       SYNC();
-      if (alive && ++rk_stage < 4) goto rk_next_stage;
+      if (++rk_stage < 4) goto rk_next_stage;
     } else {
-      if (alive) w_integrate_euler<C>(X, lane, qaccE, time);
+      w_integrate_euler<C>(X, lane, qaccE, time);
     }
     SYNC();
     STAMP(8);
   }
+#undef leave_substeps
   if (!SCHED && FULL && (kflags & KF_AUX)) return;   // observation-only launch: the state arrays are not touched
-  if (!alive) w_reset_bad<C>(X, warm_row, s1, time);
   bool track_reset = false;
-  if constexpr (TRK) { if (track_on) track_reset = w_track_epilogue<C>(X, warm_row, time); }
+  if constexpr (TRK) { if (track_on) track_reset = w_track_epilogue<C>(X, warm_row, time, !alive); }
   if (lane_id < nq) Bt.qpos[(size_t)env * nq + lane_id] = E[Y.qpos + lane_id];
   if (lane_id < nv) {
     Bt.qvel[(size_t)env * nv + lane_id] = E[Y.qvel + lane_id];
@@ -847,6 +856,7 @@ __global__ void __launch_bounds__(64, WPE) step_kernel_w(const DevModel* __restr
     int* Wt = Bt.mprw + (size_t)env * 64;
     if (lane_id < 4 * n_mprw) Wt[lane_id] = ((const int*)(E + Y.mprw))[lane_id];
     if (lane_id == 63) Wt[63] = n_mprw;
+    if (lane_id == 62 && (s0 == 0 || !alive)) Wt[62] = alive ? 0 : 1;
   }
   if (lane_id == 0) {
     Bt.time[env] = time;

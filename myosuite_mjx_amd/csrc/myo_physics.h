@@ -263,7 +263,7 @@ __device__ __forceinline__ void muscle(const float* A, float len, float vel, flo
   else if (L <= b) { x = (L - 1) / fmaxf(MINVALF, b - 1); bias = -A[15] * fpmax * 0.5f * x * x; }   // A[15]: peak force of biasprm
   else { x = (L - b) / fmaxf(MINVALF, b - 1); bias = -A[15] * fpmax * (0.5f + x); }
   *force = gain * act + bias;
-  float cc = clipf(clipf(ctrl, A[12], A[13]), 0.f, 1.f), ac = clipf(act, 0.f, 1.f);
+  float cc = ctrl == ctrl ? clipf(clipf(ctrl, A[12], A[13]), 0.f, 1.f) : ctrl /* (a NaN stays one, as through mju_clip: see clip_ctrlf) */, ac = clipf(act, 0.f, 1.f);
   float tau_act = A[10] * (0.5f + 1.5f * ac), tau_deact = A[11] / (0.5f + 1.5f * ac);
   float dctrl = cc - act;
   *actdot = dctrl / fmaxf(MINVALF, dctrl > 0 ? tau_act : tau_deact);

@@ -238,7 +238,7 @@ template <class C, class LY> __device__ __forceinline__ float w_tendons(const Wa
     if (gt < nu) {
       const float* A = M.act + 16 * gt;
       float f, ad;
-      if (A[10] < 0.f) { f = A[0] * clipf(E[Y.ctrl + gt], A[12], A[13]) + A[1] + A[14] * (A[2] * L + A[3] * vel); ad = 0.f; }   // stateless affine actuator
+      if (A[10] < 0.f) { f = A[0] * clip_ctrlf(E[Y.ctrl + gt], A[12], A[13]) + A[1] + A[14] * (A[2] * L + A[3] * vel); ad = 0.f; }   // stateless affine actuator
       else muscle(A, A[14] * L, A[14] * vel, E[Y.act + gt], E[Y.ctrl + gt], &f, &ad);
       if constexpr (RK4) actdot[rr] = ad;
       else if (!op) E[Y.act + gt] += h * ad;   // Euler: the activation is advanced right here (nothing reads it again in this substep; a bad-state env is

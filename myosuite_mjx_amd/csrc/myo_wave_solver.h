@@ -367,8 +367,7 @@ template <class C, class LY> __device__ __forceinline__ void w_pack_mass(const W
 // its geoms on the sensor's body, a positive normal force, and the ray from the contact point along the normal (reversed when the
 // sensor's body is geom 2's) meeting the site volume.  The 24-dof, TRK and RK4 instantiations have no such code.
 // LDS: reads cpos, cnrm, cpair (overflow rows for contacts >= NC), lpos, lmat; writes nothing.
-template <class C, class LY> __device__ __forceinline__ void w_touch_sensors(const WaveCtx<LY>& X, int lane, int s0, bool alive, int ncon_real, const ConConst<C::NR>& con, const float (&cjar)[C::NR]) {
-  constexpr bool SCHED = C::SCHED;
+template <class C, class LY> __device__ __forceinline__ void w_touch_sensors(const WaveCtx<LY>& X, int lane, int ncon_real, const ConConst<C::NR>& con, const float (&cjar)[C::NR]) {
   const DevModelW& W = X.W; const LY& Y = X.Y; extern __shared__ __align__(16) float E[]; const DevBatch& Bt = X.Bt; float* const ovf_env = X.ovf_env;
   const int env = X.env, ovf_row = X.ovf_row;
   const int nts = Bt.ntouch;
@@ -409,11 +408,7 @@ template <class C, class LY> __device__ __forceinline__ void w_touch_sensors(con
   }
   float* const srow = Bt.sens + (size_t)env * nts;
   float* const crow = Bt.cfrc + (size_t)env * 3 * (nts + 1);
-  // an env reset in this launch reads zeros like mj_resetData: a bad state seen by this wave, or (scheduler) by the wave of an earlier
-  // substep, which left a negative mark in the env's first sensor word
-  bool wiped = !alive;
-  if (SCHED && s0 > 0) wiped = wiped || ldstate<SCHED>(srow) < 0.f;
-  const float keep = wiped ? 0.f : 1.f;
+  // (an env reset in this launch never gets here: w_reset_bad wrote its zeros, like mj_resetData)
   for (int s = 0; s < nts; s++) {
     const gpf T = W.touch + TOUCHR * s;
     const int sl = __float_as_int(T[0]), sty = __float_as_int(T[13]), sb = __float_as_int(T[17]);
@@ -450,40 +445,63 @@ template <class C, class LY> __device__ __forceinline__ void w_touch_sensors(con
     }
     const bool counts = fn > 0.f && (cb1 == sb || cb2 == sb) && meets;
     const float S = wave_sum(counts ? fn : 0.f), Sx = wave_sum(counts ? Fw[0] : 0.f), Sy = wave_sum(counts ? Fw[1] : 0.f), Sz = wave_sum(counts ? Fw[2] : 0.f);
-    if (lane == 0) { srow[s] = keep * S; crow[3 * s] = keep * Sx; crow[3 * s + 1] = keep * Sy; crow[3 * s + 2] = keep * Sz; }
+    if (lane == 0) { srow[s] = S; crow[3 * s] = Sx; crow[3 * s + 1] = Sy; crow[3 * s + 2] = Sz; }
   }
   const float Gx = wave_sum(Fw[0]), Gy = wave_sum(Fw[1]), Gz = wave_sum(Fw[2]);
-  if (lane == 0) { crow[3 * nts] = keep * Gx; crow[3 * nts + 1] = keep * Gy; crow[3 * nts + 2] = keep * Gz; }
+  if (lane == 0) { crow[3 * nts] = Gx; crow[3 * nts + 1] = Gy; crow[3 * nts + 2] = Gz; }
 }
 
-// A bad env is reset like mj_resetData (mj_sim_scene.py:56-61).
+// A bad env is reset like mj_resetData (mj_sim_scene.py:56-61), at the substep that finds it bad; the launch runs no further substep of it.
+// Its diagnostic rows read zeros: actuator lengths and forces, link frames, touch sensors and contact forces.
 // LDS: writes qpos, qvel, act, ctrl.
-template <class C, class LY> __device__ __forceinline__ void w_reset_bad(const WaveCtx<LY>& X, float* warm_row, int s1, float& time) {
-  constexpr bool SCHED = C::SCHED, TRK = C::TRK, RK4 = C::RK4, FULL = C::FULL;
+template <class C, class LY> __device__ __forceinline__ void w_reset_bad(const WaveCtx<LY>& X, float* warm_row, float& time) {
+  constexpr bool TRK = C::TRK, RK4 = C::RK4, FULL = C::FULL;
   const DevModel& M = X.M; const LY& Y = X.Y; extern __shared__ __align__(16) float E[]; const DevBatch& Bt = X.Bt;
-  const int env = X.env, nv = X.nv, nu = X.nu, nq = X.nq, nsub = X.nsub;
+  const int env = X.env, nv = X.nv, nu = X.nu, nq = X.nq;
+  SYNC();
   if (lane_id < nq) E[Y.qpos + lane_id] = M.qpos0[lane_id];
   if (lane_id < nv) { E[Y.qvel + lane_id] = 0; warm_row[lane_id] = 0.f; }
-  for (int i = lane_id; i < nu; i += 64) { E[Y.act + i] = 0; E[Y.ctrl + i] = 0; }
-  time = 0;
-  if constexpr (SCHED && FULL && !TRK && !RK4) {   // (the wave of the last substep reads the mark and writes zeros)
-    if (Bt.sens && s1 < nsub && lane_id == 0) Bt.sens[(size_t)env * Bt.ntouch] = -1.f;
+  for (int i = lane_id; i < nu; i += 64) {
+    E[Y.act + i] = 0; E[Y.ctrl + i] = 0;
+    Bt.tenlen[(size_t)env * nu + i] = 0.f; Bt.actforce[(size_t)env * nu + i] = 0.f;
   }
+  time = 0;
+  if constexpr (TRK) {
+    if (Bt.linkx) for (int i = lane_id; i < 12 * X.nl_; i += 64) Bt.linkx[(size_t)env * 12 * X.nl_ + i] = 0.f;
+  }
+  if constexpr (FULL && !TRK && !RK4) {
+    if (Bt.sens) {
+      const int nts = Bt.ntouch;
+      for (int i = lane_id; i < nts; i += 64) Bt.sens[(size_t)env * nts + i] = 0.f;
+      for (int i = lane_id; i < 3 * (nts + 1); i += 64) Bt.cfrc[(size_t)env * 3 * (nts + 1) + i] = 0.f;
+    }
+  }
+  SYNC();
 }
 
 // Epilogue of TrackEnv.step (mjx/myodm_v0.py:185-267, 297-304): reward / done / metrics on the stepped state, masked reset, observation.  Returns
 // true when the env was reset.
 // LDS: reads qpos, qvel, lpos, lmat; a reset writes qpos, qvel, act, ctrl.
-template <class C, class LY> __device__ __forceinline__ bool w_track_epilogue(const WaveCtx<LY>& X, float* warm_row, float& time) {
+template <class C, class LY> __device__ __forceinline__ bool w_track_epilogue(const WaveCtx<LY>& X, float* warm_row, float& time, bool dead) {
   const DevModel& M = X.M; const LY& Y = X.Y; extern __shared__ __align__(16) float E[]; const DevBatch& Bt = X.Bt;
   const int env = X.env, nv = X.nv, nu = X.nu, nq = X.nq;
   bool track_reset = false;
   SYNC();
   const DevTrack& K = *Bt.track;
-  const float done = uniformf(track_reward(K, Bt, env, lane_id, E + Y.qpos, E + Y.qvel, E + Y.lpos, E + Y.lmat, M.origin, [](float v) { return wave_sum(v); }));
-  const bool trunc = K.max_steps > 0 && !(done > 0.f) && Bt.elapsed[env] + 1 >= K.max_steps;   // gym TimeLimit of the registered ids
+  float done = 1.f;
+  // an env that the step found bad (wave-uniform) is an ended episode, with or without `autoreset`: done, no reward, no metrics, and the
+  // state of TrackEnv.reset (the MJX reference has no error path; include/myo_hip.h states this one).  No reward is evaluated on the link
+  // frames of a faulted substep
+  if (dead) {
+    if (lane_id == 0) {
+      Bt.reward[env] = 0.f; Bt.done[env] = 1.f;
+      float* mt = K.metrics + 4 * (size_t)env;
+      mt[0] = 0.f; mt[1] = 0.f; mt[2] = 0.f; mt[3] = 0.f;
+    }
+  } else done = uniformf(track_reward(K, Bt, env, lane_id, E + Y.qpos, E + Y.qvel, E + Y.lpos, E + Y.lmat, M.origin, [](float v) { return wave_sum(v); }));
+  const bool trunc = !dead && K.max_steps > 0 && !(done > 0.f) && Bt.elapsed[env] + 1 >= K.max_steps;   // gym TimeLimit of the registered ids
   if (lane_id == 0) Bt.solved[env] = trunc ? 1.f : 0.f;
-  if (K.autoreset && (done > 0.f || trunc)) {   // (wave-uniform) TrackEnv.reset of this env: init_qpos, zero velocity / activation / control / warm start / time
+  if (dead || (K.autoreset && (done > 0.f || trunc))) {   // (wave-uniform) TrackEnv.reset of this env: init_qpos, zero velocity / activation / control / warm start / time
     SYNC();
     if (lane_id < nq) E[Y.qpos + lane_id] = K.init_qpos[lane_id];
     if (lane_id < nv) { E[Y.qvel + lane_id] = 0.f; warm_row[lane_id] = 0.f; }

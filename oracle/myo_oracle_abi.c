@@ -164,17 +164,22 @@ int myo_step(myo_batch* b, const float* action, int actmap, int nsubsteps, void*
       c[i] = actmap == MYO_ACTMAP_MUSCLE_SIGMOID ? 1.0f / (1.0f + expf(-5.0f * (a - 0.5f))) : a;      /* base_v0.py:87-91 */
     }
     for (int i = 0; i < m->nu; i++) d->ctrl[i] = (real)c[i];
-    int itmax = 0;
+    int itmax = 0, was_reset = 0;   /* was_reset: this launch found the env bad and reset it (include/myo_hip.h, "A bad env") */
     for (int s = 0; s < nsubsteps; s++) {
       int r = myoo_step1(m, d);
+      if (r == 1 || r == 2) was_reset = 1;
       if (r == 1) b->flags[e] |= MYO_FLAG_BAD_STATE;
       if (r == 2) b->flags[e] |= MYO_FLAG_BAD_QACC;
       if (r == 4) b->flags[e] |= MYO_FLAG_CONTACT_OVERFLOW;
       if (d->solver_iter > itmax) itmax = d->solver_iter;
       if (r) break;
     }
-    for (int k = 0; k < m->nv; k++) b->qacc[(size_t)e * m->nv + k] = (float)d->qacc[k];
-    for (int i = 0; i < m->nu; i++) { b->tenlen[(size_t)e * m->nu + i] = (float)d->actuator_length[i]; b->actforce[(size_t)e * m->nu + i] = (float)d->actuator_force[i]; }
+    for (int k = 0; k < m->nv; k++) b->qacc[(size_t)e * m->nv + k] = was_reset ? 0.f : (float)d->qacc[k];
+    for (int i = 0; i < m->nu; i++) {
+      b->tenlen[(size_t)e * m->nu + i] = was_reset ? 0.f : (float)d->actuator_length[i];
+      b->actforce[(size_t)e * m->nu + i] = was_reset ? 0.f : (float)d->actuator_force[i];
+      if (was_reset) c[i] = 0.f;
+    }
     b->diag[(size_t)e * 8 + 0] = d->nefc; b->diag[(size_t)e * 8 + 1] = d->ncon; b->diag[(size_t)e * 8 + 2] = itmax;
   }
   return MYO_OK;

@@ -37,6 +37,9 @@ class Backend:
         L.myo_status.argtypes = [C.c_void_p, C.c_void_p]
         L.myo_sync.argtypes = [C.c_void_p]
         L.myo_batch_configure_walk.argtypes = [C.c_void_p, C.c_void_p]
+        L.myo_batch_field.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.myo_bench_last_kernel_name.argtypes = [C.c_void_p]
+        L.myo_bench_last_kernel_name.restype = C.c_char_p
 
     def err(self):
         return self.L.myo_last_error().decode()
@@ -75,6 +78,64 @@ class Backend:
         f = np.zeros(B, np.int32)
         assert self.L.myo_status(b, f.ctypes.data) == 0
         return f
+
+
+# widths of the fields the CPU twin serves (it has no myo_batch_field: the HIP library is asked instead)
+TWIN_WIDTH = {capi.F_QPOS: "nq", capi.F_QVEL: "nv", capi.F_ACT: "nu", capi.F_CTRL: "nu", capi.F_WARMSTART: "nv", capi.F_TIME: 1, capi.F_QACC: "nv",
+              capi.F_TENLEN: "nu", capi.F_ACTFORCE: "nu", capi.F_FLAGS: 1, capi.F_DIAG: 8}
+
+
+class AbiBatch:
+    """One model and one batch of B envs on either backend, behind the four calls the bad-env checks (tests/bad_env.py) make: write, read
+    (None for a field the batch does not have), step, status."""
+
+    def __init__(self, be, model, B):
+        self.be, self.B = be, B
+        self.h, self.dims = be.load(model.blob())
+        self.b = be.batch(self.h, B)
+
+    def width(self, field):
+        if self.be.device < 0:
+            w = TWIN_WIDTH.get(field)
+            return getattr(self.dims, w) if isinstance(w, str) else w
+        p, pitch, w = C.c_void_p(), C.c_size_t(), C.c_size_t()
+        rc = self.be.L.myo_batch_field(self.b, field, C.byref(p), C.byref(pitch), C.byref(w))
+        return w.value if rc == 0 and p.value else None
+
+    def write(self, field, a):
+        self.be.write(self.b, field, np.ascontiguousarray(a, np.int32 if field in capi.INT_FIELDS else np.float32).view(np.float32))
+
+    def read(self, field):
+        w = self.width(field)
+        return None if w is None else self.be.read(self.b, field, (self.B, w), np.int32 if field in capi.INT_FIELDS else np.float32)
+
+    def step(self, nsub):
+        self.be.step(self.b, nsub)
+
+    def status(self):
+        return self.be.status(self.b, self.B)
+
+    def kernel(self):
+        return self.be.L.myo_bench_last_kernel_name(self.b).decode()
+
+    def close(self):
+        self.be.L.myo_batch_free(self.b); self.be.L.myo_model_free(self.h)
+
+
+def bad_env_scenario(be, model, state, kind, nsub, dead, prep=None):
+    """The bad-env sequence of tests/bad_env.py on either backend, through the ABI alone: three batches of one model (the injected one, a clean
+    one, a fresh one for the residue check); prep(batch), if given, sets each of them up first (terrain, overrides).  Returns bad_env.run_bare's record plus the
+    name of the kernel the injected batch ran (None on the CPU twin)."""
+    import bad_env
+    bs = [AbiBatch(be, model, len(state[capi.F_QPOS])) for _ in range(3)]
+    for b in bs:
+        if prep is not None:
+            prep(b)
+    rec = bad_env.run_bare(*bs, model, state, kind, nsub, dead, f64_state=be.device < 0)
+    rec["kernel"] = bs[0].kernel() if be.device >= 0 else None
+    for b in bs:
+        b.close()
+    return rec
 
 
 def scenario(be, model, seed=3, B=6, nsub=10):

@@ -75,6 +75,47 @@ def fused_epilogue_equals_stepwise(case):
     return a.batch
 
 
+def bad_env_is_contained(case):
+    """One bad env among 8 (include/myo_hip.h, "A bad env"; the checks are tests/bad_env.py's task_contained), by a NaN velocity and by a
+    NaN action, through the env's step and observation pass.  The bad env is reset to qpos0 and flagged, its task rows are those of the
+    reset state, every row is finite and the other seven envs are untouched bit for bit.  Then a NaN velocity through one step of
+    myo_bench_rollout with its one-launch epilogue (task_post_kernel: observation, auto-reset, first observation of the new episodes):
+    the env is flagged, every row is finite, the others are those of a clean batch bit for bit, and the bad env's rows are bit for bit
+    what step, myo_obs, myo_autoreset, myo_obs_reset_only leave for the same injection."""
+    import myosuite_mjx_amd as myo
+    import bad_env as BE
+    from myosuite_mjx_amd import capi
+
+    def make(n):
+        envs = [myo.make(case.bench_id, num_envs=8, seed=1, as_torch=False, autoreset=False, **case.make_kwargs) for _ in range(n)]
+        for e in envs:
+            e.reset()
+        return envs
+    for kind in ("nan_qvel", "nan_action"):
+        env, clean = make(2)
+        BE.task_contained(env, clean, kind, 5)
+        assert env.batch.last_kernel_name() == case.kernel
+    env, clean, stepwise = make(3)
+    for e in (env, stepwise):
+        e.batch.write(capi.F_QVEL, BE.inject("nan_qvel", {capi.F_QVEL: e.batch.read(capi.F_QVEL)}, (5,))[capi.F_QVEL])
+    mode = capi.BENCH_OBS | capi.BENCH_FRESH_ACTIONS | capi.BENCH_AUTORESET
+    for e in (env, clean):
+        e.batch.bench_rollout(1, case.nsub, seed=3, mode=mode, max_episode_steps=env.max_episode_steps)
+    b, ptr = stepwise.batch, stepwise.batch.field_ptr(capi.F_ACTION)[0]
+    b.random_action(ptr, 3, 0)
+    b.step(ptr, capi.ACTMAP_MUSCLE_SIGMOID, case.nsub)
+    b.obs()
+    b.autoreset(env.max_episode_steps, 3)
+    b.obs_reset_only()
+    rows, rows_clean, rows_step = (BE.read_all(BE.HipRows(e.batch, None)) for e in (env, clean, stepwise))
+    flags = env.status()
+    assert flags[5] & capi.FLAG_BAD_STATE and not (np.delete(flags, 5) & (capi.FLAG_BAD_STATE | capi.FLAG_BAD_QACC)).any()
+    BE.assert_all_fields_finite(rows)
+    BE.assert_neighbours_bitwise(rows, rows_clean, (5,))
+    for f in ("F_QPOS", "F_QVEL", "F_ACT", "F_OBS", "F_REWARD", "F_DONE", "F_SOLVED", "F_ELAPSED", "F_SITEXPOS", "F_FLAGS"):      # (fused_epilogue_equals_stepwise's list)
+        assert rows[getattr(capi, f)].tobytes() == rows_step[getattr(capi, f)].tobytes(), f
+
+
 def every_id_steps(case, env_id):
     """Five env steps of U(-1, 1) actions at 256 envs: finite rows, the TRK kernel, no status flag, muscles activated.  Returns the env."""
     import myosuite_mjx_amd as myo

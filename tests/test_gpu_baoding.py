@@ -304,6 +304,10 @@ def test_targets_follow_the_goal_trajectory():
             assert np.abs(r - 2 * np.hypot(p[:, 2] * np.cos(ang), p[:, 3] * np.sin(ang))).max() < 1e-5
 
 
+def test_bad_env_is_contained():
+    H.bad_env_is_contained(CASE)
+
+
 def test_fused_bench_epilogue_equals_step_obs_autoreset():
     H.fused_epilogue_equals_stepwise(CASE)
 

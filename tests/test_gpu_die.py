@@ -244,6 +244,10 @@ def test_goal_views_are_writable_and_take_effect():
         myo.make("myoHandPenTwirlFixed-v0", num_envs=4).goal_offset
 
 
+def test_bad_env_is_contained():
+    H.bad_env_is_contained(CASE)
+
+
 def test_fused_bench_epilogue_equals_step_obs_autoreset():
     assert H.fused_epilogue_equals_stepwise(CASE).last_kernel_name() == TRK
 

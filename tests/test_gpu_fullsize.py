@@ -159,7 +159,8 @@ def test_config5_walk_4096_envs_keep_constraints(legs):
 
 def test_terrain_4096_envs_equal_their_shards():
     """myoLegRoughTerrainWalk-v0 at B = 4096 (substep scheduler + height-field instantiation) against 32-env shards (one wave per env): the
-    per-env terrain draw is keyed by the global env id, and scheduled / unscheduled launches compute bit-identical steps."""
+    per-env terrain draw is keyed by the global env id, and scheduled / unscheduled launches compute bit-identical steps (of envs that go bad in the launch too:
+    tests/test_gpu_bad_env.py::test_scheduler_gives_the_same_bits)."""
     import torch
     from myosuite_mjx_amd import capi
     B, K = 4096, 25

@@ -236,6 +236,10 @@ def test_offset_on_with_zero_offsets_is_offset_off(key):
         assert np.array_equal(x, y)
 
 
+def test_bad_env_is_contained():
+    H.bad_env_is_contained(CASE)
+
+
 def test_fused_bench_epilogue_equals_step_obs_autoreset(key):
     """myo_bench_rollout's one-launch epilogue (keyturn_post_kernel) = step, myo_obs, myo_autoreset, myo_obs_reset_only."""
     H.fused_epilogue_equals_stepwise(CASE)

@@ -254,6 +254,10 @@ def test_override_with_compiled_quat_is_override_off(pen):
         assert np.array_equal(x, y)
 
 
+def test_bad_env_is_contained():
+    H.bad_env_is_contained(CASE)
+
+
 def test_fused_bench_epilogue_equals_step_obs_autoreset():
     H.fused_epilogue_equals_stepwise(CASE)
 

@@ -11,10 +11,11 @@
 //   myo_wave_collision.h   broad phase, narrow phase
 //   myo_wave_solver.h   constraint rows, packed mass matrix, sensor readout, task epilogues (the solver itself is inline in the kernel)
 //   myo_ldl_mfma.h      dense LDL^T of the Newton Hessian on the FP32 matrix cores (included by myo_wave_util.h)
-//   myo_kernels_aux.h   RNG, placement hint, random actions, policy inference, reset, state-only observations, task_obs_kernel / task_post_kernel
+//   myo_kernels_aux.h   RNG, placement hint, random actions, policy inference, reset, task_obs_kernel / task_post_kernel
 //   myo_kernels_ppo.h   PPO training: policy sampling with log-probabilities, GAE (include/myo_hip_ppo.h)
 //   myo_host.h          host records: myo_model, myo_batch, the per-task hook record (TaskHooks) and its generic launchers
-//   myo_task_*.h        key-turn, pen, baoding, die, classic MyoDM: a task's observation body, its configure checks and its hook record
+//   myo_task_util.h     what the task files share: link-chain walk, row prologue, site gather, activation term, the common configure checks
+//   myo_task_<name>.h   pose, reach, stand, hold, keyturn, pen, baoding, die, myodm: a task's observation body, its configure checks and its hook record
 //   myo_host_model.h    myo_model_load in pieces: blob view, table upload, packing of the per-lane records, kernel class
 //   myo_host_batch.h    batch creation, the per-env override records, the table of fields behind myo_batch_field / read / write
 //   myo_rewards.h       reward-term rows and episode statistics: column table per task, walk term kernel, statistics kernel, entry points
@@ -36,6 +37,11 @@
 #include "myo_kernels_aux.h"
 #include "myo_kernels_ppo.h"
 #include "myo_host.h"
+#include "myo_task_util.h"
+#include "myo_task_pose.h"
+#include "myo_task_reach.h"
+#include "myo_task_stand.h"
+#include "myo_task_hold.h"
 #include "myo_task_keyturn.h"
 #include "myo_task_pen.h"
 #include "myo_task_baoding.h"
@@ -464,41 +470,8 @@ int myo_step(myo_batch* b, const float* action_dev, int actmap, int nsubsteps, v
   return launch_step(b, action_dev, actmap, nsubsteps, (hipStream_t)stream);
 }
 
-// the hooks of the tasks that live in myo_kernels_aux.h / this file, and the table of all tasks
-static int state_configure(myo_batch* b, const myo_task_config* c) {   // pose / stand / hold
-  const myo_model* m = b->model;
-  const int nv = m->dm.nv, nq = m->nq, na = m->dm.na_obs;
-  if (c->task == MYO_TASK_POSE) {
-    if (c->ntarget != nv) return fail(MYO_E_ARG, "pose task: ntarget must equal nq");
-    b->task.obs_dim = 3 * nv + na;
-  } else if (c->task == MYO_TASK_STAND) {
-    if (c->ntarget != 3) return fail(MYO_E_ARG, "stand task: ntarget must be 3 (target position)");
-    if (!(m->wave_ok && m->dw.has_free && nq == nv + 1)) return fail(MYO_E_UNSUPPORTED, "stand task needs a model with a free root joint");
-    b->task.obs_dim = nq + nv + 6 + na;
-  } else {
-    if (c->ntarget != 3) return fail(MYO_E_ARG, "hold task: ntarget must be 3 (goal position)");
-    if (!(m->wave_ok && m->dw.has_free && nq == nv + 1 && nv > 6)) return fail(MYO_E_UNSUPPORTED, "hold task needs a model whose last joint is one free object");
-    b->task.obs_dim = (nq - 7) + (nv - 6) + 6 + na;
-  }
-  return MYO_OK;
-}
-static const TaskHooks state_hooks = {state_configure, launch_task_obs<StateTask>, launch_task_post<StateTask>};
-
-// reach needs tip positions: its observation reuses the lanes kernel's kinematics stage and has no fused epilogue
-static int reach_configure(myo_batch* b, const myo_task_config* c) {
-  if (c->ntarget != 3 * c->ntip) return fail(MYO_E_ARG, "reach task: ntarget must be 3*ntip");
-  b->task.obs_dim = 2 * b->model->dm.nv + 6 * c->ntip + b->model->dm.na_obs;
-  return MYO_OK;
-}
-static int reach_obs(myo_batch* b, hipStream_t s, int obs_only, int) {
-  const int EPW = 4;
-  hipLaunchKernelGGL(reach_obs_kernel<16>, dim3((b->db.B + EPW - 1) / EPW), dim3(64), (size_t)EPW * b->model->env_lds_bytes, s, b->model->dm, b->db, b->task, obs_only);
-  return MYO_OK;
-}
-static const TaskHooks reach_hooks = {reach_configure, reach_obs, nullptr};
-
-// the walk observation lives in the step kernel: run it with zero substeps as an observation-only pass (configured by myo_batch_configure_walk;
-// in myo_bench_rollout the step launch itself observes)
+// the table of all tasks: every record but the walk's sits in its myo_task_<name>.h.  The walk observation lives in the step kernel: run it
+// with zero substeps as an observation-only pass (configured by myo_batch_configure_walk; in myo_bench_rollout the step launch itself observes)
 static int walk_obs(myo_batch* b, hipStream_t s, int obs_only, int reset_only) {
   return launch_step(b, nullptr, MYO_ACTMAP_NONE, 0, s, KF_AUX | (obs_only ? KF_OBS_ONLY : 0) | (reset_only ? KF_RESET_ONLY : 0));
 }
@@ -506,9 +479,11 @@ static const TaskHooks walk_hooks = {nullptr, walk_obs, nullptr};
 
 static const TaskHooks* task_hooks(int task) {
   switch (task) {
-    case MYO_TASK_POSE: case MYO_TASK_STAND: case MYO_TASK_HOLD: return &state_hooks;
+    case MYO_TASK_POSE: return &pose_hooks;
     case MYO_TASK_REACH: return &reach_hooks;
     case MYO_TASK_WALK: return &walk_hooks;
+    case MYO_TASK_STAND: return &stand_hooks;
+    case MYO_TASK_HOLD: return &hold_hooks;
     case MYO_TASK_TRACK: return &track_hooks;
     case MYO_TASK_KEYTURN: return &keyturn_hooks;
     case MYO_TASK_PEN: return &pen_hooks;

@@ -69,6 +69,7 @@ struct myo_batch {
   float* d_metrics = nullptr;     // [B][4]
   int track_frames = 0;
   int track_flavour = 0;          // myo_track_config.flavour: 0 MJX (fused into the step kernel), 1 classic gym TrackEnv (task_obs_kernel<MyodmTask>)
+  ResetArgs *d_reset = nullptr, reset_args{};   // task_post_kernel's copy of (db, task) in device memory, and what was last uploaded to it (launch_task_post)
   uint64_t reset_seed = 0;        // seed of the last myo_reset / myo_autoreset (classic flavour: keys the RANDOM reference draws)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   uint64_t bench_step = 0;
@@ -98,9 +99,19 @@ template <class Task> static int launch_task_obs(myo_batch* b, hipStream_t s, in
   hipLaunchKernelGGL(task_obs_kernel<Task>, dim3(b->db.B), dim3(64), 0, s, b->model->dm, b->db, b->task, (const DevTrack*)b->d_track, b->reset_seed, obs_only, reset_only);
   return MYO_OK;
 }
+// the device copy of (db, task) that task_post_kernel's reset reads: uploaded on the launch's stream whenever either record has changed
+static int sync_reset_args(myo_batch* b, hipStream_t s) {
+  if (!b->d_reset) { HIPCHK(hipMalloc((void**)&b->d_reset, sizeof(ResetArgs))); b->dev_allocs.push_back(b->d_reset); }
+  else if (!memcmp(&b->reset_args.Bt, &b->db, sizeof(DevBatch)) && !memcmp(&b->reset_args.T, &b->task, sizeof(TaskDev))) return MYO_OK;
+  memcpy(&b->reset_args.Bt, &b->db, sizeof(DevBatch)); memcpy(&b->reset_args.T, &b->task, sizeof(TaskDev));
+  HIPCHK(hipMemcpyAsync(b->d_reset, &b->reset_args, sizeof(ResetArgs), hipMemcpyHostToDevice, s));
+  return MYO_OK;
+}
 template <class Task> static int launch_task_post(myo_batch* b, hipStream_t s, uint64_t seed, int auto_max) {
-  hipLaunchKernelGGL(task_post_kernel<Task>, dim3(b->db.B), dim3(64), 0, s, b->model->dm, b->db, b->task, (const DevTrack*)b->d_track, b->model->nq,
-                     b->model->dm.qpos0, seed, b->env_offset, auto_max);
+  const int rc = sync_reset_args(b, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(task_post_kernel<Task>, dim3(b->db.B), dim3(64), 0, s, b->model->dm, b->db, b->task, (const DevTrack*)b->d_track,
+                     (const ResetArgs*)b->d_reset, b->model->nq, b->model->dm.qpos0, seed, b->env_offset, auto_max);
   return MYO_OK;
 }
 

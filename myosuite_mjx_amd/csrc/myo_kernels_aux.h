@@ -1,4 +1,4 @@
-// myo_kernels_aux.h -- small kernels: RNG, placement hint, random actions, policy inference, reset, observations.
+// myo_kernels_aux.h -- small kernels: RNG, placement hint, random actions, policy inference, reset, the two kernels every task body runs in.
 // Part of the single translation unit myo_hip.hip (included there, in this order); not a stand-alone header.
 #ifndef MYO_KERNELS_AUX_H
 #define MYO_KERNELS_AUX_H
@@ -123,10 +123,14 @@ __global__ void __launch_bounds__(POL_ENVS * POL_MAXW) policy_kernel(PolicyDev P
 // auto_max > 0: gym TimeLimit / done auto-reset (reset iff done or elapsed >= auto_max); else mask-driven reset.
 // One 64-lane workgroup per env: envs that are not reset leave after one test, the others write their rows coalesced
 // (one thread per env needed ~500 serialised scattered stores per reset: 27 ms for a full reset of 4096 leg envs)
+// TEST = false: the caller has made the test itself (task_post_kernel, which reads Bt and T of the reset from memory only afterwards)
+template <bool TEST = true>
 __device__ __forceinline__ bool reset_body(const DevBatch& Bt, const TaskDev& T, int nq, int nv, int nu, const float* qpos0, const uint8_t* mask, uint64_t seed,
                                            int env_offset, int auto_max, const int e, const int lane) {
-  if (auto_max > 0) { if (!(Bt.done[e] > 0.f || Bt.elapsed[e] >= auto_max)) return false; }
-  else if (mask && !mask[e]) return false;
+  if constexpr (TEST) {
+    if (auto_max > 0) { if (!(Bt.done[e] > 0.f || Bt.elapsed[e] >= auto_max)) return false; }
+    else if (mask && !mask[e]) return false;
+  }
   seed += 0x632BE59BD9B4E019ull * (uint64_t)Bt.episode[e];  // a fresh RNG stream per (env, episode)
   __syncthreads();                                            // every lane has read done / elapsed / episode before lane 0 updates them
   if (lane == 0) { Bt.episode[e] += 1; Bt.elapsed[e] = 0; Bt.done[e] = 0.f; Bt.time[e] = 0; }
@@ -237,6 +241,8 @@ __global__ void __launch_bounds__(64) reset_kernel(DevBatch Bt, TaskDev T, int n
   if ((int)blockIdx.x >= Bt.B) return;
   reset_body(Bt, T, nq, nv, nu, qpos0, mask, seed, env_offset, auto_max, blockIdx.x, threadIdx.x);
 }
+// what reset_apply reads of a batch, as one record in device memory (myo_batch::d_reset, kept equal to db / task by launch_task_post)
+struct ResetArgs { DevBatch Bt; TaskDev T; };
 
 // per-env body masses (MYO_F_BODYMASS): link mass, COM and inertia about the COM of every link of every env from its bodies' masses, the
 // recomposition lowering.py does at compile time (parallel-axis theorem over the bodies welded into the link).  Member m of link l (CSR
@@ -277,100 +283,6 @@ __global__ void __launch_bounds__(256) link_compose_kernel(DevBatch Bt, int nl, 
   for (int j = 0; j < 6; j++) o[4 + j] = (float)I[j];
 }
 
-// observation + reward (pose_v0.py:98-138, obs_vec_dict.py:86-98); one 64-lane workgroup per env, rows written coalesced
-__device__ __forceinline__ void obs_body(const DevModel& M, const DevBatch& Bt, const TaskDev& T, int obs_only, const int e, const int lane) {
-  const int nv = M.nv, nu = M.nu;
-  float dt = (float)T.frame_skip * M.timestep;
-  float* o = Bt.obs + (size_t)e * T.obs_dim;
-  const float* q = Bt.qpos + (size_t)e * nv;
-  const float* v = Bt.qvel + (size_t)e * nv;
-  const float* a = Bt.act + (size_t)e * nu;
-  if (T.task == MYO_TASK_POSE) {
-    float err2 = 0, act2 = 0;
-    for (int i = lane; i < nv; i += 64) {
-      float qi = q[i], pe = Bt.target[(size_t)e * T.ntarget + i] - qi;
-      o[i] = qi; o[nv + i] = v[i] * dt; o[2 * nv + i] = pe;
-      err2 += pe * pe;
-    }
-    for (int i = lane; i < nu; i += 64) { float ai = a[i]; const int sl = M.act_obs[i]; if (sl >= 0) { o[3 * nv + sl] = ai; act2 += ai * ai; } }
-    if (obs_only) return;
-    float dist = sqrtf(wave_sum(err2));
-    float actn = sqrtf(wave_sum(act2)) / (float)(M.na_obs > 0 ? M.na_obs : 1);
-    if (lane == 0) {
-      float bonus = (dist < T.pose_thd ? 1.f : 0.f) + (dist < 1.5f * T.pose_thd ? 1.f : 0.f);
-      float pen = dist > T.far_th ? -1.f : 0.f;
-      const float solved = dist < T.pose_thd ? 1.f : 0.f, done = dist > T.far_th ? 1.f : 0.f;
-      if (Bt.rwd) rwd_row(Bt, e, {-dist, bonus, pen, -actn, -dist, solved, done});        // pose_v0.py:118-135
-      else Bt.reward[e] = T.w_pose * (-dist) + T.w_bonus * bonus + T.w_act_reg * (-actn) + T.w_penalty * pen;
-      Bt.solved[e] = solved;
-      Bt.done[e] = done;
-    }
-  } else if (T.task == MYO_TASK_STAND) {
-    // walk_v0.py:68-127 (ReachEnvV0 on the legs).  The tip site rides on the free root link: world position = root position + R(root quat) tip_lpos
-    const int nq = T.nq;
-    const float* qq = Bt.qpos + (size_t)e * nq;
-    float vel2 = 0.f, act2 = 0.f, err2 = 0.f;
-    for (int i = lane; i < nq; i += 64) o[i] = qq[i];
-    for (int i = lane; i < nv; i += 64) { const float vd = v[i] * dt; o[nq + i] = vd; vel2 += vd * vd; }
-    if (lane < 3) {
-      float R[9];
-      const float qn = 1.0f / sqrtf(qq[3] * qq[3] + qq[4] * qq[4] + qq[5] * qq[5] + qq[6] * qq[6]);
-      const float uq[4] = {qq[3] * qn, qq[4] * qn, qq[5] * qn, qq[6] * qn};
-      quat2mat(R, uq);
-      const float p = qq[lane] + R[3 * lane] * T.tip_lpos[0] + R[3 * lane + 1] * T.tip_lpos[1] + R[3 * lane + 2] * T.tip_lpos[2] + M.origin[lane];
-      const float er = Bt.target[(size_t)e * T.ntarget + lane] - p;
-      o[nq + nv + lane] = p; o[nq + nv + 3 + lane] = er;
-      err2 = er * er;
-    }
-    for (int i = lane; i < nu; i += 64) { float ai = a[i]; const int sl = M.act_obs[i]; if (sl >= 0) { o[nq + nv + 6 + sl] = ai; act2 += ai * ai; } }
-    if (obs_only) return;
-    const float dist = sqrtf(wave_sum(err2)), veld = sqrtf(wave_sum(vel2));
-    const float actn = sqrtf(wave_sum(act2)) / (float)(M.na_obs > 0 ? M.na_obs : 1);
-    if (lane == 0) {
-      const float far_th = Bt.time[e] > 2.f * dt ? T.far_th : 1e30f;
-      const float bonus = (dist < 2.f * T.near_th ? 1.f : 0.f) + (dist < T.near_th ? 1.f : 0.f);
-      const float pen = dist > far_th ? 1.f : 0.f;
-      const float solved = dist < T.near_th ? 1.f : 0.f;
-      if (Bt.rwd) rwd_row(Bt, e, {10.0f - dist - 10.0f * veld, bonus, -100.0f * actn, -pen, -dist, solved, pen});   // walk_v0.py:117-133
-      else Bt.reward[e] = T.w_reach * (10.0f - dist - 10.0f * veld) + T.w_bonus * bonus + T.w_act_reg * (-100.0f * actn) + T.w_penalty * (-pen);
-      Bt.solved[e] = solved;
-      Bt.done[e] = pen;
-    }
-  } else if (T.task == MYO_TASK_TRACK) {
-    // TrackEnv.get_obs (mjx/myodm_v0.py:297-304): [qpos, qvel]; reward / done belong to the step kernel's epilogue (they need the reference row
-    // of the step and the body frames of its last substep) and are not recomputed here
-    const int nq = T.nq;
-    const float* qq = Bt.qpos + (size_t)e * nq;
-    for (int i = lane; i < nq; i += 64) o[i] = qq[i];
-    for (int i = lane; i < nv; i += 64) o[nq + i] = v[i];
-  } else if (T.task == MYO_TASK_HOLD) {
-    // obj_hold_v0.py:66-118.  The object's site sits at the origin of its free body, whose world position is the free joint's qpos
-    // (free-floating models are not origin-shifted); the goal site is world-fixed = the target row
-    const int nq = T.nq, nqh = nq - 7, nvh = nv - 6;
-    const float* qq = Bt.qpos + (size_t)e * nq;
-    for (int i = lane; i < nqh; i += 64) o[i] = qq[i];
-    for (int i = lane; i < nvh; i += 64) o[nqh + i] = v[i] * dt;
-    float err2 = 0.f, act2 = 0.f;
-    if (lane < 3) {
-      float p = qq[nqh + lane] + M.origin[lane], er = Bt.target[(size_t)e * T.ntarget + lane] - p;
-      o[nqh + nvh + lane] = p; o[nqh + nvh + 3 + lane] = er;
-      err2 = er * er;
-    }
-    for (int i = lane; i < nu; i += 64) { float ai = a[i]; const int sl = M.act_obs[i]; if (sl >= 0) { o[nqh + nvh + 6 + sl] = ai; act2 += ai * ai; } }
-    if (obs_only) return;
-    float dist = sqrtf(wave_sum(err2));
-    float actn = sqrtf(wave_sum(act2)) / (float)(M.na_obs > 0 ? M.na_obs : 1);
-    if (lane == 0) {
-      float bonus = (dist < 2.f * T.near_th ? 1.f : 0.f) + (dist < T.near_th ? 1.f : 0.f);
-      float drop = dist > T.far_th ? 1.f : 0.f;
-      const float solved = dist < T.near_th ? 1.f : 0.f;
-      if (Bt.rwd) rwd_row(Bt, e, {-dist, bonus, -actn, -drop, -dist, solved, drop});      // obj_hold_v0.py:102-117
-      else Bt.reward[e] = T.w_reach * (-dist) + T.w_bonus * bonus + T.w_act_reg * (-actn) + T.w_penalty * (-drop);
-      Bt.solved[e] = solved;
-      Bt.done[e] = drop;
-    }
-  }
-}
 // A task hands its observation to the two kernels below as a struct with one static function, Task::obs(M, Bt, T, K, seed, obs_only, e, lane),
 // that wraps its *_obs_body (StateObs / TrackObs take the body as a template argument, so a kernel's symbol carries its task's name).  K (the
 // track record) and seed (the seed of the last reset) are read by the classic MyoDM flavour only
@@ -380,7 +292,6 @@ struct StateObs {   // a body that reads the batch state alone
     Body(M, Bt, T, obs_only, e, lane);
   }
 };
-using StateTask = StateObs<obs_body>;   // pose / hold / stand / MJX track
 template <void (*Body)(const DevModel&, const DevBatch&, const TaskDev&, const DevTrack&, uint64_t, int, int, int)>
 struct TrackObs {   // a body that also reads the track record and the seed of the last reset (classic MyoDM)
   static __device__ __forceinline__ void obs(const DevModel& M, const DevBatch& Bt, const TaskDev& T, const DevTrack* K, uint64_t seed, int obs_only, int e, int lane) {
@@ -396,70 +307,19 @@ __global__ void __launch_bounds__(64) task_obs_kernel(DevModel M, DevBatch Bt, T
 }
 // observation / reward / done of the stepped state, gym TimeLimit + done auto-reset, and the first observation of the new episode for the
 // envs that were reset: the three launches of the per-step epilogue (task_obs_kernel, reset_kernel, task_obs_kernel(reset_only)) in one --
-// on the critical path between two step kernels every launch costs a few microseconds of dispatch gap
+// on the critical path between two step kernels every launch costs a few microseconds of dispatch gap.  The reset reads its copy of the batch and
+// task records through R, after the test: as kernel arguments their loads were issued on every env's path and spilled scalar registers there
 template <class Task>
-__global__ void __launch_bounds__(64) task_post_kernel(DevModel M, DevBatch Bt, TaskDev T, const DevTrack* K, int nq, const float* qpos0, uint64_t seed,
-                                                       int env_offset, int auto_max) {
+__global__ void __launch_bounds__(64) task_post_kernel(DevModel M, DevBatch Bt, TaskDev T, const DevTrack* K, const ResetArgs* __restrict__ R, int nq,
+                                                       const float* qpos0, uint64_t seed, int env_offset, int auto_max) {
   const int e = blockIdx.x, lane = threadIdx.x;
   if (e >= Bt.B) return;
   Task::obs(M, Bt, T, K, seed, 0, e, lane);
   __syncthreads();                       // reward / done of this env written (lane 0) before every lane tests them
-  if (reset_body(Bt, T, nq, M.nv, M.nu, qpos0, nullptr, seed, env_offset, auto_max, e, lane)) {
-    __syncthreads();                     // the new state rows (and what the reset drew for the task) are complete before they are read back
-    Task::obs(M, Bt, T, K, seed, 1, e, lane);
-  }
-}
-
-// reach task needs tip positions: per-env group kernel reusing the kinematics stage
-template <int G>
-__global__ void __launch_bounds__(64) reach_obs_kernel(DevModel M, DevBatch Bt, TaskDev T, int obs_only) {
-  extern __shared__ __align__(16) float smem[];
-  const Lay& Y = M.lay;
-  const int lane = threadIdx.x, grp = lane / G, sub = lane % G;
-  int env = blockIdx.x * (64 / G) + grp;
-  const bool valid = env < Bt.B;
-  if (!valid) env = Bt.B - 1;
-  float* E = smem + grp * Y.total;
-  const int nv = M.nv, nu = M.nu;
-  GFOR(i, nv) E[Y.qpos + i] = Bt.qpos[(size_t)env * nv + i];
-  SYNC();
-  stage_kinematics<G>(M, E, sub);
-  float dt = (float)T.frame_skip * M.timestep;
-  float* o = Bt.obs + (size_t)env * T.obs_dim;
-  float err2 = 0;
-  GFOR(i, T.ntip) {
-    float p[3];
-    site_world(M, E, T.tip_site[i], p);
-    for (int k = 0; k < 3; k++) {
-      p[k] += M.origin[k];  // kernels work relative to the lowered origin; observations are world coordinates
-      float tg = Bt.target[(size_t)env * T.ntarget + 3 * i + k];
-      float re = tg - p[k];
-      err2 += re * re;
-      if (valid) {
-        o[2 * nv + 3 * i + k] = p[k];
-        o[2 * nv + 3 * T.ntip + 3 * i + k] = re;
-        Bt.sitexpos[(size_t)env * 3 * T.ntip + 3 * i + k] = p[k];
-      }
-    }
-  }
-  err2 = grp_sum<G>(err2);
-  float actn = 0;
-  GFOR(i, nu) { float a = Bt.act[(size_t)env * nu + i]; const int sl = M.act_obs[i]; if (sl >= 0) { actn += a * a; if (valid) o[2 * nv + 6 * T.ntip + sl] = a; } }
-  actn = sqrtf(grp_sum<G>(actn)) / (float)(M.na_obs > 0 ? M.na_obs : 1);
-  if (valid) {
-    GFOR(i, nv) { o[i] = E[Y.qpos + i]; o[nv + i] = Bt.qvel[(size_t)env * nv + i] * dt; }
-    if (sub == 0 && !obs_only) {
-      float dist = sqrtf(err2);
-      float near_th = T.near_th, far_th = Bt.time[env] > 2 * dt ? T.far_th : 1e30f;
-      float bonus = (dist < 2 * near_th ? 1.f : 0.f) + (dist < near_th ? 1.f : 0.f);
-      float pen = dist > far_th ? -1.f : 0.f;
-      const float solved = dist < near_th ? 1.f : 0.f, done = dist > far_th ? 1.f : 0.f;
-      if (Bt.rwd) rwd_row(Bt, env, {-dist, bonus, -actn, pen, -dist, solved, done});      // reach_v0.py:126-141
-      else Bt.reward[env] = T.w_reach * (-dist) + T.w_bonus * bonus + T.w_act_reg * (-actn) + T.w_penalty * pen;
-      Bt.solved[env] = solved;
-      Bt.done[env] = done;
-    }
-  }
+  if (!(Bt.done[e] > 0.f || Bt.elapsed[e] >= auto_max)) return;   // (auto_max > 0: the epilogue is launched for an auto-reset only)
+  reset_body<false>(R->Bt, R->T, nq, M.nv, M.nu, qpos0, nullptr, seed, env_offset, auto_max, e, lane);
+  __syncthreads();                       // the new state rows (and what the reset drew for the task) are complete before they are read back
+  Task::obs(M, Bt, T, K, seed, 1, e, lane);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -12,11 +12,8 @@
 // target2; Bt.target row = start angle, sign, x radius, y radius, period.
 __device__ __forceinline__ void baoding_obs_body(const DevModel& M, const DevBatch& Bt, const TaskDev& T, int obs_only, const int e, const int lane) {
   const int nv = M.nv, nq = nv + 2, nh = nv - 12;
-  const float dt = (float)T.frame_skip * M.timestep;
-  float* o = Bt.obs + (size_t)e * T.obs_dim;
-  const float* q = Bt.qpos + (size_t)e * nq;
-  const float* v = Bt.qvel + (size_t)e * nv;
-  float p[3] = {0.f, 0.f, 0.f};
+  const auto [o, q, v, a, dt] = task_row(M, Bt, T, e, nq);
+  float p[3] = {0.f, 0.f, 0.f}, x[4][3];
   if (lane < 4) {
     const int s = T.tip_site[lane];
     if (lane < 2) {   // ball site: its free joint's position + R(quat) site_lpos
@@ -40,16 +37,8 @@ __device__ __forceinline__ void baoding_obs_body(const DevModel& M, const DevBat
       for (int c = 0; c < 3; c++) lp[c] = F[6 + 3 * (lane - 2) + c] + F[c] * X + F[3 + c] * Yc;
       link_point_pos(M, Bt, q, e, M.site_link[s], lp, p);
     }
-#pragma unroll
-    for (int c = 0; c < 3; c++) p[c] += M.origin[c];
-#pragma unroll
-    for (int c = 0; c < 3; c++) Bt.sitexpos[(size_t)e * 12 + 3 * lane + c] = p[c];
   }
-  float x[4][3];
-#pragma unroll
-  for (int i = 0; i < 4; i++)
-#pragma unroll
-    for (int c = 0; c < 3; c++) x[i][c] = __shfl(p[c], i);
+  site_gather<4>(M, Bt, e, lane, 4, p, x);
   if (lane < 3) {
     o[nh + lane] = x[0][lane];
     o[nh + 3 + lane] = v[nh + lane] * dt;
@@ -62,14 +51,8 @@ __device__ __forceinline__ void baoding_obs_body(const DevModel& M, const DevBat
   }
   for (int i = lane; i < nh; i += 64) o[i] = q[i];
   if (obs_only) return;
-  float actn = 0.f;
-  if (Bt.rwd) {   // act_reg (baoding_v1.py:220-222) is a column of the term row only: the registered reward does not weigh it
-    const int nu = M.nu;
-    const float* a = Bt.act + (size_t)e * nu;
-    float act2 = 0.f;
-    for (int i = lane; i < nu; i += 64) { const float ai = a[i]; if (M.act_obs[i] >= 0) act2 += ai * ai; }
-    actn = sqrtf(wave_sum(act2)) / (float)(M.na_obs > 0 ? M.na_obs : 1);
-  }
+  // act_reg (baoding_v1.py:220-222) is a column of the term row only: the registered reward does not weigh it
+  const float actn = Bt.rwd ? act_norm(M, act_sq(M, a, lane)) : 0.f;
   if (lane == 0) {
     float d1[3], d2[3];
 #pragma unroll
@@ -92,15 +75,15 @@ static int baoding_configure(myo_batch* b, const myo_task_config* c) {
   const myo_model* m = b->model;
   TaskDev& T = b->task;
   const int nv = m->dm.nv;
-  if (!(m->wave_ok && m->trk) || m->nq != nv + 2 || nv < 13) return fail(MYO_E_UNSUPPORTED, "baoding task: a TrackEnv-class model whose last two joints are free joints (the balls)");
+  if (!trk_model(m, 2) || nv < 13) return fail(MYO_E_UNSUPPORTED, "baoding task: a TrackEnv-class model whose last two joints are free joints (the balls)");
   const int ball[2] = {root_link_of_dofs(m, nv - 12, 6), root_link_of_dofs(m, nv - 6, 6)};
   if (ball[0] < 0 || ball[1] < 0 || ball[0] == ball[1]) return fail(MYO_E_UNSUPPORTED, "baoding task: the last twelve dofs must be two free joints of root bodies");
   if (c->ntip != 4 || c->ntarget != 5) return fail(MYO_E_ARG, "baoding task: ntip = 4 (ball1, ball2, target1, target2) and ntarget = 5 (goal parameters)");
-  for (int k = 0; k < 4; k++) if (c->tip_site[k] < 0 || c->tip_site[k] >= m->dims.nsite) return fail(MYO_E_ARG, "baoding task: site id out of range");
+  if (!sites_in_range(m, c, 4)) return fail(MYO_E_ARG, "baoding task: site id out of range");
   const int tb = m->site_body[c->tip_site[2]], tl = m->site_link[c->tip_site[2]];
   if (m->site_link[c->tip_site[0]] != ball[0] || m->site_link[c->tip_site[1]] != ball[1] || tb != m->site_body[c->tip_site[3]] || tl < 0 || m->body_link[tb] != tl)
     return fail(MYO_E_UNSUPPORTED, "baoding task: the ball sites must be on the balls, both target sites on one moving body");
-  if (!(c->far_th == c->far_th) || !(c->pose_thd == c->pose_thd)) return fail(MYO_E_ARG, "baoding task: far_th (drop_th) and pose_thd (proximity_th) numbers");
+  if (!is_number(c->far_th) || !is_number(c->pose_thd)) return fail(MYO_E_ARG, "baoding task: far_th (drop_th) and pose_thd (proximity_th) numbers");
   const float* bq = &m->body_lquat[4 * (size_t)tb];
   const double qd[4] = {bq[0], bq[1], bq[2], bq[3]};
   double R[9];

@@ -27,39 +27,18 @@ __device__ __forceinline__ void die_mat2euler(float* eu, const float* cx, const 
 // T.tip_site = object_o, object_x, object_y, object_z, target_o, target_x, target_y, target_z; T.tip_lpos = goal_obj_offset; Bt.target row =
 // the goal offset from the compiled target position.
 __device__ __forceinline__ void die_obs_body(const DevModel& M, const DevBatch& Bt, const TaskDev& T, int obs_only, const int e, const int lane) {
-  const int nv = M.nv, nu = M.nu, nh = nv - 6, b0 = 2 * nh - 1;
-  const float dt = (float)T.frame_skip * M.timestep;
-  float* o = Bt.obs + (size_t)e * T.obs_dim;
-  const float* q = Bt.qpos + (size_t)e * nv;
-  const float* v = Bt.qvel + (size_t)e * nv;
-  const float* a = Bt.act + (size_t)e * nu;
-  float p[3] = {0.f, 0.f, 0.f};
+  const int nv = M.nv, nh = nv - 6, b0 = 2 * nh - 1;
+  const auto [o, q, v, a, dt] = task_row(M, Bt, T, e, nv);
+  float p[3] = {0.f, 0.f, 0.f}, x[8][3];
   if (lane < 8) {   // lanes 0-3: the die's sites, 4-7: the target's
-    const int s = T.tip_site[lane];
-    link_point_pos(M, Bt, q, e, M.site_link[s], M.site_lpos + 3 * s, p);
+    site_pos(M, Bt, q, e, T.tip_site[lane], p);
     if (lane >= 4) {   // a static site of the per-env oriented body (checked at configure), moved by the env's goal offset
-      if (Bt.bquat) {
-        float D[9], Rq[9], w[3];
-        const float* c = Bt.bq_c;
-        const float* bq = Bt.bquat + 4 * (size_t)e;
-        const float qe[4] = {bq[0], bq[1], bq[2], bq[3]};
-        quat2mat(Rq, qe);
-        matmul3(D, Rq, c);
-        const float d[3] = {p[0] - c[9], p[1] - c[10], p[2] - c[11]};
-        matvec(w, D, d);
-        p[0] = c[9] + w[0]; p[1] = c[10] + w[1]; p[2] = c[11] + w[2];
-      }
+      if (Bt.bquat) body_rot_point({Bt.bquat + 4 * (size_t)e, Bt.bq_c, nullptr}, p);
       const float* g = Bt.target + 3 * (size_t)e;
       p[0] += g[0]; p[1] += g[1]; p[2] += g[2];
     }
-#pragma unroll
-    for (int k = 0; k < 3; k++) { p[k] += M.origin[k]; Bt.sitexpos[(size_t)e * 24 + 3 * lane + k] = p[k]; }
   }
-  float x[8][3];
-#pragma unroll
-  for (int i = 0; i < 8; i++)
-#pragma unroll
-    for (int k = 0; k < 3; k++) x[i][k] = __shfl(p[k], i);
+  site_gather<8>(M, Bt, e, lane, 8, p, x);
   float col[6][3];   // the columns of the die's frame (0-2) and of the target's (3-5)
 #pragma unroll
   for (int f = 0; f < 2; f++)
@@ -90,9 +69,7 @@ __device__ __forceinline__ void die_obs_body(const DevModel& M, const DevBatch& 
     o[nh - 1 + i] = v[i] * dt;
   }
   if (obs_only) return;
-  float act2 = 0.f;
-  for (int i = lane; i < nu; i += 64) { const float ai = a[i]; if (M.act_obs[i] >= 0) act2 += ai * ai; }
-  const float actn = sqrtf(wave_sum(act2)) / (float)(M.na_obs > 0 ? M.na_obs : 1);
+  const float actn = act_norm(M, act_sq(M, a, lane));
   if (lane == 0) {
     const float pos_dist = norm3(perr), rot_dist = norm3(rerr);
     const bool drop = pos_dist > T.far_th;
@@ -112,13 +89,11 @@ static int die_configure(myo_batch* b, const myo_task_config* c) {
   const myo_model* m = b->model;
   TaskDev& T = b->task;
   const int nv = m->dm.nv;
-  if (!(m->wave_ok && m->trk) || m->nq != nv || nv < 8) return fail(MYO_E_UNSUPPORTED, "die task: a TrackEnv-class model without free / ball joints whose last six joints are the die's");
-  const int ol = root_link_of_dofs(m, nv - 6, 6);
-  bool ok = ol >= 0;
-  for (int k = 0; k < 6; k++) ok = ok && m->dof_type[nv - 6 + k] == (k < 3 ? 2 : 3);
-  if (!ok) return fail(MYO_E_UNSUPPORTED, "die task: the last six joints must be 3 slides + 3 hinges of one root body");
+  if (!trk_model(m) || nv < 8) return fail(MYO_E_UNSUPPORTED, "die task: a TrackEnv-class model without free / ball joints whose last six joints are the die's");
+  const int ol = object_link_6dof(m);
+  if (ol < 0) return fail(MYO_E_UNSUPPORTED, "die task: the last six joints must be 3 slides + 3 hinges of one root body");
   if (c->ntip != 8 || c->ntarget != 3) return fail(MYO_E_ARG, "die task: ntip = 8 (object_o / x / y / z, target_o / x / y / z) and ntarget = 3 (goal offset)");
-  for (int k = 0; k < 8; k++) if (c->tip_site[k] < 0 || c->tip_site[k] >= m->dims.nsite) return fail(MYO_E_ARG, "die task: site id out of range");
+  if (!sites_in_range(m, c, 8)) return fail(MYO_E_ARG, "die task: site id out of range");
   if (b->bq_body < 0) return fail(MYO_E_ARG, "die task: quat_body (the target body) must be selected");
   if (m->site_body.empty() || m->site_pos0.empty() || m->body_pos0.empty()) return fail(MYO_E_UNSUPPORTED, "die task: the model blob lacks the body tables");
   const int ob = m->site_body[c->tip_site[0]], tb = b->bq_body;
@@ -137,7 +112,7 @@ static int die_configure(myo_batch* b, const myo_task_config* c) {
       const double *s0 = &m->site_pos0[3 * (size_t)c->tip_site[4 * f]], *sk = &m->site_pos0[3 * (size_t)c->tip_site[4 * f + k]];
       if (!(std::hypot(sk[0] - s0[0], sk[1] - s0[1], sk[2] - s0[2]) > 1e-6)) return fail(MYO_E_ARG, "die task: an axis site coincides with its origin site");
     }
-  if (!(c->near_th == c->near_th) || !(c->pose_thd == c->pose_thd) || !(c->far_th == c->far_th)) return fail(MYO_E_ARG, "die task: near_th (pos_th), pose_thd (rot_th) and far_th (drop_th) numbers");
+  if (!is_number(c->near_th) || !is_number(c->pose_thd) || !is_number(c->far_th)) return fail(MYO_E_ARG, "die task: near_th (pos_th), pose_thd (rot_th) and far_th (drop_th) numbers");
   double wo[3], wt[3];
   site_world0(ob, c->tip_site[0], wo);
   site_world0(tb, c->tip_site[4], wt);

@@ -1,5 +1,6 @@
 // myo_task_myodm.h -- the classic gym flavour of the MyoDM TrackEnv (envs/myo/myodm/myodm_v0.py, the entry point of the registered MyoDM
-// ids): observation / reward / done / metrics of MYO_TASK_TRACK batches configured with myo_track_config.flavour = 1.
+// ids): observation / reward / done / metrics of MYO_TASK_TRACK batches configured with myo_track_config.flavour = 1.  The MJX flavour
+// (flavour = 0) is fused into the TRK step kernel (myo_task_track.h); only its state row, mjx_track_obs_body, is here.
 //
 // The env step itself is BaseV0.step on the TRK step kernel, unchanged: the muscle sigmoid on the muscles, the raw action on the position
 // actuators (clamped to ctrlrange where the actuator force reads it, as MuJoCo clamps ctrl), frame_skip = 10 substeps.  get_obs_dict then
@@ -9,53 +10,6 @@
 #ifndef MYO_TASK_MYODM_H
 #define MYO_TASK_MYODM_H
 
-// world frame (relative to the lowered origin) of a frame fixed in link `link`: point lp -> p, rotation Rl -> R, at the joint positions q of
-// env e.  The walk of link_point_pos (myo_task_keyturn.h) with the rotation carried along.  Hinge / slide joints only (nq == nv, checked at
-// configure).
-__device__ __forceinline__ void myodm_link_frame(const DevModel& M, const DevBatch& Bt, const float* q, int e, int link, const float* lp, const float* Rl,
-                                                 float* p, float* R) {
-  p[0] = lp[0]; p[1] = lp[1]; p[2] = lp[2];
-#pragma unroll
-  for (int k = 0; k < 9; k++) R[k] = Rl[k];
-  for (int l = link; l >= 0; l = M.link_parent[l]) {
-    float A[9], c[3] = {M.link_pos[3 * l], M.link_pos[3 * l + 1], M.link_pos[3 * l + 2]};
-    const float lq[4] = {M.link_quat[4 * l], M.link_quat[4 * l + 1], M.link_quat[4 * l + 2], M.link_quat[4 * l + 3]};
-    quat2mat(A, lq);
-    if (Bt.bpos && l == Bt.bpos_link) {
-      const float* o = Bt.bpos + 3 * (size_t)e;
-      c[0] += o[0]; c[1] += o[1]; c[2] += o[2];
-    }
-    const int da = M.link_dofadr[l], dn = M.link_dofnum[l];
-    for (int k = 0; k < dn; k++) {
-      const int d = da + k;
-      const float al[3] = {M.dof_axis[3 * d], M.dof_axis[3 * d + 1], M.dof_axis[3 * d + 2]};
-      const float dp[3] = {M.dof_pos[3 * d], M.dof_pos[3 * d + 1], M.dof_pos[3 * d + 2]};
-      const float ang = q[d] - M.qpos0[d];
-      float ax[3], an[3];
-      matvec(ax, A, al);
-      matvec(an, A, dp);
-      an[0] += c[0]; an[1] += c[1]; an[2] += c[2];
-      if (M.dof_type[d] == 3) {   // hinge: rotate about the axis through the anchor
-        float sn, cs;
-        sincosf(ang, &sn, &cs);
-        const float oc = 1 - cs, x = al[0], y = al[1], z = al[2];
-        const float Rj[9] = {cs + oc * x * x, oc * x * y - sn * z, oc * x * z + sn * y, oc * x * y + sn * z, cs + oc * y * y, oc * y * z - sn * x,
-                             oc * x * z - sn * y, oc * y * z + sn * x, cs + oc * z * z};
-        float v[3];
-        matmul3(A, A, Rj);
-        matvec(v, A, dp);
-        c[0] = an[0] - v[0]; c[1] = an[1] - v[1]; c[2] = an[2] - v[2];
-      } else {                    // slide
-        c[0] += ax[0] * ang; c[1] += ax[1] * ang; c[2] += ax[2] * ang;
-      }
-    }
-    float w[3];
-    matvec(w, A, p);
-    p[0] = w[0] + c[0]; p[1] = w[1] + c[1]; p[2] = w[2] + c[2];
-    matmul3(R, A, R);
-  }
-}
-
 // get_obs_dict (:189-251, + act, base_v0.py:34-38) and get_reward_dict / check_termination (:253-311, :336-362) of env e.  Row: qpos (nq),
 // qvel (nv), hand_qpos_err (nr), hand_qvel_err (nr, or the single 0 of a reference without robot_vel), obj_com_err (3), act (na).
 // The reference row is looked up at t = elapsed * frame_skip * timestep + motion_start_time in double (the post-step sim.data.time, which
@@ -63,12 +17,9 @@ __device__ __forceinline__ void myodm_link_frame(const DevModel& M, const DevBat
 // global env id, env step).  `seed` is the seed of the last reset.
 __device__ __forceinline__ void myodm_obs_body(const DevModel& M, const DevBatch& Bt, const TaskDev& T, const DevTrack& K, uint64_t seed, int obs_only,
                                                const int e, const int lane) {
-  const int nv = M.nv, nu = M.nu, nr = K.robot_dim;
+  const int nv = M.nv, nr = K.robot_dim;
   const int vdim = K.has_vel ? nr : 1, oe = 2 * nv + nr + vdim;   // offset of obj_com_err
-  const float* q = Bt.qpos + (size_t)e * nv;
-  const float* v = Bt.qvel + (size_t)e * nv;
-  const float* a = Bt.act + (size_t)e * nu;
-  float* o = Bt.obs + (size_t)e * T.obs_dim;
+  const auto [o, q, v, a, dt] = task_row(M, Bt, T, e, nv);
   const int elapsed = Bt.elapsed[e];
   track_lookup<true>(K, e, e + Bt.env_offset, 0.f, elapsed, lane, (double)elapsed * (double)T.frame_skip * (double)M.timestep,
                      seed + 0x632BE59BD9B4E019ull * (uint64_t)Bt.episode[e]);
@@ -76,15 +27,10 @@ __device__ __forceinline__ void myodm_obs_body(const DevModel& M, const DevBatch
   const float* R = K.ref + (size_t)e * K.ref_pitch;
   const float* tc = R + 2 * nr;          // target object pose: com (3) | quaternion (4)
   // xipos / ximat of the object body (lane 0) and xipos of the wrist (lunate) body (lane 1) of the post-step state
-  float p[3] = {0.f, 0.f, 0.f}, Rb[9];
-  if (lane < 2) {
-    myodm_link_frame(M, Bt, q, e, lane == 0 ? K.obj_link : K.wrist_link, lane == 0 ? K.obj_p : K.wrist_p, K.obj_R, p, Rb);
-#pragma unroll
-    for (int k = 0; k < 3; k++) p[k] += M.origin[k];
-  }
-  float com[3], wr[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) { com[k] = __shfl(p[k], 0); wr[k] = __shfl(p[k], 1); }
+  float p[3] = {0.f, 0.f, 0.f}, Rb[9], x[2][3];
+  if (lane < 2) link_chain<true>(M, Bt, q, e, lane == 0 ? K.obj_link : K.wrist_link, lane == 0 ? K.obj_p : K.wrist_p, K.obj_R, p, Rb);
+  site_gather<2>(M, Bt, e, lane, 0, p, x);
+  const float *com = x[0], *wr = x[1];
   for (int i = lane; i < nv; i += 64) { o[i] = q[i]; o[nv + i] = v[i]; }
   float qe = 0.f, ve = 0.f;
   if (lane < nr) {
@@ -94,7 +40,7 @@ __device__ __forceinline__ void myodm_obs_body(const DevModel& M, const DevBatch
   }
   if (!K.has_vel && lane == 0) o[2 * nv + nr] = 0.f;
   if (lane < 3) o[oe + lane] = com[lane] - tc[lane];
-  for (int i = lane; i < nu; i += 64) { const int sl = M.act_obs[i]; if (sl >= 0) o[oe + 3 + sl] = a[i]; }
+  for (int i = lane; i < M.nu; i += 64) { const int sl = M.act_obs[i]; if (sl >= 0) o[oe + 3 + sl] = a[i]; }   // (the reward has no activation term)
   if (obs_only) return;
   const float q2 = wave_sum(qe * qe), v2 = wave_sum(ve * ve);
   if (lane == 0) {
@@ -125,10 +71,20 @@ __device__ __forceinline__ void myodm_obs_body(const DevModel& M, const DevBatch
 
 using MyodmTask = TrackObs<myodm_obs_body>;
 
+// the MJX flavour's row, TrackEnv.get_obs (mjx/myodm_v0.py:297-304): [qpos, qvel]; reward / done belong to the step kernel's epilogue (they
+// need the reference row of the step and the body frames of its last substep) and are not recomputed here
+__device__ __forceinline__ void mjx_track_obs_body(const DevModel& M, const DevBatch& Bt, const TaskDev& T, int, const int e, const int lane) {
+  const int nv = M.nv, nq = T.nq;
+  const auto [o, q, v, a, dt] = task_row(M, Bt, T, e, nq);
+  for (int i = lane; i < nq; i += 64) o[i] = q[i];
+  for (int i = lane; i < nv; i += 64) o[nq + i] = v[i];
+}
+using MjxTrackTask = StateObs<mjx_track_obs_body>;
+
 // MYO_TASK_TRACK (configured by myo_batch_configure_track: no configure hook).  The classic flavour observes with MyodmTask, keyed by the seed of the
 // last reset, and has a fused epilogue; the MJX flavour observes the state-only row and myo_bench_rollout skips its epilogue (the step kernel's own)
 static int track_obs(myo_batch* b, hipStream_t s, int obs_only, int reset_only) {
-  return b->track_flavour == 1 ? launch_task_obs<MyodmTask>(b, s, obs_only, reset_only) : launch_task_obs<StateTask>(b, s, obs_only, reset_only);
+  return b->track_flavour == 1 ? launch_task_obs<MyodmTask>(b, s, obs_only, reset_only) : launch_task_obs<MjxTrackTask>(b, s, obs_only, reset_only);
 }
 static int track_post(myo_batch* b, hipStream_t s, uint64_t seed, int max_episode_steps) {
   b->reset_seed = seed;

@@ -11,41 +11,17 @@
 // (3), object position - eps_ball (3), obj_rot - obj_des_rot (3), act (na).  T.tip_site = object top, object bottom, target top, target
 // bottom, eps_ball; T.tip_lpos = the object body's origin in the frame of the link of the last dof.
 __device__ __forceinline__ void pen_obs_body(const DevModel& M, const DevBatch& Bt, const TaskDev& T, int obs_only, const int e, const int lane) {
-  const int nv = M.nv, nu = M.nu, nh = nv - 6;
-  const float dt = (float)T.frame_skip * M.timestep;
-  float* o = Bt.obs + (size_t)e * T.obs_dim;
-  const float* q = Bt.qpos + (size_t)e * nv;
-  const float* v = Bt.qvel + (size_t)e * nv;
-  const float* a = Bt.act + (size_t)e * nu;
-  float p[3] = {0.f, 0.f, 0.f};
+  const int nv = M.nv, nh = nv - 6;
+  const auto [o, q, v, a, dt] = task_row(M, Bt, T, e, nv);
+  float p[3] = {0.f, 0.f, 0.f}, x[6][3];
   if (lane < 6) {   // lanes 0-4: the sites, 5: the object body's origin
     const int s = lane < 5 ? T.tip_site[lane] : 0;
     const int link = lane < 5 ? M.site_link[s] : M.dof_link[nv - 1];
     link_point_pos(M, Bt, q, e, link, lane < 5 ? M.site_lpos + 3 * s : T.tip_lpos, p);
-    if (Bt.bquat && lane < 5 && link < 0 && Bt.bq_flag[M.ncg + s]) {   // a static site of the per-env oriented body
-      float D[9], w[3];
-      const float* c = Bt.bq_c;
-      const float* bq = Bt.bquat + 4 * (size_t)e;
-      const float qe[4] = {bq[0], bq[1], bq[2], bq[3]};
-      float Rq[9];
-      quat2mat(Rq, qe);
-      matmul3(D, Rq, c);
-      const float d[3] = {p[0] - c[9], p[1] - c[10], p[2] - c[11]};
-      matvec(w, D, d);
-      p[0] = c[9] + w[0]; p[1] = c[10] + w[1]; p[2] = c[11] + w[2];
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++) p[k] += M.origin[k];
-    if (lane < 5) {
-#pragma unroll
-      for (int k = 0; k < 3; k++) Bt.sitexpos[(size_t)e * 15 + 3 * lane + k] = p[k];
-    }
+    // a static site of the per-env oriented body
+    if (Bt.bquat && lane < 5 && link < 0 && Bt.bq_flag[M.ncg + s]) body_rot_point({Bt.bquat + 4 * (size_t)e, Bt.bq_c, nullptr}, p);
   }
-  float x[6][3];
-#pragma unroll
-  for (int i = 0; i < 6; i++)
-#pragma unroll
-    for (int k = 0; k < 3; k++) x[i][k] = __shfl(p[k], i);
+  site_gather<6>(M, Bt, e, lane, 5, p, x);
   const int so_t = T.tip_site[0], so_b = T.tip_site[1], st_t = T.tip_site[2], st_b = T.tip_site[3];
   float lo[3], lt[3];
 #pragma unroll
@@ -65,10 +41,9 @@ __device__ __forceinline__ void pen_obs_body(const DevModel& M, const DevBatch& 
     if (i < nh) o[i] = q[i];
     else o[nh + 3 + (i - nh)] = v[i] * dt;
   }
-  float act2 = 0.f;
-  for (int i = lane; i < nu; i += 64) { const float ai = a[i]; const int sl = M.act_obs[i]; if (sl >= 0) { o[nh + 21 + sl] = ai; act2 += ai * ai; } }
+  const float act2 = act_sq(M, a, lane, o + nh + 21);
   if (obs_only) return;
-  const float actn = sqrtf(wave_sum(act2)) / (float)(M.na_obs > 0 ? M.na_obs : 1);
+  const float actn = act_norm(M, act2);
   if (lane == 0) {
     const float pos_align = norm3(epos);
     float np = norm3(rot) * norm3(drot);
@@ -91,14 +66,12 @@ using PenTask = StateObs<pen_obs_body>;
 static int pen_configure(myo_batch* b, const myo_task_config* c) {
   const myo_model* m = b->model;
   const int nv = m->dm.nv;
-  if (!(m->wave_ok && m->trk) || m->nq != nv || nv < 7) return fail(MYO_E_UNSUPPORTED, "pen task: a TrackEnv-class model without free / ball joints whose last six joints are the pen's");
-  bool ok = root_link_of_dofs(m, nv - 6, 6) >= 0;
-  for (int k = 0; k < 6; k++) ok = ok && m->dof_type[nv - 6 + k] == (k < 3 ? 2 : 3);
-  if (!ok) return fail(MYO_E_UNSUPPORTED, "pen task: the last six joints must be 3 slides + 3 hinges of one root body");
+  if (!trk_model(m) || nv < 7) return fail(MYO_E_UNSUPPORTED, "pen task: a TrackEnv-class model without free / ball joints whose last six joints are the pen's");
+  if (object_link_6dof(m) < 0) return fail(MYO_E_UNSUPPORTED, "pen task: the last six joints must be 3 slides + 3 hinges of one root body");
   if (c->ntip != 5 || c->ntarget != 0) return fail(MYO_E_ARG, "pen task: ntip = 5 (object top, object bottom, target top, target bottom, eps_ball) and ntarget = 0");
-  for (int k = 0; k < 5; k++) if (c->tip_site[k] < 0 || c->tip_site[k] >= m->dims.nsite) return fail(MYO_E_ARG, "pen task: site id out of range");
+  if (!sites_in_range(m, c, 5)) return fail(MYO_E_ARG, "pen task: site id out of range");
   for (int k = 0; k < 3; k++) if (!std::isfinite(c->tip_lpos[k])) return fail(MYO_E_ARG, "pen task: tip_lpos must be finite");
-  if (!(c->far_th > 0.f) || !(c->pose_thd == c->pose_thd)) return fail(MYO_E_ARG, "pen task: far_th > 0, pose_thd a number");
+  if (!(c->far_th > 0.f) || !is_number(c->pose_thd)) return fail(MYO_E_ARG, "pen task: far_th > 0, pose_thd a number");
   b->task.obs_dim = (nv - 6) + 21 + m->dm.na_obs;
   return MYO_OK;
 }

@@ -171,6 +171,14 @@ __device__ __forceinline__ void body_rot(const BodyRot& br, float* D) {
   quat2mat(Rq, q);
   matmul3(D, Rq, br.c);
 }
+// ... of a static point of that body, in place: x = p_b + D (x - p_b)
+__device__ __forceinline__ void body_rot_point(const BodyRot& br, float* x) {
+  float D[9], v[3];
+  const float d[3] = {x[0] - br.c[9], x[1] - br.c[10], x[2] - br.c[11]};
+  body_rot(br, D);
+  matvec(v, D, d);
+  x[0] = br.c[9] + v[0]; x[1] = br.c[10] + v[1]; x[2] = br.c[11] + v[2];
+}
 // world centre / rotation of collision geom g from its record (DevModelW::cg_rec: link, lpos | rotation | type, bounding radius)
 template <class LY> __device__ __forceinline__ void geom_world_pos(const DevModelW& W, const LY& Y, const float* E, int g, float* out) {
   const float4 r0 = W.cg_rec[4 * g];
@@ -192,13 +200,7 @@ template <class LY> __device__ __forceinline__ void geom_world_mat(const DevMode
 // ... with the per-env orientation of BodyRot (br: a constant nullptr outside the TRK instantiation, which leaves the two calls above)
 template <class LY> __device__ __forceinline__ void geom_world_pos(const DevModelW& W, const LY& Y, const float* E, int g, float* out, const BodyRot* br) {
   geom_world_pos(W, Y, E, g, out);
-  if (br && br->q && __float_as_int(W.cg_rec[4 * g].x) < 0 && br->flag[g]) {
-    float D[9], v[3];
-    const float d[3] = {out[0] - br->c[9], out[1] - br->c[10], out[2] - br->c[11]};
-    body_rot(*br, D);
-    matvec(v, D, d);
-    out[0] = br->c[9] + v[0]; out[1] = br->c[10] + v[1]; out[2] = br->c[11] + v[2];
-  }
+  if (br && br->q && __float_as_int(W.cg_rec[4 * g].x) < 0 && br->flag[g]) body_rot_point(*br, out);
 }
 template <class LY> __device__ __forceinline__ void geom_world_mat(const DevModelW& W, const LY& Y, const float* E, int g, float* R, const BodyRot* br) {
   geom_world_mat(W, Y, E, g, R);

@@ -241,14 +241,19 @@ def test_new_and_changed_kernels_have_no_spill_and_no_scratch():
     import kernel_resources
     if not os.path.exists(capi.LIB_PATH):
         capi.build_library()
-    found = {}
+    found, bodies = {}, {"task_obs_kernel<": [], "task_post_kernel<": []}
     for r in kernel_resources.resources(capi.LIB_PATH):
         name = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip()
         for key in ("walk_terms_kernel(", "episode_stats_kernel(", "reach_obs_kernel<16>(", "task_obs_kernel<", "task_post_kernel<"):
             if name.startswith(("void " + key, key)) and "myodm_obs_body" not in name:
                 found.setdefault(key, []).append(r)
-    assert [len(found[k]) for k in ("walk_terms_kernel(", "episode_stats_kernel(", "reach_obs_kernel<16>(", "task_obs_kernel<", "task_post_kernel<")] == [1, 1, 1, 5, 5], \
-        {k: len(v) for k, v in found.items()}
+                if key in bodies:     # (a TrackObs body other than myodm's would not match: give it a case of its own here)
+                    bodies[key].append(re.match(r"(?:void )?task_\w+_kernel<StateObs<&\(?(\w+)\(", name).group(1))
+    assert [len(found[k]) for k in ("walk_terms_kernel(", "episode_stats_kernel(", "reach_obs_kernel<16>(")] == [1, 1, 1], {k: len(v) for k, v in found.items()}
+    # one body per task, each in one observation kernel and one fused epilogue; the MJX track row has no epilogue of its own (the step kernel's)
+    tasks = ["baoding_obs_body", "die_obs_body", "hold_obs_body", "keyturn_obs_body", "pen_obs_body", "pose_obs_body", "stand_obs_body"]
+    assert sorted(bodies["task_obs_kernel<"]) == sorted(tasks + ["mjx_track_obs_body"]), bodies
+    assert sorted(bodies["task_post_kernel<"]) == tasks, bodies
     for rs in found.values():
         for r in rs:
             assert r["vgpr_spill"] == 0 and r["scratch"] == 0 and r["vgpr"] + r["agpr"] <= 128, r

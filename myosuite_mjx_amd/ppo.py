@@ -6,6 +6,10 @@ What runs where.  HIP (include/myo_hip_ppo.h): the rollout's action sampling wit
 env step next to the env's own), the advantage recurrence (`myo_ppo_gae`, one launch per SGD step where a torch loop takes six or more per
 time step) and the refresh of the device policy's weights (`myo_policy_update`, device to device).  torch: the two networks' forward and
 backward passes, Adam, and a handful of reductions (running observation statistics, metrics).
+With `train(..., update="hip")` (opt-in; the default is the torch update above) the whole SGD step is HIP as well: `Learner` wraps
+`myo_ppo_learner_step`, which gathers and normalises the minibatch's observations, runs both networks forward and backward on the FP32
+matrix cores, GAE, the loss and Adam in 3 (policy layers + value layers) + 2 launches, and keeps the parameters on the device.  torch then
+only draws the permutation and the entropy noise and keeps the running observation statistics.
 
 Every function below dispatches on where its tensors live: CUDA tensors go to the HIP kernel, CPU tensors to a plain torch statement of
 the same formula, which is also what a CPU-only training run (`backend="torch"`, or an env whose observations are CPU tensors) uses.
@@ -212,6 +216,135 @@ def params_dict(stats, pw, pb, vw, vb):
     return out
 
 
+class _LearnerConfig(C.Structure):
+    """myo_ppo_config of include/myo_hip_ppo.h."""
+    _fields_ = [("obs_dim", C.c_int), ("act_dim", C.c_int), ("policy_nlayers", C.c_int), ("policy_out", C.c_int * 8),
+                ("value_nlayers", C.c_int), ("value_out", C.c_int * 8), ("max_unroll", C.c_int), ("max_minibatch", C.c_int),
+                ("learning_rate", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("adam_eps", C.c_double),
+                ("discounting", C.c_float), ("gae_lambda", C.c_float), ("clipping_epsilon", C.c_float), ("entropy_cost", C.c_float),
+                ("reward_scaling", C.c_float), ("normalize_advantage", C.c_int)]
+
+
+def _learner_lib():
+    L = capi.lib()
+    pp = C.POINTER(C.POINTER(C.c_float))
+    L.myo_ppo_learner_create.argtypes = [C.c_int, C.POINTER(_LearnerConfig), pp, pp, pp, pp, C.POINTER(C.c_void_p)]
+    L.myo_ppo_learner_free.argtypes = [C.c_void_p]
+    L.myo_ppo_learner_free.restype = None
+    L.myo_ppo_learner_step.argtypes = [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5
+    L.myo_ppo_learner_tensor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    return L
+
+
+class Learner:
+    """The device learner (include/myo_hip_ppo.h): both networks' parameters, their gradients and Adam's moments live in the library, and
+    `step` is one whole minibatch SGD step -- what one pass of `train`'s inner loop does with torch autograd and `torch.optim.Adam` -- as
+    HIP kernels on torch's current stream, without allocation or host synchronisation.
+
+    pw, pb, vw, vb: the initial parameters as `init_networks` returns them (any device; kernels [in, out]).  max_unroll and max_minibatch
+    size the workspace: `step` takes any T <= max_unroll and any number of unrolls <= max_minibatch.  Hyperparameters: learning_rate,
+    beta1, beta2, adam_eps (torch.optim.Adam's), discounting, gae_lambda, clipping_epsilon, entropy_cost, reward_scaling,
+    normalize_advantage, with `train`'s defaults.  Layer widths 1..MAX_WIDTH, at most MAX_LAYERS layers per network, any obs_dim.
+    NaNs in the inputs end up in the parameters, as they do with torch."""
+
+    WHICH = {"param": 0, "grad": 1, "m": 2, "v": 3}
+
+    def __init__(self, obs_dim, act_dim, pw, pb, vw, vb, max_unroll, max_minibatch, *, learning_rate=3e-4, beta1=0.9, beta2=0.999,
+                 adam_eps=1e-8, discounting=0.95, gae_lambda=0.95, clipping_epsilon=0.3, entropy_cost=1e-3, reward_scaling=5.0,
+                 normalize_advantage=True, device=0):
+        self.h = None
+        host = [[capi._f32(a.detach().cpu().numpy() if hasattr(a, "detach") else a) for a in group] for group in (pw, pb, vw, vb)]
+        if len(host[0]) != len(host[1]) or len(host[2]) != len(host[3]) or not host[0] or not host[2]:
+            raise ValueError("Learner: one bias per kernel, at least one layer per network")
+        self.obs_dim, self.act_dim, self.device = int(obs_dim), int(act_dim), int(device)
+        self.max_unroll, self.max_minibatch = int(max_unroll), int(max_minibatch)
+        sizes = []
+        for ws, bs in ((host[0], host[1]), (host[2], host[3])):
+            nin = self.obs_dim
+            for w, b in zip(ws, bs):
+                if w.ndim != 2 or w.shape[0] != nin or b.shape != (w.shape[1],):
+                    raise ValueError(f"Learner: kernel {w.shape} / bias {b.shape} do not continue a layer input of {nin}")
+                nin = w.shape[1]
+            sizes.append([w.shape[1] for w in ws])
+        cfg = _LearnerConfig(obs_dim=self.obs_dim, act_dim=self.act_dim, policy_nlayers=len(sizes[0]), value_nlayers=len(sizes[1]),
+                             max_unroll=self.max_unroll, max_minibatch=self.max_minibatch, learning_rate=learning_rate, beta1=beta1,
+                             beta2=beta2, adam_eps=adam_eps, discounting=discounting, gae_lambda=gae_lambda,
+                             clipping_epsilon=clipping_epsilon, entropy_cost=entropy_cost, reward_scaling=reward_scaling,
+                             normalize_advantage=int(bool(normalize_advantage)))
+        for k in range(min(8, len(sizes[0]))):
+            cfg.policy_out[k] = sizes[0][k]
+        for k in range(min(8, len(sizes[1]))):
+            cfg.value_out[k] = sizes[1][k]
+        arrs = [(C.POINTER(C.c_float) * len(g))(*(capi._ptr(a) for a in g)) for g in host]
+        h = C.c_void_p()
+        capi._chk(_learner_lib().myo_ppo_learner_create(self.device, C.byref(cfg), *arrs, C.byref(h)))
+        self.h = h
+        self.sizes = sizes
+        self._views = {}
+
+    def __del__(self):
+        try:
+            if self.h:
+                capi.lib().myo_ppo_learner_free(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def step_rc(self, obs_buf, u_buf, logp_buf, rew_buf, term_buf, trunc_buf, idx, mean, std, noise, loss_sums=None, T=None, mb=None):
+        """`step` without the check of the return code and of the tensors' shapes: pointers as given (None is NULL), T and mb as given."""
+        import torch
+        ptr = lambda a: None if a is None else a.data_ptr()
+        T = u_buf.shape[0] if T is None else T
+        mb = idx.shape[0] if mb is None else mb
+        B = u_buf.shape[1] if u_buf is not None else 0
+        with torch.cuda.device(self.device):
+            return _learner_lib().myo_ppo_learner_step(self.h, ptr(obs_buf), ptr(u_buf), ptr(logp_buf), ptr(rew_buf), ptr(term_buf), ptr(trunc_buf),
+                                                       int(T), int(B), ptr(idx), int(mb), ptr(mean), ptr(std), ptr(noise), ptr(loss_sums),
+                                                       torch.cuda.current_stream().cuda_stream)
+
+    def step(self, obs_buf, u_buf, logp_buf, rew_buf, term_buf, trunc_buf, idx, mean, std, noise, loss_sums=None):
+        """One SGD step on the unrolls `idx` of a rollout.  Contiguous float32 CUDA tensors: obs_buf [T + 1, B, obs_dim], u_buf [T, B,
+        act_dim], logp_buf / rew_buf / term_buf / trunc_buf [T, B], mean / std [obs_dim], noise [T, mb, act_dim]; idx: mb int64 env columns
+        without repeats (a slice of a permutation is fine).  loss_sums: 3 floats to which the step's policy, value and entropy loss are
+        added on the device, or None."""
+        import torch
+        T, B, mb = u_buf.shape[0], u_buf.shape[1], idx.shape[0]
+        want = [(obs_buf, (T + 1, B, self.obs_dim)), (u_buf, (T, B, self.act_dim)), (logp_buf, (T, B)), (rew_buf, (T, B)), (term_buf, (T, B)),
+                (trunc_buf, (T, B)), (mean, (self.obs_dim,)), (std, (self.obs_dim,)), (noise, (T, mb, self.act_dim))]
+        if loss_sums is not None:
+            want.append((loss_sums, (3,)))
+        for a, shape in want:
+            if not a.is_cuda or a.dtype != torch.float32 or not a.is_contiguous() or tuple(a.shape) != shape:
+                raise ValueError(f"Learner.step: a contiguous float32 CUDA tensor of shape {shape} is needed, got {a.dtype} {tuple(a.shape)}")
+        if not idx.is_cuda or idx.dtype != torch.int64 or idx.dim() != 1 or not idx.is_contiguous():
+            raise ValueError("Learner.step: idx is a contiguous int64 CUDA vector")
+        capi._chk(self.step_rc(obs_buf, u_buf, logp_buf, rew_buf, term_buf, trunc_buf, idx, mean, std, noise, loss_sums))
+
+    def tensors(self, which="param"):
+        """(pw, pb, vw, vb): lists of torch views (zero copy, cached) of the learner's own buffers; which = "param", "grad" (of the last
+        step), "m" or "v" (Adam's moments)."""
+        import torch
+        if which not in self._views:
+            L, out = _learner_lib(), []
+            for net in (0, 1):
+                nin = self.obs_dim
+                ws, bs = [], []
+                for layer, nout in enumerate(self.sizes[net]):
+                    for what, shape, dst in ((0, (nin, nout), ws), (1, (nout,), bs)):
+                        p, n = C.c_void_p(), C.c_size_t()
+                        capi._chk(L.myo_ppo_learner_tensor(self.h, net, layer, what, self.WHICH[which], C.byref(p), C.byref(n)))
+                        assert n.value == int(np.prod(shape))
+                        dst.append(torch.as_tensor(capi._DevArray(p.value, shape, "<f4", self), device=f"cuda:{self.device}"))
+                    nin = nout
+                out += [ws, bs]
+            self._views[which] = tuple(out)
+        return self._views[which]
+
+    def params_dict(self, stats):
+        """What `params_dict` gives, from the learner's parameters."""
+        return params_dict(stats, *self.tensors("param"))
+
+
 def save(path, params):
     """Writes the `.npz` that `BraxPolicy.from_npz` reads (obs_mean, obs_std, obs_count, w*, b*), the value network under vw* / vb*."""
     np.savez(path, **{k: np.asarray(v, np.float32) for k, v in params.items()})
@@ -220,7 +353,7 @@ def save(path, params):
 def train(env, num_timesteps, episode_length=None, unroll_length=50, num_minibatches=32, num_updates_per_batch=8, discounting=0.95,
           gae_lambda=0.95, learning_rate=3e-4, entropy_cost=1e-3, clipping_epsilon=0.3, reward_scaling=5.0, normalize_observations=True,
           normalize_advantage=True, action_repeat=1, policy_hidden=(32, 32, 32, 32), value_hidden=(256,) * 5, seed=1, progress_fn=None,
-          backend=None, keep_first_rollout=False):
+          backend=None, keep_first_rollout=False, update=None):
     """PPO on a batched env; returns (BraxPolicy or None, params, metrics).  The argument names and defaults are those of the reference's
     `mjx/ppo_continuous_action.py`, with brax's defaults for what that script leaves unset.
 
@@ -247,8 +380,15 @@ def train(env, num_timesteps, episode_length=None, unroll_length=50, num_minibat
     progress_fn(num_steps, metrics) is called once per iteration, like the reference's callback; metrics holds "eval/episode_reward"
     and "eval/episode_length" (means over the episodes that ended in the iteration, nan when none did), "episodes", "policy_loss",
     "value_loss", "entropy_loss", "steps_per_s", "rollout_s" and "update_s".  The list of all of them is returned.
-    keep_first_rollout adds host copies of the first unroll's buffers (obs, u, logp, reward) to the first metrics record."""
+    keep_first_rollout adds host copies of the first unroll's buffers (obs, u, logp, reward) to the first metrics record.
+
+    update: None or "torch": step (3) is torch autograd and torch.optim.Adam on `loss`.  "hip" (opt-in, needs backend "hip"): the
+    parameters live in a `Learner` and each SGD step is one `Learner.step`; no torch optimiser is built.  The permutation and the entropy
+    noise are drawn from the same generator in the same order either way, the loss sums stay on the device until the iteration's one
+    read, and the device policy is refreshed from the learner's parameter views."""
     import torch
+    if update not in (None, "torch", "hip"):
+        raise ValueError(f"update {update!r}: None, 'torch' or 'hip'")
     _check(env, unroll_length, num_minibatches, action_repeat, policy_hidden, episode_length)
     B, D, A, T = int(env.num_envs), int(env.obs_dim), int(env.act_dim), int(unroll_length)
     obs = torch.as_tensor(env.reset(seed=seed))
@@ -258,10 +398,18 @@ def train(env, num_timesteps, episode_length=None, unroll_length=50, num_minibat
     if backend not in ("hip", "torch") or (backend == "hip" and not obs.is_cuda):
         raise ValueError(f"backend {backend!r}: 'hip' needs an env whose observations are CUDA tensors, else 'torch'")
     hip = backend == "hip"
+    if update == "hip" and not hip:
+        raise ValueError("update 'hip' needs backend 'hip' (an env whose observations are CUDA tensors)")
     dgen = torch.Generator(device=dev).manual_seed(int(seed))       # permutations, entropy noise, the torch backend's action noise
     pw, pb, vw, vb = init_networks(D, A, policy_hidden, value_hidden, seed, dev)
     stats = RunningStats(D, dev)
-    opt = torch.optim.Adam([*pw, *pb, *vw, *vb], lr=learning_rate)
+    learner = opt = None
+    if update == "hip":
+        learner = Learner(D, A, pw, pb, vw, vb, T, B // num_minibatches, learning_rate=learning_rate, discounting=discounting,
+                          gae_lambda=gae_lambda, clipping_epsilon=clipping_epsilon, entropy_cost=entropy_cost, reward_scaling=reward_scaling,
+                          normalize_advantage=normalize_advantage, device=dev.index or 0)
+    else:
+        opt = torch.optim.Adam([*pw, *pb, *vw, *vb], lr=learning_rate)
     pol = None
     if hip:
         from .policy import BraxPolicy
@@ -327,10 +475,15 @@ def train(env, num_timesteps, episode_length=None, unroll_length=50, num_minibat
                 pol.update(obs_mean=stats.mean.contiguous(), obs_std=stats.std.contiguous())
         # (3) SGD
         sums = {k: torch.zeros((), **f32) for k in ("policy_loss", "value_loss", "entropy_loss")}
+        dev_sums = torch.zeros(3, **f32) if learner is not None else None
         for _ in range(num_updates_per_batch):
             perm = torch.randperm(B, generator=dgen, device=dev)
             for g in range(num_minibatches):
                 idx = perm[g * mb:(g + 1) * mb]
+                if learner is not None:
+                    noise = torch.randn((T, mb, A), generator=dgen, **f32)
+                    learner.step(obs_buf, u_buf, logp_buf, rew_buf, term_buf, trunc_buf, idx, stats.mean, stats.std, noise, dev_sums)
+                    continue
                 o = obs_buf[:, idx]
                 loc, scale = policy_forward(o[:T], stats.mean, stats.std, pw, pb)
                 v = mlp_forward((o - stats.mean) / stats.std, vw, vb).squeeze(-1)
@@ -345,7 +498,11 @@ def train(env, num_timesteps, episode_length=None, unroll_length=50, num_minibat
                 for k2 in sums:
                     sums[k2] += terms[k2]
         # (4) the new weights go to the device policy
-        if hip:
+        if learner is not None:
+            lw, lb, _, _ = learner.tensors("param")
+            pol.update(kernels=lw, biases=lb)
+            sums = dict(zip(sums, dev_sums))
+        elif hip:
             pol.update(kernels=[w.data for w in pw], biases=[b.data for b in pb])
         # one read of the iteration's numbers
         nsgd = num_updates_per_batch * num_minibatches
@@ -361,4 +518,4 @@ def train(env, num_timesteps, episode_length=None, unroll_length=50, num_minibat
         metrics.append(m)
         if progress_fn is not None:
             progress_fn((it + 1) * steps_per_iter, m)
-    return pol, params_dict(stats, pw, pb, vw, vb), metrics
+    return pol, learner.params_dict(stats) if learner is not None else params_dict(stats, pw, pb, vw, vb), metrics

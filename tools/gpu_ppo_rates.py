@@ -1,9 +1,10 @@
 """The numbers of profiles/ppo_training.md: what PPO training costs next to pure stepping, and myo_ppo_gae next to the torch loop.
 
-Part 1, per env id: `ppo.train` runs `--iterations` iterations (hyperparameters of tools/train_ppo.py, action_repeat 1); after every
-iteration its progress callback steps a second instance of the same id with device-resident random actions for `--steps` env steps
-between two device synchronisations, so training and pure stepping alternate within one process and clock drift hits both alike.  The
-first iteration (allocator and kernel warm-up) is reported but kept out of the medians.
+Part 1, per env id: `ppo.train` runs `--iterations` iterations (hyperparameters of tools/train_ppo.py, action_repeat 1) with the torch update,
+then with the HIP update (`update="hip"`), and the two take turns like that for `--rounds` rounds in one process; after every iteration
+the progress callback steps a second instance of the same id with device-resident random actions for `--steps` env steps between two
+device synchronisations, so the two update modes and pure stepping alternate and clock drift hits all alike.  The first iteration of
+every run (allocator and kernel warm-up) is reported but kept out of the medians.  One JSON line per id and update mode.
 Part 2: one myo_ppo_gae call against the torch loop (`ppo._gae_torch`) on the same CUDA tensors at T = 50, B = 128 and 4096, `--reps`
 calls per window between synchronisations, the two sides taking turns for `--windows` windows.
 Prints one JSON line per measurement (median, min, max).  No threshold: the numbers are recorded.
@@ -31,6 +32,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ids", nargs="*", default=["myoHandPoseRandom-v0:4096", "MyoHandAirplaneRandom-v0:1024"])
     ap.add_argument("--iterations", type=int, default=4)
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--updates", nargs="*", default=["torch", "hip"], choices=["torch", "hip"])
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--reps", type=int, default=50)
@@ -44,26 +47,34 @@ def main():
         acts = torch.rand((64, n, other.act_dim), device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * 2 - 1
         for i in range(30):
             other.step(acts[i % 64])
-        train, step = [], []
+        train, first, step = {u: [] for u in a.updates}, {u: [] for u in a.updates}, []
+        for _ in range(a.rounds):
+            for update in a.updates:
+                run = []
 
-        def progress(num_steps, m):
-            train.append(m)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for i in range(a.steps):
-                other.step(acts[i % 64])
-            torch.cuda.synchronize()
-            step.append(a.steps * n / (time.perf_counter() - t0))
+                def progress(num_steps, m):
+                    run.append(m)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for i in range(a.steps):
+                        other.step(acts[i % 64])
+                    torch.cuda.synchronize()
+                    if len(run) > 1:
+                        step.append(a.steps * n / (time.perf_counter() - t0))
 
-        ppo.train(env, a.iterations * n * 50, progress_fn=progress, seed=1)
-        rest = train[1:] or train
-        print(json.dumps({"id": env_id, "envs": n, "unroll_length": 50, "sgd_steps_per_iteration": 256,
-                          "train_env_steps_per_s": med([m["steps_per_s"] for m in rest]),
-                          "rollout_env_steps_per_s": med([n * 50 / m["rollout_s"] for m in rest]),
-                          "pure_stepping_env_steps_per_s": med(step[1:] or step),
-                          "rollout_share": med([m["rollout_s"] / (m["rollout_s"] + m["update_s"]) for m in rest]),
-                          "rollout_s": med([m["rollout_s"] for m in rest]), "update_s": med([m["update_s"] for m in rest]),
-                          "first_iteration": {"rollout_s": train[0]["rollout_s"], "update_s": train[0]["update_s"]}}), flush=True)
+                ppo.train(env, a.iterations * n * 50, progress_fn=progress, seed=1, update=update)
+                first[update].append(run[0])
+                train[update] += run[1:] or run
+        for update in a.updates:
+            rest = train[update]
+            print(json.dumps({"id": env_id, "envs": n, "update": update, "unroll_length": 50, "sgd_steps_per_iteration": 256,
+                              "train_env_steps_per_s": med([m["steps_per_s"] for m in rest]),
+                              "rollout_env_steps_per_s": med([n * 50 / m["rollout_s"] for m in rest]),
+                              "pure_stepping_env_steps_per_s": med(step) if step else None,
+                              "rollout_share": med([m["rollout_s"] / (m["rollout_s"] + m["update_s"]) for m in rest]),
+                              "rollout_s": med([m["rollout_s"] for m in rest]), "update_s": med([m["update_s"] for m in rest]),
+                              "update_ms_per_sgd_step": med([m["update_s"] / 256 * 1e3 for m in rest]),
+                              "first_iterations": [{"rollout_s": m["rollout_s"], "update_s": m["update_s"]} for m in first[update]]}), flush=True)
         del env, other
     for T, B in ((50, 128), (50, 4096)):
         g = torch.Generator("cuda").manual_seed(T + B)

@@ -33,6 +33,8 @@ def main():
     ap.add_argument("--reward-scaling", type=float, default=5.0)
     ap.add_argument("--no-normalize-observations", action="store_true")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--update", choices=["torch", "hip"], default="torch",
+                    help="the SGD step: torch autograd and Adam (default), or the device learner's HIP kernels")
     a = ap.parse_args()
     import myosuite_mjx_amd as myo
     from myosuite_mjx_amd import ppo
@@ -50,7 +52,7 @@ def main():
                              num_updates_per_batch=a.num_updates_per_batch, discounting=a.discounting, gae_lambda=a.gae_lambda,
                              learning_rate=a.learning_rate, entropy_cost=a.entropy_cost, clipping_epsilon=a.clipping_epsilon,
                              reward_scaling=a.reward_scaling, normalize_observations=not a.no_normalize_observations,
-                             action_repeat=a.action_repeat, seed=a.seed, progress_fn=progress)
+                             action_repeat=a.action_repeat, seed=a.seed, progress_fn=progress, update=a.update)
     print(f"time to train: {times[-1] - times[0]:.1f} s")
     if a.out:
         ppo.save(a.out, params)

@@ -9,10 +9,11 @@ importable, so the directory is `myosuite_mjx_amd`.
 
     m = myo.put_model("myohand_pose")                           # MJX-flavour functional API (sim.py)
     d = myo.make_data(m, 4096); myo.step(m, d, ctrl, nsubsteps=10)
+    myo.forward(m, d); xpos, ncon = myo.get(d, "xpos"), myo.get(d, "ncon")      # frames and contacts without a step
 """
 from .envs import REGISTRY, UNSUPPORTED, BatchedMyoEnv, make  # noqa: F401
 from .policy import BraxPolicy  # noqa: F401
-from .sim import HipSimScene, get, make_data, put_model, set_, step  # noqa: F401
+from .sim import HipSimScene, forward, get, make_data, put_model, set_, step  # noqa: F401
 from . import trace  # noqa: F401  (batched rollouts <-> the reference's Trace logger layout)
 from . import ppo  # noqa: F401  (PPO training on the device: ppo.train, the counterpart of mjx/ppo_continuous_action.py)
 

@@ -30,6 +30,14 @@ FLAG_BAD_STATE, FLAG_BAD_QACC, FLAG_CONTACT_OVERFLOW, FLAG_CAND_OVERFLOW, FLAG_S
 RWD_DENSE, RWD_SPARSE = 0, 1
 EP_RUNNING, EP_LAST, EP_FINISHED, EP_COUNT = range(4)
 _EP_DTYPE = {EP_RUNNING: np.float32, EP_LAST: np.float32, EP_FINISHED: np.uint8, EP_COUNT: np.int32}
+# forward pass (include/myo_hip_forward.h): buffer ids, words of a contact record, and the per-item shape of each buffer
+FWD_XPOS, FWD_XMAT, FWD_XIPOS, FWD_SITE_XPOS, FWD_SITE_XMAT, FWD_GEOM_XPOS, FWD_GEOM_XMAT, FWD_NCON, FWD_CONTACT = range(9)
+FWD_COUNT = 9
+FWD_CONTACT_WORDS = 16
+FWD_NAMES = {"xpos": FWD_XPOS, "xmat": FWD_XMAT, "xipos": FWD_XIPOS, "site_xpos": FWD_SITE_XPOS, "site_xmat": FWD_SITE_XMAT,
+             "geom_xpos": FWD_GEOM_XPOS, "geom_xmat": FWD_GEOM_XMAT, "ncon": FWD_NCON, "contact": FWD_CONTACT}
+_FWD_ITEM = {FWD_XPOS: (3,), FWD_XMAT: (3, 3), FWD_XIPOS: (3,), FWD_SITE_XPOS: (3,), FWD_SITE_XMAT: (3, 3), FWD_GEOM_XPOS: (3,),
+             FWD_GEOM_XMAT: (3, 3), FWD_NCON: (), FWD_CONTACT: (FWD_CONTACT_WORDS,)}
 
 
 class Dims(C.Structure):
@@ -203,6 +211,11 @@ def lib():
         L.myo_batch_episode_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
         L.myo_episode_update.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.myo_episode_clear.argtypes = [C.c_void_p, C.c_void_p]
+        L.myo_forward.argtypes = [C.c_void_p, C.c_void_p]
+        L.myo_forward_buffer.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.myo_forward_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+        L.myo_model_forward_dims.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
+        L.myo_forward_host_tables.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
         _lib = L
     return _lib
 
@@ -241,6 +254,12 @@ class HipModel:
 
     def set_switch(self, disable_contact=0, disable_limit=0, disable_ellipsoid=0):
         _chk(lib().myo_model_set_switch(self.h, disable_contact, disable_limit, disable_ellipsoid))
+
+    def forward_dims(self):
+        """(nbody, nsite, ngeom, ncon_max) of the forward pass's buffers; MyoError for a model without one (generic lanes kernel)."""
+        v = [C.c_int() for _ in range(4)]
+        _chk(lib().myo_model_forward_dims(self.h, *(C.byref(x) for x in v)))
+        return tuple(x.value for x in v)
 
     def __del__(self):
         try:
@@ -457,6 +476,29 @@ class HipBatch:
     def obs(self, stream=None):
         _chk(lib().myo_obs(self.h, stream))
 
+    # -- forward pass (include/myo_hip_forward.h) --
+    def forward(self, stream=None):
+        """Body, site and geom frames and the contact list at the current state, without a step (asynchronous; the first call allocates)."""
+        _chk(lib().myo_forward(self.h, stream))
+
+    def forward_ptr(self, which):
+        """(device pointer, pitch, width) of forward buffer FWD_*; MyoError before the first forward()."""
+        p, pitch, width = C.c_void_p(), C.c_size_t(), C.c_size_t()
+        _chk(lib().myo_forward_buffer(self.h, int(which), C.byref(p), C.byref(pitch), C.byref(width)))
+        return p.value, pitch.value, width.value
+
+    def forward_shape(self, which):
+        """Shape of forward buffer FWD_*: [B, n, 3], [B, n, 3, 3], [B] (ncon) or [B, ncon_max, 16] (contact)."""
+        width = self.forward_ptr(which)[2]
+        item = _FWD_ITEM[which]
+        return (self.B, width // int(np.prod(item)), *item) if item else (self.B,)
+
+    def forward_read(self, which) -> np.ndarray:
+        """Host copy of forward buffer FWD_* in its shape; FWD_NCON is int32, FWD_CONTACT float32 (words 13..15 of a record are int32 bits)."""
+        out = np.empty(self.forward_shape(which), np.int32 if which == FWD_NCON else np.float32)
+        _chk(lib().myo_forward_read(self.h, int(which), out.ctypes.data, out.nbytes))
+        return out
+
     def status(self) -> np.ndarray:
         out = np.zeros(self.B, np.int32)
         _chk(lib().myo_status(self.h, out.ctypes.data))
@@ -520,6 +562,77 @@ class FieldViews:
 
     def _stream(self):
         return self._torch.cuda.current_stream(self.device).cuda_stream if self._torch is not None else None
+
+    def forward(self):
+        """Body, site and geom frames and the contact list of the env's batch at its current state, without a step (what the reference's
+        get_obs_dict reads from sim.data: site_xpos, body_xpos, geom_xpos, ncon, contact): one launch, returns the ForwardRecord -- zero-copy
+        torch views, or fresh numpy copies without torch.  The state, observation and reward rows are not touched."""
+        self.batch.forward(self._stream())
+        if getattr(self, "_fwd", None) is None:
+            self._fwd = ForwardRecord(self.batch, self._torch, self.device)
+        else:
+            self._fwd.refresh()
+        return self._fwd
+
+
+class ContactList:
+    """`contact` of a forward pass: dist [B, C], pos [B, C, 3], frame [B, C, 9] (normal, then the two tangents), geom1 / geom2 [B, C] (model
+    geom ids, int32) and pair [B, C] (the kernel's pair index).  Entries at or beyond ncon[e] are unspecified; so is the order within an env."""
+
+    def __init__(self, rec, as_int):
+        ids = as_int(rec[..., 13:16])
+        self.dist, self.pos, self.frame = rec[..., 0], rec[..., 1:4], rec[..., 4:13]
+        self.geom1, self.geom2, self.pair = ids[..., 0], ids[..., 1], ids[..., 2]
+
+
+class ForwardRecord:
+    """What a forward pass leaves, as attributes: xpos / xipos / site_xpos / geom_xpos [B, n, 3], xmat / site_xmat / geom_xmat [B, n, 3, 3]
+    (site_xmat: None for a model compiled without site_quat), body_xpos / body_xmat (the reference's spelling of xpos / xmat), ncon [B]
+    int32 and contact (ContactList).  With a torch module they are zero-copy views of the library's buffers, valid for the batch's lifetime
+    and current after every `HipBatch.forward` once the stream has run it; without one, host arrays that `refresh()` reads again."""
+
+    def __init__(self, batch, torch=None, device=0):
+        self._batch, self._torch, self._device = batch, torch, device
+        self.refresh()
+
+    def _get(self, which):
+        b = self._batch
+        if self._torch is None:
+            return b.forward_read(which)
+        ptr = b.forward_ptr(which)[0]
+        arr = _DevArray(ptr, b.forward_shape(which), "<i4" if which == FWD_NCON else "<f4", b)
+        return self._torch.as_tensor(arr, device=f"cuda:{self._device}")
+
+    def refresh(self):
+        if self._torch is not None and hasattr(self, "xpos"):
+            return self       # views: nothing to copy
+        for name, which in FWD_NAMES.items():
+            if which == FWD_CONTACT:
+                as_int = (lambda t: t.view(self._torch.int32)) if self._torch is not None else (lambda a: a.view(np.int32))
+                self.contact = ContactList(self._get(which), as_int)
+            elif which == FWD_SITE_XMAT:
+                try:
+                    self.site_xmat = self._get(which)
+                except MyoError:
+                    self.site_xmat = None
+            else:
+                setattr(self, name, self._get(which))
+        self.body_xpos, self.body_xmat = self.xpos, self.xmat
+        return self
+
+
+def forward_host_tables(blob: bytes):
+    """The forward pass's export tables as the library builds them at model load (no GPU needed): (body, site, geom), each [n, 16] float64 =
+    link | position (3) | rotation (9) in the link's frame | bodies: COM in the link's frame (3); sites, geoms: body id, 0, 0."""
+    out = []
+    for t in range(3):
+        n = C.c_int()
+        _chk(lib().myo_forward_host_tables(blob, len(blob), t, None, 0, C.byref(n)))
+        a = np.zeros((n.value, 16), np.float64)
+        if n.value:
+            _chk(lib().myo_forward_host_tables(blob, len(blob), t, a.ctypes.data, a.size, C.byref(n)))
+        out.append(a)
+    return tuple(out)
 
 
 def set_lanes(lanes):

@@ -48,6 +48,11 @@ struct myo_model {
   std::vector<int> body_parent, body_jntnum, cg_body, site_body;
   std::vector<double> body_pos0, body_quat0;
   std::vector<double> site_pos0;   // compiled site_pos (site in its body's frame): the baoding task's moving targets keep its z
+  // forward pass (myo_kernel_forward.h): the per-body / site / geom export records and the collision geoms' model ids, built at load
+  bool fwd_ok = false, fwd_site_mat = false;
+  int fwd_nbody = 0, fwd_nsite = 0, fwd_ngeom = 0, fwd_ncap = 0;
+  const float *d_fwd_body = nullptr, *d_fwd_site = nullptr, *d_fwd_geom = nullptr;
+  const int* d_fwd_cg_geom = nullptr;
 };
 
 // episode statistics (myo_batch_enable_episode_stats): running and last-finished rows [B][4] = dense return, sparse return, length, solved
@@ -84,6 +89,8 @@ struct myo_batch {
   bool sens_on = false;          // touch sensors / contact forces enabled (DevBatch.sens / cfrc allocated)
   myo_episode episode;           // episode statistics (device buffers in dev_allocs)
   bool bq_on = false;            // per-env body orientation started (DevBatch.bquat / bquat_range / bq_c / bq_flag allocated)
+  bool fwd_on = false;           // forward buffers allocated (the first myo_forward)
+  void* fwd_buf[16] = {};        // ... one per MYO_FWD_* id
   std::vector<hipEvent_t> kev;   // per-launch event pairs around the step kernel (bench only)
   int kev_pending = 0;           // pairs recorded by asynchronous bench calls and not collected yet
   float last_kernel_ms = 0.f;

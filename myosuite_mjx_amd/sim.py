@@ -4,6 +4,8 @@
     mjx.put_data(m, d) (vmapped) -> make_data(model, B)         B environments' state on the device
     jit(mjx.step)(m, d)          -> step(model, data, ctrl, nsubsteps)   in place, asynchronous
     mjx.get_data(m, dx)          -> get(data, "qpos")           host numpy copy
+    jit(mjx.forward)(m, d)       -> forward(model, data)        frames and contacts at the current state, no step; then
+                                    get(data, "xpos" | "xmat" | "xipos" | "site_xpos" | "site_xmat" | "geom_xpos" | "geom_xmat" | "ncon" | "contact")
 """
 from __future__ import annotations
 
@@ -45,7 +47,18 @@ def step(m: DeviceModel, d: capi.HipBatch, ctrl=None, nsubsteps=1, stream=None):
     return d
 
 
+def forward(m: DeviceModel, d: capi.HipBatch, stream=None):
+    """Body, site and geom frames and the contact list of every env at its current state (in place, asynchronous; the state is not
+    touched).  Read them with `get`.  The contacts are those the next `step` sees in its first substep."""
+    d.forward(stream)
+    return d
+
+
 def get(d: capi.HipBatch, field: str) -> np.ndarray:
+    """Host copy of a state field, or of what the last `forward` left: frames as [B, n, 3] / [B, n, 3, 3], ncon [B] int32, contact
+    [B, ncon_max, 16] (dist | pos | frame 3 x 3, normal first | geom1, geom2, pair as int32 bits; `capi.ContactList` splits it)."""
+    if field in capi.FWD_NAMES:
+        return d.forward_read(capi.FWD_NAMES[field])
     return d.read(_FIELDS[field])
 
 
@@ -145,7 +158,7 @@ class HipSimScene:
     disable_option(_context), model.*_name2id -- is provided with its batched / MYOB meaning, see each method.
     """
 
-    def __init__(self, model_handle, num_envs=1, device=0, as_torch=True, sensors=False):
+    def __init__(self, model_handle, num_envs=1, device=0, as_torch=True, sensors=False, kinematics=False):
         self.num_envs = int(num_envs)
         self.device = device
         self.as_torch = as_torch
@@ -156,6 +169,8 @@ class HipSimScene:
             self._batch.enable_sensors()
         self.data = (_DeviceData(self._batch, self.num_envs, device, self.model, self.sensors) if as_torch
                      else _HostData(self.num_envs, self.model, self.sensors))
+        self.kinematics = bool(kinematics)
+        self._fwd = None
         self.lib = self.get_mjlib()
         self.renderer = self._create_renderer(self.sim)
         self.init_qpos = np.asarray(self.model.qpos0, np.float64).copy()
@@ -164,6 +179,8 @@ class HipSimScene:
         self._flags_stale = False
         self._dirty = not as_torch
         self._disabled = [0, 0, 0]
+        if self.kinematics:    # `data.xpos / site_xpos / geom_xpos / ncon / contact ...` (capi.ForwardRecord), refreshed by forward()
+            self.forward()
 
     def _load_simulation(self, model_handle, device=0):
         m = put_model(model_handle, device)
@@ -279,9 +296,26 @@ class HipSimScene:
         return out
 
     def forward(self):
-        """Derived quantities are recomputed inside every substep; state-only observations need no extra mj_forward."""
+        """Derived quantities are recomputed inside every substep; state-only observations need no extra mj_forward, and without
+        `kinematics=True` this launches nothing.  With it: one forward launch at the current state (host-mirror mode pushes a dirty state
+        first), after which `data.xpos / xmat / xipos / site_xpos / site_xmat / geom_xpos / geom_xmat` ([B, n, 3] or [B, n, 3, 3]; `body_xpos` /
+        `body_xmat` alias the first two), `data.ncon` [B] and `data.contact` (dist, pos, frame, geom1, geom2) are current: zero-copy torch
+        views with `as_torch=True`, host arrays refreshed here otherwise."""
         if not self.as_torch and self._dirty:
             self._push_state()
+        if not self.kinematics:
+            return
+        self._batch.forward(self._stream())
+        self._flags_stale = True
+        if self._fwd is None:
+            torch = None
+            if self.as_torch:
+                import torch
+            self._fwd = capi.ForwardRecord(self._batch, torch, self.device)
+        else:
+            self._fwd.refresh()
+        for k in ("xpos", "xmat", "xipos", "site_xpos", "site_xmat", "geom_xpos", "geom_xmat", "ncon", "contact", "body_xpos", "body_xmat"):
+            setattr(self.data, k, getattr(self._fwd, k))
 
     def reset(self):
         """mj_resetData for every env: qpos0, zero velocity / activation / time / warm start."""

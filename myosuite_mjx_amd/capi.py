@@ -90,6 +90,93 @@ class TrackConfig(C.Structure):
                 ("autoreset", C.c_int), ("max_episode_steps", C.c_int), ("seed", C.c_uint64), ("flavour", C.c_int)]
 
 
+class LearnerConfig(C.Structure):
+    """ctypes mirror of `myo_ppo_config` (include/myo_hip_ppo.h)."""
+    _fields_ = [("obs_dim", C.c_int), ("act_dim", C.c_int), ("policy_nlayers", C.c_int), ("policy_out", C.c_int * 8),
+                ("value_nlayers", C.c_int), ("value_out", C.c_int * 8), ("max_unroll", C.c_int), ("max_minibatch", C.c_int),
+                ("learning_rate", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("adam_eps", C.c_double),
+                ("discounting", C.c_float), ("gae_lambda", C.c_float), ("clipping_epsilon", C.c_float), ("entropy_cost", C.c_float),
+                ("reward_scaling", C.c_float), ("normalize_advantage", C.c_int)]
+
+
+# Every function of the five public headers: name -> (restype, argtypes), applied once by lib().  tests/test_capi_host.py parses the headers'
+# prototypes and struct definitions and compares them with this table and with the mirrors above.  Handles (myo_model*, myo_batch*,
+# myo_policy*, myo_ppo_learner*), streams and device pointers travel as c_void_p.
+_V, _I, _U64, _SZ, _STR = C.c_void_p, C.c_int, C.c_uint64, C.c_size_t, C.c_char_p
+_pV, _pI, _pF, _pD, _ppF = C.POINTER(_V), C.POINTER(_I), C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.POINTER(C.c_float))
+_BUF = [_pV, C.POINTER(_SZ), C.POINTER(_SZ)]       # the (device pointer, pitch, width) out-arguments of a buffer lookup
+SIGNATURES = {
+    # include/myo_hip.h
+    "myo_last_error": (_STR, []),
+    "myo_version": (_I, []),
+    "myo_model_load": (_I, [_STR, _SZ, _I, _pV]),
+    "myo_model_free": (None, [_V]),
+    "myo_model_dims": (_I, [_V, C.POINTER(Dims)]),
+    "myo_model_set_switch": (_I, [_V, _I, _I, _I]),
+    "myo_batch_create": (_I, [_V, _I, _pV]),
+    "myo_batch_free": (None, [_V]),
+    "myo_batch_size": (_I, [_V]),
+    "myo_batch_configure": (_I, [_V, C.POINTER(TaskConfig)]),
+    "myo_batch_configure_walk": (_I, [_V, C.POINTER(WalkConfig)]),
+    "myo_batch_configure_track": (_I, [_V, C.POINTER(TrackConfig)]),
+    "myo_batch_set_condition": (_I, [_V, _I, _I, _I]),
+    "myo_batch_set_fatigue_reset": (_I, [_V, _I, _V]),
+    "myo_batch_set_geom_override": (_I, [_V, _I, _pF, _pF]),
+    "myo_batch_field": (_I, [_V, _I, *_BUF]),
+    "myo_batch_read": (_I, [_V, _I, _V, _SZ]),
+    "myo_batch_write": (_I, [_V, _I, _V, _SZ]),
+    "myo_reset": (_I, [_V, _V, _U64, _V]),
+    "myo_set_state": (_I, [_V, _V, _V, _V, _V, _V]),
+    "myo_step": (_I, [_V, _V, _I, _I, _V]),
+    "myo_obs": (_I, [_V, _V]),
+    "myo_obs_only": (_I, [_V, _V]),
+    "myo_obs_reset_only": (_I, [_V, _V]),
+    "myo_autoreset": (_I, [_V, _I, _U64, _V]),
+    "myo_set_env_offset": (_I, [_V, _I]),
+    "myo_status": (_I, [_V, _V]),
+    "myo_random_action": (_I, [_V, _V, _U64, _U64, _I, _V]),
+    "myo_sync": (_I, [_V]),
+    "myo_set_balance": (_I, [_V, _I]),
+    "myo_set_lanes": (_I, [_I]),
+    "myo_read_stamps": (_I, [_V, _V, _I]),
+    "myo_bench_rollout": (_I, [_V, _I, _I, _U64, _I, _I, _V, _pF]),
+    "myo_bench_last_kernel_ms": (_I, [_V, _pF]),
+    "myo_probe_valu": (_I, [_I, _I, _I, _pD, _pI]),
+    "myo_bench_last_kernel_name": (_STR, [_V]),
+    "myo_policy_load": (_I, [_I, _I, _I, _I, _pI, _V, _V, _pV, _pV, _pV]),
+    "myo_policy_free": (None, [_V]),
+    "myo_policy_act": (_I, [_V, _V, _I, _V, _I, _U64, _U64, _I, _V]),
+    # include/myo_hip_sensors.h
+    "myo_model_nsensor": (_I, [_V]),
+    "myo_batch_enable_sensors": (_I, [_V]),
+    # include/myo_hip_rewards.h
+    "myo_batch_rwd_ncol": (_I, [_V]),
+    "myo_batch_rwd_name": (_STR, [_V, _I]),
+    "myo_batch_enable_rewards": (_I, [_V, _pF, _I, _I]),
+    "myo_batch_rwd_row": (_I, [_V, *_BUF]),
+    "myo_batch_rwd_read": (_I, [_V, _V, _SZ]),
+    "myo_batch_enable_episode_stats": (_I, [_V]),
+    "myo_batch_episode_buffer": (_I, [_V, _I, *_BUF]),
+    "myo_batch_episode_read": (_I, [_V, _I, _V, _SZ]),
+    "myo_episode_update": (_I, [_V, _I, _V]),
+    "myo_episode_clear": (_I, [_V, _V]),
+    # include/myo_hip_forward.h
+    "myo_model_forward_dims": (_I, [_V, _pI, _pI, _pI, _pI]),
+    "myo_forward": (_I, [_V, _V]),
+    "myo_forward_buffer": (_I, [_V, _I, *_BUF]),
+    "myo_forward_read": (_I, [_V, _I, _V, _SZ]),
+    "myo_forward_host_tables": (_I, [_STR, _SZ, _I, _V, _SZ, _pI]),
+    # include/myo_hip_ppo.h
+    "myo_policy_update": (_I, [_V, _V, _V, _pV, _pV, _I, _V]),
+    "myo_policy_sample": (_I, [_V, _V, _I, _V, _V, _V, _U64, _U64, _I, _V]),
+    "myo_ppo_gae": (_I, [_V, _V, _V, _V, _V, _I, _I, C.c_float, C.c_float, _V, _V, _V]),
+    "myo_ppo_learner_create": (_I, [_I, C.POINTER(LearnerConfig), _ppF, _ppF, _ppF, _ppF, _pV]),
+    "myo_ppo_learner_free": (None, [_V]),
+    "myo_ppo_learner_step": (_I, [_V, _V, _V, _V, _V, _V, _V, _I, _I, _V, _I, _V, _V, _V, _V, _V]),
+    "myo_ppo_learner_tensor": (_I, [_V, _I, _I, _I, _I, _pV, C.POINTER(_SZ)]),
+}
+
+
 # -mllvm -disable-machine-licm: the post-ISel loop-invariant code motion hoists constant materialisations (polynomial coefficients, masks) out
 # of the 10-substep loop into the kernel prologue, where a dozen of them stay live in VGPRs for the whole kernel and push other values into
 # scratch memory; with the pass off the headline kernel needs no register spill at all (35 before; tests/test_kernel_resources.py)
@@ -162,60 +249,9 @@ def lib():
             except ImportError:
                 pass
         L = C.CDLL(LIB_PATH)
-        L.myo_last_error.restype = C.c_char_p
-        L.myo_model_load.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]
-        L.myo_model_free.argtypes = [C.c_void_p]
-        L.myo_model_dims.argtypes = [C.c_void_p, C.POINTER(Dims)]
-        L.myo_model_set_switch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-        L.myo_batch_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
-        L.myo_batch_free.argtypes = [C.c_void_p]
-        L.myo_batch_size.argtypes = [C.c_void_p]
-        L.myo_batch_configure.argtypes = [C.c_void_p, C.POINTER(TaskConfig)]
-        L.myo_batch_field.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-        L.myo_batch_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
-        L.myo_batch_write.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
-        L.myo_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
-        L.myo_set_state.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_void_p]
-        L.myo_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        L.myo_obs.argtypes = [C.c_void_p, C.c_void_p]
-        L.myo_status.argtypes = [C.c_void_p, C.c_void_p]
-        L.myo_random_action.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
-        L.myo_sync.argtypes = [C.c_void_p]
-        L.myo_bench_rollout.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
-        L.myo_bench_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-        L.myo_batch_set_geom_override.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-        L.myo_probe_valu.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]
-        L.myo_bench_last_kernel_name.argtypes = [C.c_void_p]
-        L.myo_bench_last_kernel_name.restype = C.c_char_p
-        L.myo_obs_only.argtypes = [C.c_void_p, C.c_void_p]
-        L.myo_autoreset.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]
-        L.myo_set_env_offset.argtypes = [C.c_void_p, C.c_int]
-        L.myo_set_lanes.argtypes = [C.c_int]
-        L.myo_set_balance.argtypes = [C.c_void_p, C.c_int]
-        L.myo_read_stamps.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.myo_batch_configure_walk.argtypes = [C.c_void_p, C.POINTER(WalkConfig)]
-        L.myo_batch_configure_track.argtypes = [C.c_void_p, C.POINTER(TrackConfig)]
-        L.myo_obs_reset_only.argtypes = [C.c_void_p, C.c_void_p]
-        L.myo_batch_set_condition.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-        L.myo_batch_set_fatigue_reset.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.myo_batch_enable_sensors.argtypes = [C.c_void_p]
-        L.myo_model_nsensor.argtypes = [C.c_void_p]
-        L.myo_batch_rwd_ncol.argtypes = [C.c_void_p]
-        L.myo_batch_rwd_name.argtypes = [C.c_void_p, C.c_int]
-        L.myo_batch_rwd_name.restype = C.c_char_p
-        L.myo_batch_enable_rewards.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int]
-        L.myo_batch_rwd_row.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-        L.myo_batch_rwd_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        L.myo_batch_enable_episode_stats.argtypes = [C.c_void_p]
-        L.myo_batch_episode_buffer.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-        L.myo_batch_episode_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
-        L.myo_episode_update.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.myo_episode_clear.argtypes = [C.c_void_p, C.c_void_p]
-        L.myo_forward.argtypes = [C.c_void_p, C.c_void_p]
-        L.myo_forward_buffer.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-        L.myo_forward_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
-        L.myo_model_forward_dims.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
-        L.myo_forward_host_tables.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 

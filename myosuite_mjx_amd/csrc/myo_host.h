@@ -1,5 +1,5 @@
-// myo_host.h -- host-side records shared by myo_hip.hip, the model loader and the task headers: error reporting, myo_model, myo_batch, and
-// the per-task hook record with its two generic launchers.
+// myo_host.h -- what every host file shares: error reporting, the helpers each subsystem would otherwise write out again (device-memory
+// pool, device selection, blob view, kernel attributes), myo_model, myo_batch, and the per-task hook record with its two generic launchers.
 #ifndef MYO_HOST_H
 #define MYO_HOST_H
 
@@ -9,6 +9,95 @@ static int g_lanes = 64;  // lanes per env (16 / 32 / 64); MYO_LANES env var or 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(MYO_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
+
+// The device memory of one host object (model, batch, policy, learner): allocations live as long as the object and are freed with it, so a
+// half-built object held in a unique_ptr frees what it had allocated on any failure path.  Sizes are in bytes; alloc zero-fills
+struct DevPool {
+  std::vector<void*> ptrs;
+  DevPool() = default;
+  DevPool(const DevPool&) = delete;
+  DevPool& operator=(const DevPool&) = delete;
+  ~DevPool() { for (void* p : ptrs) (void)hipFree(p); }
+  template <class T> int alloc(T** out, size_t nbytes, bool zero = true) {
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, nbytes);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? MYO_E_NOMEM : MYO_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+    ptrs.push_back(p);
+    if (zero) HIPCHK(hipMemset(p, 0, nbytes));
+    *out = (T*)p;
+    return MYO_OK;
+  }
+  // n elements of src followed by `pad` zero elements (at least 8 bytes, so an empty table still has an address).  (out is a template so
+  // that the device-side address-space types of the struct fields do not matter to this host code)
+  template <class T, class P> int upload(P* out, const T* src, size_t n, size_t pad = 0) {
+    T* p = nullptr;
+    const int rc = alloc(&p, std::max<size_t>((n + pad) * sizeof(T), 8));
+    if (rc) return rc;
+    if (n) HIPCHK(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
+    *out = (P)(const T*)p;
+    return MYO_OK;
+  }
+};
+
+// `device` is an ordinal of this machine: make it the calling thread's current device
+static int use_device(int device, const char* who, const char* note = "") {
+  int ndev = 0;
+  HIPCHK(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return fail(MYO_E_HIP, std::string(who) + ": no such HIP device" + note);
+  HIPCHK(hipSetDevice(device));
+  return MYO_OK;
+}
+
+struct BlobRec { char name[32]; uint32_t dtype, ndim, shape[4]; uint64_t nbytes, offset; };
+
+// Read-only view of a MYOB v3 blob.  ints / floats / doubles return host vectors and allocate nothing on the device.  A missing or mistyped
+// array comes back empty and leaves the first such error in rc (MYO_E_BLOB, the array's name in the message): read, then check rc, then use
+struct Blob {
+  const uint8_t* p;
+  mutable int rc = MYO_OK;
+  const BlobRec* find(const char* name) const {
+    uint32_t n;
+    memcpy(&n, p + 8, 4);
+    for (uint32_t i = 0; i < n; i++) {
+      const BlobRec* r = (const BlobRec*)(p + 16 + (size_t)i * sizeof(BlobRec));
+      if (!strncmp(r->name, name, 32)) return r;
+    }
+    return nullptr;
+  }
+  bool has(const char* name) const { return find(name) != nullptr; }
+  template <class Src, class Dst> std::vector<Dst> read(const char* name, uint32_t dtype) const {
+    const BlobRec* r = find(name);
+    if (!r || r->dtype != dtype) {
+      if (!rc) rc = fail(MYO_E_BLOB, std::string("model blob lacks ") + (dtype ? "i32" : "f64") + " array " + name);
+      return {};
+    }
+    const Src* s = (const Src*)(p + r->offset);
+    return std::vector<Dst>(s, s + r->nbytes / sizeof(Src));
+  }
+  std::vector<int> ints(const char* name) const { return read<int, int>(name, 1); }
+  std::vector<float> floats(const char* name) const { return read<double, float>(name, 0); }   // f64 narrowed to float
+  std::vector<double> doubles(const char* name) const { return read<double, double>(name, 0); }
+};
+// the view of a caller's blob, after the magic and version check
+static int blob_open(const void* blobv, size_t nbytes, const char* who, Blob* B) {
+  uint32_t ver = 0;
+  if (nbytes >= 16) memcpy(&ver, (const uint8_t*)blobv + 4, 4);
+  if (nbytes < 16 || memcmp(blobv, "MYOB", 4) || ver != 3) return fail(MYO_E_BLOB, std::string(who) + ": not a MYOB v3 blob");
+  B->p = (const uint8_t*)blobv;
+  return MYO_OK;
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize for every kernel of a list, once per device: kernel attributes are per device, so each list
+// keeps one flag per device ordinal (a process that opens models on two GPUs).  A list holds records with the kernel in `fn`
+struct OncePerDevice { std::mutex mu; bool done[64] = {}; };
+template <class Kernels> static int set_lds_limit(OncePerDevice& once, const Kernels& kernels, int nbytes, int device) {
+  std::lock_guard<std::mutex> lock(once.mu);
+  bool& done = once.done[device & 63];
+  if (done) return MYO_OK;
+  for (const auto& k : kernels) HIPCHK(hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, nbytes));
+  done = true;
+  return MYO_OK;
+}
 
 struct myo_model {
   int device = 0;
@@ -28,7 +117,7 @@ struct myo_model {
   int has_tl = 0;
   bool has_affine = false;   // some actuator is a stateless affine one (motor / position / velocity): wave kernel only
   myo_dims dims{};
-  std::vector<void*> dev_allocs;
+  DevPool pool;
   std::vector<float> qpos0, jnt_lo, jnt_hi;
   std::vector<int> dof_type, dof_link, link_parent, link_dofnum, site_link;   // host copies of the uploaded tables the task checks read
   std::vector<int> cg_geom, cg_type_h;   // collision geom -> compiled geom id, and its type (host copies)
@@ -64,7 +153,7 @@ struct myo_batch {
   DevBatch db{};
   TaskDev task{};
   int ntarget_alloc = 0, obs_alloc = 0, env_offset = 0;
-  std::vector<void*> dev_allocs;
+  DevPool pool;
   float *d_tlo = nullptr, *d_thi = nullptr, *d_init = nullptr, *d_jlo = nullptr, *d_jhi = nullptr, *d_action = nullptr, *d_rnd = nullptr;
   float* d_initv = nullptr;
   float *d_init2 = nullptr, *d_initv2 = nullptr, *d_fatvec = nullptr;   // walk reset "random": second keyframe; fatigue reset vector
@@ -87,28 +176,37 @@ struct myo_batch {
   bool bp_on = false;            // per-env root-body offset started (DevBatch.bpos / bpos_range allocated)
   int bq_body = -1;              // body of MYO_F_BODYQUAT (myo_task_config.quat_body; -1: none selected)
   bool sens_on = false;          // touch sensors / contact forces enabled (DevBatch.sens / cfrc allocated)
-  myo_episode episode;           // episode statistics (device buffers in dev_allocs)
+  myo_episode episode;           // episode statistics (device buffers in pool)
   bool bq_on = false;            // per-env body orientation started (DevBatch.bquat / bquat_range / bq_c / bq_flag allocated)
   bool fwd_on = false;           // forward buffers allocated (the first myo_forward)
   void* fwd_buf[16] = {};        // ... one per MYO_FWD_* id
   std::vector<hipEvent_t> kev;   // per-launch event pairs around the step kernel (bench only)
   int kev_pending = 0;           // pairs recorded by asynchronous bench calls and not collected yet
   float last_kernel_ms = 0.f;
+  ~myo_batch() {
+    for (hipEvent_t e : kev) (void)hipEventDestroy(e);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+  }
 };
 
-// What differs per task on the host, indexed by task id (task_hooks in myo_hip.hip); a task's record lives next to its kernel.
+// What differs per task on the host, indexed by task id (task_hooks in myo_host_tasks.h); a task's record lives next to its kernel.
 struct TaskHooks {
-  int (*configure)(myo_batch*, const myo_task_config*);                    // argument and model checks, obs_dim, task-specific TaskDev fields; null: no observation row
+  int (*configure)(myo_batch*, const myo_task_config*);                    // argument and model checks, obs_dim, task-specific TaskDev fields; null: no observation row,
+                                                                           // or a task with a config record of its own (walk_configure, track_configure)
   int (*obs)(myo_batch*, hipStream_t, int obs_only, int reset_only);       // observation launch; null: the task has none
   int (*post)(myo_batch*, hipStream_t, uint64_t seed, int auto_max);       // myo_bench_rollout's fused epilogue; null: observation, auto-reset and re-observation are three launches
 };
+// the step launch (myo_host_step.h): the walk task observes through it
+static int launch_step(myo_batch* b, const float* action, int actmap, int nsub, hipStream_t s, int kflags = 0);
+
 template <class Task> static int launch_task_obs(myo_batch* b, hipStream_t s, int obs_only, int reset_only) {
   hipLaunchKernelGGL(task_obs_kernel<Task>, dim3(b->db.B), dim3(64), 0, s, b->model->dm, b->db, b->task, (const DevTrack*)b->d_track, b->reset_seed, obs_only, reset_only);
   return MYO_OK;
 }
 // the device copy of (db, task) that task_post_kernel's reset reads: uploaded on the launch's stream whenever either record has changed
 static int sync_reset_args(myo_batch* b, hipStream_t s) {
-  if (!b->d_reset) { HIPCHK(hipMalloc((void**)&b->d_reset, sizeof(ResetArgs))); b->dev_allocs.push_back(b->d_reset); }
+  if (!b->d_reset) { const int rc = b->pool.alloc(&b->d_reset, sizeof(ResetArgs), false); if (rc) return rc; }   // (not filled: the copy below writes all of it, on s)
   else if (!memcmp(&b->reset_args.Bt, &b->db, sizeof(DevBatch)) && !memcmp(&b->reset_args.T, &b->task, sizeof(TaskDev))) return MYO_OK;
   memcpy(&b->reset_args.Bt, &b->db, sizeof(DevBatch)); memcpy(&b->reset_args.T, &b->task, sizeof(TaskDev));
   HIPCHK(hipMemcpyAsync(b->d_reset, &b->reset_args, sizeof(ResetArgs), hipMemcpyHostToDevice, s));

@@ -4,25 +4,9 @@
 #ifndef MYO_HOST_BATCH_H
 #define MYO_HOST_BATCH_H
 
-static int balloc(myo_batch* b, void** p, size_t nbytes) {
-  HIPCHK(hipMalloc(p, nbytes));
-  HIPCHK(hipMemset(*p, 0, nbytes));
-  b->dev_allocs.push_back(*p);
-  return 0;
-}
-
-static void batch_free(myo_batch* b) {
-  if (!b) return;
-  for (hipEvent_t e : b->kev) (void)hipEventDestroy(e);
-  for (void* p : b->dev_allocs) (void)hipFree(p);
-  if (b->ev0) (void)hipEventDestroy(b->ev0);
-  if (b->ev1) (void)hipEventDestroy(b->ev1);
-  delete b;
-}
-
 static int batch_create(const myo_model* m, int B, myo_batch** out) {
   HIPCHK(hipSetDevice(m->device));
-  std::unique_ptr<myo_batch, void (*)(myo_batch*)> owner(new myo_batch(), batch_free);   // a failed create frees what it had allocated
+  std::unique_ptr<myo_batch> owner(new myo_batch());   // a failed create frees what it had allocated
   myo_batch* b = owner.get();   // (value-initialised: every pointer, flag and size not set below is null / 0)
   DevBatch& d = b->db;
   int nv = m->dm.nv, nu = m->dm.nu, nq = m->nq, rc;
@@ -33,7 +17,7 @@ static int batch_create(const myo_model* m, int B, myo_batch** out) {
     d.ovf_row = 8 + nj * kc + (kc + 3) / 4 + (m->trk ? TRK_STATE : 0);
     d.ovf_rows = m->trk ? NCX2 : NCX;
   }
-#define BA(ptr, n) if ((rc = balloc(b, (void**)&ptr, (size_t)(n) * 4))) return rc;
+#define BA(ptr, n) if ((rc = b->pool.alloc(&ptr, (size_t)(n) * 4))) return rc;
   BA(d.qpos, (size_t)B * nq) BA(d.qvel, (size_t)B * nv) BA(d.act, (size_t)B * nu) BA(d.ctrl, (size_t)B * nu) BA(d.warm, (size_t)B * nv)
   BA(d.time, B) BA(d.target, (size_t)B * b->ntarget_alloc) BA(d.obs, (size_t)B * b->obs_alloc) BA(d.reward, B) BA(d.done, B)
   BA(d.solved, B) BA(d.qacc, (size_t)B * nv) BA(d.tenlen, (size_t)B * nu) BA(d.actforce, (size_t)B * nu) BA(d.sitexpos, (size_t)B * 24)
@@ -116,8 +100,8 @@ static int bm_start(myo_batch* b) {
   DevBatch& d = b->db;
   const int nb = (int)m->body_mass0.size();
   float *bm = nullptr, *br = nullptr, *lc = nullptr; int rc;
-  if ((rc = balloc(b, (void**)&bm, (size_t)d.B * nb * 4)) || (rc = balloc(b, (void**)&br, (size_t)d.B * 2 * nb * 4)) ||
-      (rc = balloc(b, (void**)&lc, (size_t)d.B * m->dm.nl * 10 * 4))) return rc;
+  if ((rc = b->pool.alloc(&bm, (size_t)d.B * nb * 4)) || (rc = b->pool.alloc(&br, (size_t)d.B * 2 * nb * 4)) ||
+      (rc = b->pool.alloc(&lc, (size_t)d.B * m->dm.nl * 10 * 4))) return rc;
   std::vector<float> v((size_t)d.B * nb);
   bm_default(b, MYO_F_BODYMASS, v.data(), d.B, nb);
   HIPCHK(hipSetDevice(m->device));
@@ -151,7 +135,7 @@ static int bp_start(myo_batch* b) {
   DevBatch& d = b->db;
   float *bp = nullptr, *br = nullptr; int rc;
   HIPCHK(hipSetDevice(b->model->device));
-  if ((rc = balloc(b, (void**)&bp, (size_t)d.B * 3 * 4)) || (rc = balloc(b, (void**)&br, (size_t)d.B * 6 * 4))) return rc;   // zero: no offset
+  if ((rc = b->pool.alloc(&bp, (size_t)d.B * 3 * 4)) || (rc = b->pool.alloc(&br, (size_t)d.B * 6 * 4))) return rc;   // zero: no offset
   d.bpos = bp; d.bpos_range = br; d.bpos_link = b->model->bp_link;
   return MYO_OK;
 }
@@ -205,8 +189,8 @@ static int bq_start(myo_batch* b) {
   float *bq = nullptr, *br = nullptr, *bc = nullptr;
   int *bf = nullptr, rc;
   HIPCHK(hipSetDevice(m->device));
-  if ((rc = balloc(b, (void**)&bq, (size_t)d.B * 4 * 4)) || (rc = balloc(b, (void**)&br, (size_t)d.B * 6 * 4)) ||
-      (rc = balloc(b, (void**)&bc, 12 * 4)) || (rc = balloc(b, (void**)&bf, fl.size() * 4))) return rc;
+  if ((rc = b->pool.alloc(&bq, (size_t)d.B * 4 * 4)) || (rc = b->pool.alloc(&br, (size_t)d.B * 6 * 4)) ||
+      (rc = b->pool.alloc(&bc, 12 * 4)) || (rc = b->pool.alloc(&bf, fl.size() * 4))) return rc;
   HIPCHK(hipMemcpy(bq, q.data(), q.size() * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(bc, c.data(), c.size() * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(bf, fl.data(), fl.size() * 4, hipMemcpyHostToDevice));
@@ -243,7 +227,7 @@ static int enable_sensors(myo_batch* b) {
   DevBatch& d = b->db; const int n = b->model->dw.ntouch;
   float *sd = nullptr, *cf = nullptr;
   HIPCHK(hipSetDevice(b->model->device));
-  if ((rc = balloc(b, (void**)&sd, (size_t)d.B * n * 4)) || (rc = balloc(b, (void**)&cf, (size_t)d.B * 3 * (n + 1) * 4))) return rc;
+  if ((rc = b->pool.alloc(&sd, (size_t)d.B * n * 4)) || (rc = b->pool.alloc(&cf, (size_t)d.B * 3 * (n + 1) * 4))) return rc;
   d.sens = sd; d.cfrc = cf; d.ntouch = n; b->sens_on = true;
   return MYO_OK;
 }

@@ -1,50 +1,10 @@
-// myo_host_model.h -- the pieces of myo_model_load: blob view, upload of the lowered tables, packing of the per-lane records (host only),
+// myo_host_model.h -- the pieces of myo_model_load over the blob view of myo_host.h: upload of the lowered tables, packing of the per-lane records (host only),
 // choice of the kernel class (host only), member tables of the per-env overrides.
 #ifndef MYO_HOST_MODEL_H
 #define MYO_HOST_MODEL_H
 
-struct BlobRec { char name[32]; uint32_t dtype, ndim, shape[4]; uint64_t nbytes, offset; };
-
-// Read-only view of a MYOB v3 blob.  ints / floats / doubles return host vectors and allocate nothing on the device.  A missing or mistyped
-// array comes back empty and leaves the first such error in rc (MYO_E_BLOB, the array's name in the message): read, then check rc, then use
-struct Blob {
-  const uint8_t* p;
-  mutable int rc = MYO_OK;
-  const BlobRec* find(const char* name) const {
-    uint32_t n;
-    memcpy(&n, p + 8, 4);
-    for (uint32_t i = 0; i < n; i++) {
-      const BlobRec* r = (const BlobRec*)(p + 16 + (size_t)i * sizeof(BlobRec));
-      if (!strncmp(r->name, name, 32)) return r;
-    }
-    return nullptr;
-  }
-  bool has(const char* name) const { return find(name) != nullptr; }
-  template <class Src, class Dst> std::vector<Dst> read(const char* name, uint32_t dtype) const {
-    const BlobRec* r = find(name);
-    if (!r || r->dtype != dtype) {
-      if (!rc) rc = fail(MYO_E_BLOB, std::string("model blob lacks ") + (dtype ? "i32" : "f64") + " array " + name);
-      return {};
-    }
-    const Src* s = (const Src*)(p + r->offset);
-    return std::vector<Dst>(s, s + r->nbytes / sizeof(Src));
-  }
-  std::vector<int> ints(const char* name) const { return read<int, int>(name, 1); }
-  std::vector<float> floats(const char* name) const { return read<double, float>(name, 0); }   // f64 narrowed to float
-  std::vector<double> doubles(const char* name) const { return read<double, double>(name, 0); }
-};
-
-// (out is a template so that the struct fields' device-side address-space types do not matter to this host code)
-template <typename T, class P> static int upload(myo_model* m, const std::vector<T>& v, P* out) {
-  void* p = nullptr;
-  size_t nb = (v.size() + 4) * sizeof(T);
-  HIPCHK(hipMalloc(&p, nb));
-  m->dev_allocs.push_back(p);
-  HIPCHK(hipMemset(p, 0, nb));
-  if (!v.empty()) HIPCHK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  *out = (P)(const T*)p;
-  return 0;
-}
+// a table into the model's pool, four zero elements behind it
+template <typename T, class P> static int upload(myo_model* m, const std::vector<T>& v, P* out) { return m->pool.upload(out, v.data(), v.size(), 4); }
 // the tables the kernels read: blob array -> device (and, with keep, a host copy)
 template <class P> static int load_f(myo_model* m, const Blob& B, const char* name, P* out, std::vector<float>* keep = nullptr) {
   const std::vector<float> v = B.floats(name);
@@ -462,12 +422,7 @@ static int load_model(myo_model* m, const Blob& B) {
   if (B.has("integrator")) { const std::vector<int> ig = B.ints("integrator"); if (B.rc) return B.rc; m->rk4 = !ig.empty() && ig[0] == 1; }
   if ((rc = classify(m, pair_i, dpar))) return rc;
   if ((rc = load_touch_tables(m, B))) return rc;
-  void* p1 = nullptr; void* p2 = nullptr;
-  if (hipMalloc(&p1, sizeof(DevModel)) == hipSuccess) m->dev_allocs.push_back(p1);
-  if (hipMalloc(&p2, sizeof(DevModelW)) == hipSuccess) m->dev_allocs.push_back(p2);
-  if (!p1 || !p2) return fail(MYO_E_NOMEM, "hipMalloc model structs");
-  m->d_dm = (DevModel*)p1; m->d_dw = (DevModelW*)p2;
-  if (hipMemcpy(p1, &d, sizeof(DevModel), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(p2, &w, sizeof(DevModelW), hipMemcpyHostToDevice) != hipSuccess) return fail(MYO_E_HIP, "upload model structs");
+  if ((rc = m->pool.upload(&m->d_dm, &d, 1)) || (rc = m->pool.upload(&m->d_dw, &w, 1))) return rc;
   m->dims.na = d.na_obs;
   m->dims.env_lds_bytes = m->wave_ok ? m->env_lds_bytes_w : m->env_lds_bytes;
   m->dims.ncon_max = m->wave_ok ? (m->wave_cfg >= 1 ? 32 : NCONW) : NCON;

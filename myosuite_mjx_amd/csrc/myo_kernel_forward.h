@@ -286,7 +286,7 @@ static int fwd_start(myo_batch* b) {
   if (b->fwd_on) return MYO_OK;
   HIPCHK(hipSetDevice(b->model->device));
   for (int w = 0; w < MYO_FWD_COUNT; w++) {
-    int rc = balloc(b, &b->fwd_buf[w], std::max<size_t>((size_t)b->db.B * fwd_width(b->model, w), 1) * 4);
+    int rc = b->pool.alloc(&b->fwd_buf[w], std::max<size_t>((size_t)b->db.B * fwd_width(b->model, w), 1) * 4);
     if (rc) return rc;
   }
   b->fwd_on = true;

@@ -1,6 +1,6 @@
 // myo_rewards.h -- reward-term rows and episode statistics (include/myo_hip_rewards.h): the column table per task, the walk task's term
 // kernel, the episode-statistics kernel and the host entry points.  The other tasks write their rows in their own observation kernels
-// (rwd_row, myo_common.h).  Included by myo_hip.hip after myo_host_batch.h.
+// (rwd_row, myo_common.h).  Included by myo_hip.hip after myo_host.h, before the task files (their configure reads rwd_cols).
 #ifndef MYO_REWARDS_H
 #define MYO_REWARDS_H
 
@@ -92,7 +92,7 @@ static int rewards_enable(myo_batch* b, const float* w, int nw, int mode) {
   int rc;
   if (!d.rwd) {
     float *row = nullptr, *wd = nullptr;
-    if ((rc = balloc(b, (void**)&row, (size_t)d.B * c.n * 4)) || (rc = balloc(b, (void**)&wd, (size_t)nw * 4))) return rc;
+    if ((rc = b->pool.alloc(&row, (size_t)d.B * c.n * 4)) || (rc = b->pool.alloc(&wd, (size_t)nw * 4))) return rc;
     d.rwd = row; d.rwd_w = wd; d.rwd_n = c.n;
   }
   HIPCHK(hipDeviceSynchronize());
@@ -115,8 +115,8 @@ static int episode_enable(myo_batch* b) {
   const size_t B = b->db.B;
   int rc;
   HIPCHK(hipSetDevice(b->model->device));
-  if ((rc = balloc(b, (void**)&ep.run, B * 16)) || (rc = balloc(b, (void**)&ep.last, B * 16)) ||
-      (rc = balloc(b, (void**)&ep.finished, (B + 3) / 4 * 4)) || (rc = balloc(b, (void**)&ep.count, B * 4))) return rc;
+  if ((rc = b->pool.alloc(&ep.run, B * 16)) || (rc = b->pool.alloc(&ep.last, B * 16)) ||
+      (rc = b->pool.alloc(&ep.finished, (B + 3) / 4 * 4)) || (rc = b->pool.alloc(&ep.count, B * 4))) return rc;
   b->episode = ep;
   return MYO_OK;
 }

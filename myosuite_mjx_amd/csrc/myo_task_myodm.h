@@ -81,8 +81,68 @@ __device__ __forceinline__ void mjx_track_obs_body(const DevModel& M, const DevB
 }
 using MjxTrackTask = StateObs<mjx_track_obs_body>;
 
-// MYO_TASK_TRACK (configured by myo_batch_configure_track: no configure hook).  The classic flavour observes with MyodmTask, keyed by the seed of the
-// last reset, and has a fused epilogue; the MJX flavour observes the state-only row and myo_bench_rollout skips its epilogue (the step kernel's own)
+// MYO_TASK_TRACK of either flavour: the configure of myo_batch_configure_track (a config record of its own: no configure hook).  The
+// reference tables and the per-env reference rows go into the batch's pool; every call uploads its tables anew
+static int track_configure(myo_batch* b, const myo_track_config* c) {
+  const myo_model* m = b->model;
+  if (!(m->wave_ok && m->trk)) return fail(MYO_E_UNSUPPORTED, "track task: models of the TrackEnv class only (condim-4 / friction-loss / hull geoms)");
+  const int nq = m->nq, nv = m->dm.nv, nu = m->dm.nu;
+  if (c->n_frames <= 0 || c->ref_type < 0 || c->ref_type > 2 || c->horizon < 1 || c->robot_dim < 0 || c->object_dim < 0 || c->robot_dim > 64 ||
+      c->robot_dim + c->object_dim > 64 || c->robot_dim > nq || !c->ref_time || !c->init_qpos || !c->ctrl_lo || !c->ctrl_hi)
+    return fail(MYO_E_ARG, "myo_batch_configure_track: bad reference / pose arguments");
+  if ((c->robot_dim > 0 && (!c->ref_robot || c->robot_horizon < 1)) || (c->object_dim > 0 && (!c->ref_object || c->object_horizon < 1)))
+    return fail(MYO_E_ARG, "myo_batch_configure_track: reference rows missing");
+  if (c->ref_type == 1 && ((c->robot_dim > 0 && c->robot_horizon < 2) || (c->object_dim > 0 && c->object_horizon < 2))) return fail(MYO_E_ARG, "RANDOM reference needs two rows");
+  if (c->object_link < 0 || c->object_link >= m->dm.nl || c->wrist_link < 0 || c->wrist_link >= m->dm.nl) return fail(MYO_E_ARG, "myo_batch_configure_track: link out of range");
+  if (c->flavour != 0 && c->flavour != 1) return fail(MYO_E_ARG, "myo_batch_configure_track: flavour must be 0 (MJX) or 1 (classic)");
+  // classic flavour (envs/myo/myodm/myodm_v0.py): hand_qpos_err = qpos[:-6] - robot, the object pose is 7 wide, and its own kinematics walk
+  // takes hinge / slide joints only
+  if (c->flavour == 1 && (nq != nv || c->robot_dim != nq - 6 || c->object_dim != 7))
+    return fail(MYO_E_ARG, "myo_batch_configure_track: the classic flavour needs nq == nv, robot_dim == nq - 6 and object_dim == 7");
+  const int obs_dim = c->flavour == 1 ? nq + nv + c->robot_dim + (c->ref_robot_vel ? c->robot_dim : 1) + 3 + m->dm.na_obs : nq + nv;
+  if (obs_dim > b->obs_alloc) return fail(MYO_E_ARG, "obs_dim too large");
+  HIPCHK(hipSetDevice(m->device));
+  HIPCHK(hipDeviceSynchronize());
+  const int B = b->db.B;
+  DevPool& pool = b->pool;
+  DevTrack K{};
+  K.ref_type = c->ref_type; K.horizon = c->horizon; K.robot_horizon = c->robot_horizon; K.object_horizon = c->object_horizon;
+  K.robot_dim = c->robot_dim; K.object_dim = c->object_dim; K.has_vel = c->ref_robot_vel != nullptr;
+  K.extrapolate = c->motion_extrapolation; K.linear = c->interpolation_linear; K.autoreset = c->autoreset;
+  K.term_obj = c->terminate_obj_fail; K.term_pose = c->terminate_pose_fail; K.start_time = c->motion_start_time; K.max_steps = c->max_episode_steps;
+  const size_t nrobot = (size_t)c->robot_horizon * c->robot_dim;
+  int rc;
+  if ((rc = pool.upload(&K.T, c->ref_time, (size_t)c->horizon)) || (rc = pool.upload(&K.robot, c->ref_robot, nrobot)) ||
+      (K.has_vel && (rc = pool.upload(&K.robot_vel, c->ref_robot_vel, nrobot))) ||
+      (rc = pool.upload(&K.object, c->ref_object, (size_t)c->object_horizon * c->object_dim)) || (rc = pool.upload(&K.init_qpos, c->init_qpos, (size_t)nq)) ||
+      (rc = pool.upload(&K.lo, c->ctrl_lo, (size_t)nu)) || (rc = pool.upload(&K.hi, c->ctrl_hi, (size_t)nu))) return rc;
+  K.obj_link = c->object_link; K.wrist_link = c->wrist_link;
+  for (int k = 0; k < 3; k++) { K.obj_p[k] = c->object_ipos[k]; K.wrist_p[k] = c->wrist_ipos[k]; }
+  for (int k = 0; k < 9; k++) K.obj_R[k] = c->object_imat[k];
+  K.lift_z = c->lift_z; K.obj_err_scale = c->obj_err_scale; K.base_err_scale = c->base_err_scale; K.lift_bonus_mag = c->lift_bonus_mag;
+  K.qpos_w = c->qpos_reward_weight; K.qpos_err_scale = c->qpos_err_scale; K.qvel_w = c->qvel_reward_weight; K.qvel_err_scale = c->qvel_err_scale;
+  K.obj_fail2 = c->obj_fail_thresh * c->obj_fail_thresh; K.base_fail2 = c->base_fail_thresh * c->base_fail_thresh; K.qpos_fail = c->qpos_fail_thresh;
+  K.w_pose = c->w_pose; K.w_object = c->w_object; K.w_bonus = c->w_bonus; K.w_penalty = c->w_penalty;
+  K.ref_pitch = 2 * c->robot_dim + c->object_dim;
+  K.seed = c->seed;
+  if ((rc = pool.alloc(&K.ref, (size_t)B * K.ref_pitch * 4)) || (!b->d_metrics && (rc = pool.alloc(&b->d_metrics, (size_t)B * 4 * 4))) ||
+      (!b->d_track && (rc = pool.alloc(&b->d_track, sizeof(DevTrack))))) return rc;
+  K.metrics = b->d_metrics;
+  HIPCHK(hipMemcpy(b->d_track, &K, sizeof(DevTrack), hipMemcpyHostToDevice));
+  b->db.track = b->d_track;
+  b->track_frames = c->n_frames;
+  b->track_flavour = c->flavour;
+  // the generic reset / observation plumbing: TrackEnv.reset puts every env at init_qpos with zero velocity, activation, control and time
+  TaskDev& T = b->task;
+  T = TaskDev{};
+  T.task = MYO_TASK_TRACK; T.frame_skip = c->n_frames; T.nq = nq; T.obs_dim = obs_dim;
+  HIPCHK(hipMemcpy(b->d_init, c->init_qpos, (size_t)nq * 4, hipMemcpyHostToDevice));
+  T.init_qpos = b->d_init; T.jnt_lo = b->d_jlo; T.jnt_hi = b->d_jhi; T.target_lo = b->d_tlo; T.target_hi = b->d_thi;
+  return MYO_OK;
+}
+
+// The classic flavour observes with MyodmTask, keyed by the seed of the last reset, and has a fused epilogue; the MJX flavour observes the
+// state-only row and myo_bench_rollout skips its epilogue (the step kernel's own)
 static int track_obs(myo_batch* b, hipStream_t s, int obs_only, int reset_only) {
   return b->track_flavour == 1 ? launch_task_obs<MyodmTask>(b, s, obs_only, reset_only) : launch_task_obs<MjxTrackTask>(b, s, obs_only, reset_only);
 }

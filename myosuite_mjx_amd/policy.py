@@ -24,13 +24,6 @@ def _f32(a):
 
 class BraxPolicy:
     def __init__(self, obs_mean, obs_std, kernels, biases, device=0):
-        L = capi.lib()
-        L.myo_policy_load.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
-                                      C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
-        L.myo_policy_free.argtypes = [C.c_void_p]
-        L.myo_policy_act.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
-        L.myo_policy_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_void_p]
-        L.myo_policy_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
         self.kernels = [_f32(k) for k in kernels]
         self.biases = [_f32(b) for b in biases]
         self.obs_mean, self.obs_std = _f32(obs_mean), _f32(obs_std)
@@ -43,8 +36,8 @@ class BraxPolicy:
         kp = (C.c_void_p * n)(*[k.ctypes.data for k in self.kernels])
         bp = (C.c_void_p * n)(*[b.ctypes.data for b in self.biases])
         self.h = C.c_void_p()
-        capi._chk(L.myo_policy_load(device, self.obs_dim, self.act_dim, n, widths, self.obs_mean.ctypes.data, self.obs_std.ctypes.data,
-                                    kp, bp, C.byref(self.h)))
+        capi._chk(capi.lib().myo_policy_load(device, self.obs_dim, self.act_dim, n, widths, self.obs_mean.ctypes.data, self.obs_std.ctypes.data,
+                                             kp, bp, C.byref(self.h)))
 
     @classmethod
     def from_npz(cls, path, device=0):

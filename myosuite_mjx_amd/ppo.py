@@ -36,12 +36,6 @@ _HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
 MAX_WIDTH, MAX_LAYERS, MAX_OBS_DIM = 512, 8, 64 * 1024 // (2 * 8 * 4)
 
 
-def _gae_lib():
-    L = capi.lib()
-    L.myo_ppo_gae.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    return L
-
-
 def _gae_torch(rewards, values, bootstrap, termination, truncation, discount, gae_lambda):
     import torch
     T = rewards.shape[0]
@@ -77,7 +71,7 @@ def compute_gae(rewards, values, bootstrap, termination, truncation, discount, g
             raise ValueError("compute_gae: all tensors must be on one device")
         vs, adv = torch.empty_like(v), torch.empty_like(v)
         with torch.cuda.device(r.device):
-            capi._chk(_gae_lib().myo_ppo_gae(*(a.data_ptr() for a in args), r.shape[0], r.shape[1], float(discount), float(gae_lambda),
+            capi._chk(capi.lib().myo_ppo_gae(*(a.data_ptr() for a in args), r.shape[0], r.shape[1], float(discount), float(gae_lambda),
                                              vs.data_ptr(), adv.data_ptr(), torch.cuda.current_stream().cuda_stream))
         return vs, adv
 
@@ -216,26 +210,6 @@ def params_dict(stats, pw, pb, vw, vb):
     return out
 
 
-class _LearnerConfig(C.Structure):
-    """myo_ppo_config of include/myo_hip_ppo.h."""
-    _fields_ = [("obs_dim", C.c_int), ("act_dim", C.c_int), ("policy_nlayers", C.c_int), ("policy_out", C.c_int * 8),
-                ("value_nlayers", C.c_int), ("value_out", C.c_int * 8), ("max_unroll", C.c_int), ("max_minibatch", C.c_int),
-                ("learning_rate", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("adam_eps", C.c_double),
-                ("discounting", C.c_float), ("gae_lambda", C.c_float), ("clipping_epsilon", C.c_float), ("entropy_cost", C.c_float),
-                ("reward_scaling", C.c_float), ("normalize_advantage", C.c_int)]
-
-
-def _learner_lib():
-    L = capi.lib()
-    pp = C.POINTER(C.POINTER(C.c_float))
-    L.myo_ppo_learner_create.argtypes = [C.c_int, C.POINTER(_LearnerConfig), pp, pp, pp, pp, C.POINTER(C.c_void_p)]
-    L.myo_ppo_learner_free.argtypes = [C.c_void_p]
-    L.myo_ppo_learner_free.restype = None
-    L.myo_ppo_learner_step.argtypes = [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5
-    L.myo_ppo_learner_tensor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-    return L
-
-
 class Learner:
     """The device learner (include/myo_hip_ppo.h): both networks' parameters, their gradients and Adam's moments live in the library, and
     `step` is one whole minibatch SGD step -- what one pass of `train`'s inner loop does with torch autograd and `torch.optim.Adam` -- as
@@ -266,18 +240,18 @@ class Learner:
                     raise ValueError(f"Learner: kernel {w.shape} / bias {b.shape} do not continue a layer input of {nin}")
                 nin = w.shape[1]
             sizes.append([w.shape[1] for w in ws])
-        cfg = _LearnerConfig(obs_dim=self.obs_dim, act_dim=self.act_dim, policy_nlayers=len(sizes[0]), value_nlayers=len(sizes[1]),
-                             max_unroll=self.max_unroll, max_minibatch=self.max_minibatch, learning_rate=learning_rate, beta1=beta1,
-                             beta2=beta2, adam_eps=adam_eps, discounting=discounting, gae_lambda=gae_lambda,
-                             clipping_epsilon=clipping_epsilon, entropy_cost=entropy_cost, reward_scaling=reward_scaling,
-                             normalize_advantage=int(bool(normalize_advantage)))
+        cfg = capi.LearnerConfig(obs_dim=self.obs_dim, act_dim=self.act_dim, policy_nlayers=len(sizes[0]), value_nlayers=len(sizes[1]),
+                                 max_unroll=self.max_unroll, max_minibatch=self.max_minibatch, learning_rate=learning_rate, beta1=beta1,
+                                 beta2=beta2, adam_eps=adam_eps, discounting=discounting, gae_lambda=gae_lambda,
+                                 clipping_epsilon=clipping_epsilon, entropy_cost=entropy_cost, reward_scaling=reward_scaling,
+                                 normalize_advantage=int(bool(normalize_advantage)))
         for k in range(min(8, len(sizes[0]))):
             cfg.policy_out[k] = sizes[0][k]
         for k in range(min(8, len(sizes[1]))):
             cfg.value_out[k] = sizes[1][k]
         arrs = [(C.POINTER(C.c_float) * len(g))(*(capi._ptr(a) for a in g)) for g in host]
         h = C.c_void_p()
-        capi._chk(_learner_lib().myo_ppo_learner_create(self.device, C.byref(cfg), *arrs, C.byref(h)))
+        capi._chk(capi.lib().myo_ppo_learner_create(self.device, C.byref(cfg), *arrs, C.byref(h)))
         self.h = h
         self.sizes = sizes
         self._views = {}
@@ -298,9 +272,9 @@ class Learner:
         mb = idx.shape[0] if mb is None else mb
         B = u_buf.shape[1] if u_buf is not None else 0
         with torch.cuda.device(self.device):
-            return _learner_lib().myo_ppo_learner_step(self.h, ptr(obs_buf), ptr(u_buf), ptr(logp_buf), ptr(rew_buf), ptr(term_buf), ptr(trunc_buf),
-                                                       int(T), int(B), ptr(idx), int(mb), ptr(mean), ptr(std), ptr(noise), ptr(loss_sums),
-                                                       torch.cuda.current_stream().cuda_stream)
+            return capi.lib().myo_ppo_learner_step(self.h, ptr(obs_buf), ptr(u_buf), ptr(logp_buf), ptr(rew_buf), ptr(term_buf), ptr(trunc_buf),
+                                                   int(T), int(B), ptr(idx), int(mb), ptr(mean), ptr(std), ptr(noise), ptr(loss_sums),
+                                                   torch.cuda.current_stream().cuda_stream)
 
     def step(self, obs_buf, u_buf, logp_buf, rew_buf, term_buf, trunc_buf, idx, mean, std, noise, loss_sums=None):
         """One SGD step on the unrolls `idx` of a rollout.  Contiguous float32 CUDA tensors: obs_buf [T + 1, B, obs_dim], u_buf [T, B,
@@ -325,7 +299,7 @@ class Learner:
         step), "m" or "v" (Adam's moments)."""
         import torch
         if which not in self._views:
-            L, out = _learner_lib(), []
+            L, out = capi.lib(), []
             for net in (0, 1):
                 nin = self.obs_dim
                 ws, bs = [], []

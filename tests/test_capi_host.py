@@ -19,14 +19,130 @@ def lib_path():
     return capi.LIB_PATH
 
 
+HEADERS = ("myo_hip.h", "myo_hip_sensors.h", "myo_hip_rewards.h", "myo_hip_ppo.h", "myo_hip_forward.h")
+
+
+def _header_text(name):
+    """A public header without its comments."""
+    hdr = open(os.path.join(ROOT, "include", name)).read()
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
+
+
 def test_library_exports_every_declared_symbol(lib_path):
-    hdr = open(os.path.join(ROOT, "include", "myo_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    names = sorted(set(re.findall(r"\b(myo_[a-z0-9_]+)\s*\(", hdr)))
-    assert len(names) >= 20
+    names = sorted({n for h in HEADERS for n in re.findall(r"\b(myo_[a-z0-9_]+)\s*\(", _header_text(h))})
+    assert len(names) >= 60 and "myo_ppo_learner_step" in names and "myo_forward" in names and "myo_episode_clear" in names
     lib = ctypes.CDLL(lib_path)
     missing = [n for n in names if not hasattr(lib, n)]
     assert not missing, missing
+
+
+# the kind of a C type as the binding has to spell it: scalar kinds by their ctypes class, every pointer as one kind
+SCALAR_KINDS = {"int": ctypes.c_int, "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+def _c_kind(decl):
+    """Kind of a C parameter or return declaration (`const float* obs_dev`, `int B`, `myo_batch*`, `void`): "pointer", "void", or the
+    ctypes class of its scalar type.  The parameter's name, if any, is dropped."""
+    decl = " ".join(decl.replace("*", " * ").split())
+    if "*" in decl:
+        return "pointer"
+    words = [w for w in decl.split() if w != "const"]
+    assert words and (words[0] in SCALAR_KINDS or words == ["void"]) and len(words) <= 2, decl
+    return "void" if words[0] == "void" else SCALAR_KINDS[words[0]]
+
+
+def _ctypes_kind(t):
+    """The same kind of a ctypes restype / argtypes entry."""
+    if t is None:
+        return "void"
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return "pointer"
+    return t
+
+
+def _header_prototypes():
+    """{name: (return kind, [argument kinds])} of every function the five public headers declare."""
+    protos = {}
+    for h in HEADERS:
+        for ret, name, args in re.findall(r"^[ \t]*((?:const\s+)?\w+[\s*]+)(myo_[a-z0-9_]+)\s*\(([^;{}]*?)\)\s*;", _header_text(h), flags=re.M):
+            assert name not in protos, name
+            args = [] if args.strip() == "void" else [a for a in args.split(",")]
+            protos[name] = (_c_kind(ret), [_c_kind(a) for a in args])
+    return protos
+
+
+def test_binding_table_matches_the_header_prototypes():
+    """capi.SIGNATURES against every prototype of the five public headers: the same names, and per function the same number of arguments, the
+    same kind per argument (pointer / int / uint64_t / size_t / float / double; any pointer type matches c_void_p, c_char_p or POINTER(...))
+    and the same return kind.  A c_int where the header says size_t or uint64_t fails here instead of truncating silently at run time."""
+    from myosuite_mjx_amd import capi
+    protos = _header_prototypes()
+    assert len(protos) == 63 and protos["myo_sync"] == (ctypes.c_int, ["pointer"]) and protos["myo_model_free"] == ("void", ["pointer"])      # (the parser parses)
+    assert protos["myo_reset"] == (ctypes.c_int, ["pointer", "pointer", ctypes.c_uint64, "pointer"]) and protos["myo_last_error"] == ("pointer", [])
+    assert protos["myo_ppo_gae"][1][5:9] == [ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float]
+    assert sorted(capi.SIGNATURES) == sorted(protos)
+    wrong = {}
+    for name, (ret, args) in protos.items():
+        restype, argtypes = capi.SIGNATURES[name]
+        bound = (_ctypes_kind(restype), [_ctypes_kind(t) for t in argtypes])
+        if bound != (ret, args):
+            wrong[name] = (bound, (ret, args))
+    assert not wrong, wrong
+    L = capi.lib()                              # and lib() has applied the table
+    for name, (restype, argtypes) in capi.SIGNATURES.items():
+        fn = getattr(L, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+
+
+def _header_struct(name):
+    """[(member, kind, array length or None)] of `typedef struct <name> { ... } <name>;`: a declaration is `type a, b[8], *c;`."""
+    text = "".join(_header_text(h) for h in HEADERS)
+    body = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (name, name), text, flags=re.S).group(1)
+    members = []
+    for decl in filter(None, (" ".join(d.split()) for d in body.split(";"))):
+        base, first = re.fullmatch(r"((?:const )?\w+)\s*(.*)", decl).groups()
+        for item in (x.strip() for x in first.split(",")):
+            m = re.fullmatch(r"(\*?)\s*(\w+)(?:\[(\d+)\])?", item)
+            assert m, decl
+            members.append((m.group(2), _c_kind(base + (" *" if m.group(1) else "")), int(m.group(3)) if m.group(3) else None))
+    return members
+
+
+def _mirror_struct(cls):
+    """The same list from a ctypes.Structure's _fields_."""
+    out = []
+    for member, t in cls._fields_:
+        n = None
+        if issubclass(t, ctypes.Array):
+            t, n = t._type_, t._length_
+        out.append((member, _ctypes_kind(t), n))
+    return out
+
+
+def _mirrors():
+    from myosuite_mjx_amd import capi
+    return {"myo_dims": capi.Dims, "myo_task_config": capi.TaskConfig, "myo_walk_config": capi.WalkConfig, "myo_track_config": capi.TrackConfig,
+            "myo_ppo_config": capi.LearnerConfig}
+
+
+def test_struct_mirrors_match_the_header_structs(tmp_path):
+    """The five ctypes.Structure mirrors against the headers' typedef structs: member names, order, scalar kind and array length; and, with
+    gcc, ctypes.sizeof against the C compiler's sizeof."""
+    import shutil
+    import subprocess
+    for name, cls in _mirrors().items():
+        parsed = _header_struct(name)
+        assert len(parsed) >= 13 and parsed == _mirror_struct(cls), (name, [x for x in zip(parsed, _mirror_struct(cls)) if x[0] != x[1]])
+    assert ("tip_site", ctypes.c_int, 8) in _header_struct("myo_task_config") and ("seed", ctypes.c_uint64, None) in _header_struct("myo_track_config")
+    assert ("ref_robot_vel", "pointer", None) in _header_struct("myo_track_config")      # (the parser parses)
+    if shutil.which("gcc") is None:
+        pytest.skip("no gcc")
+    src = tmp_path / "sizes.c"
+    src.write_text('#include <stdio.h>\n#include "include/myo_hip.h"\n'
+                   'int main(void) { printf("' + " ".join(["%zu"] * len(_mirrors())) + '\\n", ' + ", ".join(f"sizeof({n})" for n in _mirrors()) + "); return 0; }\n")
+    subprocess.check_call(["gcc", "-std=c99", "-I", ROOT, str(src), "-o", str(tmp_path / "sizes")])
+    sizes = [int(x) for x in subprocess.check_output([str(tmp_path / "sizes")]).split()]
+    assert sizes == [ctypes.sizeof(cls) for cls in _mirrors().values()]
 
 
 def _header_enums(hdr):

@@ -99,8 +99,8 @@ def test_ppo_gae(gae_runs, case):
 
 def test_ppo_gae_refuses_bad_arguments():
     import torch
-    from myosuite_mjx_amd import capi, ppo
-    L = ppo._gae_lib()
+    from myosuite_mjx_amd import capi
+    L = capi.lib()
     x = torch.zeros((2, 3), device="cuda")
     p = x.data_ptr()
     assert L.myo_ppo_gae(p, p, p, p, p, 0, 3, 0.9, 0.9, p, p, None) == L.myo_ppo_gae(p, p, p, p, p, 2, 0, 0.9, 0.9, p, p, None) != 0

@@ -26,7 +26,7 @@ def kernels():
     return out
 
 
-# <NVT, KC, NC, NTR, WPE, SCHED, SPEC, HF, TRK, RK4>: what myo_hip.hip launch_step can select
+# <NVT, KC, NC, NTR, WPE, SCHED, SPEC, HF, TRK, RK4>: what launch_step (csrc/myo_host_step.h, select_wave_kernel) can select
 WAVE = {
     "headline: MyoHand, size-specialised": ("24, 8, 32, 1, 4, false, 1, false, false, false", 128),
     "hand / finger class, run-time sizes": ("24, 8, 32, 1, 3, false, 0, false, false, false", 128),   # budget of 3 waves per SIMD, lands on 128 registers = 4

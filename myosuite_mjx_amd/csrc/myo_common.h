@@ -165,7 +165,28 @@ struct DevBatch {
   const float* rwd_w;      // [rwd_n - 1] weight of every column but dense (weighted_reward_keys; 0: not summed)
   int rwd_n;               // columns of a row, dense included
   int rwd_sparse;          // 1: MYO_F_REWARD = the sparse column (rwd_mode "sparse"), 0: dense
+  // per-env object parameters (include/myo_hip_objects.h, myo_host_objects.h): size / position / friction of up to 16 selected collision
+  // geoms and the mass of up to 4 selected bodies.  Read by the TRK instantiation and its forward twin behind wave-uniform null tests
+  const float* objk;       // [B][obj_ng][12] what the kernels read, composed from the three geom tables once per launch (obj_compose_kernel): size (3),
+                           // bounding radius | centre in the LINK frame (3), - | friction (3), -; NULL: no geom selected
+  const int* obj_slot;     // [ncg] slot of a collision geom | [ngeom] slot of a model geom (forward pass) | [nl] body slot of a link; -1: not selected
+  const float* obj_cgf;    // [ncg][4] compiled friction (3) and priority of every collision geom: the partner's side of the per-env friction mix
+  float* obj_mass;         // [B][obj_nb] MYO_OBJ_MASS, read as the link's mass; NULL: no body selected
+  float *obj_size, *obj_pos, *obj_fric;   // [B][obj_ng][3] MYO_OBJ_SIZE / _POS / _FRICTION as the user writes them (body frame, user's coordinates)
+  const float* obj_gc;     // [obj_ng][16] per selected geom: type (bits), its body's origin (3) and rotation (9) inside the link frame, -, -, -
+  const float* obj_draw;   // [9 obj_ng + obj_nb][2] base, scale of every scalar parameter at a reset (scale 0: left alone); NULL: no draws
+  const int* obj_draw_k;   // ... and its draw: 0 .. 7 a shared one, -1 its own
+  int obj_ng, obj_nb, obj_ncg, obj_ngeom;
 };
+// key of a draw of the object parameters inside the reset's RNG stream: the shared draws first, then one per scalar parameter
+#define OBJ_MAX_DRAWS 8
+__device__ __host__ inline float obj_draw_u(uint64_t episode_seed, uint64_t global_env, int draw, int param) {
+  return u01(episode_seed ^ 0x7A5662DCDF6B1F6Dull, global_env * 1024 + (uint64_t)(draw >= 0 ? draw : OBJ_MAX_DRAWS + param), 12);
+}
+// bounding radius of a primitive geom from its size (mjModel.geom_rbound as the compiler sets it for these types)
+__device__ __host__ inline float obj_rbound(int type, float s0, float s1, float s2) {
+  return type == GEOM_SPHERE ? s0 : (type == GEOM_CAPSULE ? s0 + s1 : (type == GEOM_CYLINDER ? sqrtf(s0 * s0 + s1 * s1) : (type == GEOM_ELLIPSOID ? fmaxf(s0, fmaxf(s1, s2)) : sqrtf(s0 * s0 + s1 * s1 + s2 * s2))));
+}
 #define NCX 48      // overflow contact rows ALLOCATED per env; a kernel with NC LDS slots uses 64 - NC of them: 64 contacts in all
 #define NCX2 96     // TRK models: 128 contacts, 32 in LDS + 96 rows; rows of the second bank also hold that contact's solver state
 #define TRK_STATE 36  // floats of solver state at the end of a TRK overflow row: aref[6] | D mu mu_t D_t kc | jar[6] | jv[6] | 4 force + 7 Hessian coefficients | active-set word | pad, one per lane

@@ -6,6 +6,7 @@
 //   myo_task_track.h    MyoDM TrackEnv as a fused task of the TRK step kernel: reference lookup, reward / done, masked reset
 //   myo_kernel_lanes.h  step_kernel<G>: the first kernel, G = 16 / 32 / 64 lanes per env, all state in LDS (cross-check / fallback)
 //   myo_kernel_wave.h   step_kernel_w: one env per 64-lane wavefront (default): LDS layout, substep scheduler, size specialisations, the kernel body
+//   myo_kernel_wave_body.h  ... the text of the kernel body, compiled into step_kernel_w and into step_kernel_obj (per-env object parameters)
 //   myo_wave_util.h     its cross-lane / register helpers, WaveCfg (what the template parameters imply), con_row, the stage context
 //   myo_wave_motion.h   its stages: state check, kinematics, tendons and muscles, CRB + RNE, integration
 //   myo_wave_collision.h   broad phase, narrow phase
@@ -23,6 +24,7 @@
 //   myo_task_<name>.h   pose, reach, walk, stand, hold, keyturn, pen, baoding, die, myodm: a task's observation body, its configure and its hook record
 //   myo_host_model.h    myo_model_load in pieces: table upload, packing of the per-lane records, kernel class
 //   myo_host_batch.h    batch creation, the per-env override records, the table of fields behind myo_batch_field / read / write
+//   myo_host_objects.h  per-env object parameters (include/myo_hip_objects.h): selection, tables, the per-launch compose kernel, draw table, entry points
 //   myo_host_step.h     the table of step-kernel instantiations, launch_reset, launch_step, myo_bench_rollout and the other timing entry points
 //   myo_kernel_forward.h   forward_kernel_w: frames and contact list without a step (include/myo_hip_forward.h), its export tables and buffers
 //   myo_host_forward.h  ... its instantiations, launch and entry points
@@ -52,6 +54,8 @@
 #include "myo_host_tasks.h"
 #include "myo_host_model.h"
 #include "myo_host_batch.h"
+#include "../../include/myo_hip_objects.h"
+#include "myo_host_objects.h"
 #include "myo_host_step.h"
 #include "../../include/myo_hip_forward.h"
 #include "myo_kernel_forward.h"
@@ -72,7 +76,7 @@ int myo_model_load(const void* blobv, size_t nbytes, int device, myo_model** out
   std::unique_ptr<myo_model> m(new myo_model());   // a failed load frees what it had uploaded
   m->device = device;
   { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device) == hipSuccess) m->n_cu = prop.multiProcessorCount; }
-  if ((rc = load_model(m.get(), B)) || (rc = fwd_model_tables(m.get(), B))) return rc;
+  if ((rc = load_model(m.get(), B)) || (rc = fwd_model_tables(m.get(), B)) || (rc = obj_model_tables(m.get(), B))) return rc;
   *out = m.release();
   return MYO_OK;
 }

@@ -142,6 +142,11 @@ struct myo_model {
   int fwd_nbody = 0, fwd_nsite = 0, fwd_ngeom = 0, fwd_ncap = 0;
   const float *d_fwd_body = nullptr, *d_fwd_site = nullptr, *d_fwd_geom = nullptr;
   const int* d_fwd_cg_geom = nullptr;
+  // per-env object parameters (myo_host_objects.h): the compiled geom and body arrays a selection is checked against and starts from, as
+  // the blob has them (all optional there: a blob without them refuses the subsystem)
+  bool obj_ok = false;
+  std::vector<int> geom_type0, geom_body0, geom_priority0;
+  std::vector<double> geom_size0, geom_pos0, geom_friction0, body_mass_d;
 };
 
 // episode statistics (myo_batch_enable_episode_stats): running and last-finished rows [B][4] = dense return, sparse return, length, solved
@@ -180,6 +185,10 @@ struct myo_batch {
   bool bq_on = false;            // per-env body orientation started (DevBatch.bquat / bquat_range / bq_c / bq_flag allocated)
   bool fwd_on = false;           // forward buffers allocated (the first myo_forward)
   void* fwd_buf[16] = {};        // ... one per MYO_FWD_* id
+  bool obj_on = false;           // per-env object parameters enabled (myo_objects_enable: DevBatch.obj* allocated)
+  std::vector<int> obj_geoms, obj_bodies;   // ... the selection, model ids
+  float *d_objk = nullptr, *d_obj_draw = nullptr;   // ... the composed rows and the draw table (non-const twins of DevBatch.objk / obj_draw)
+  int* d_obj_draw_k = nullptr;
   std::vector<hipEvent_t> kev;   // per-launch event pairs around the step kernel (bench only)
   int kev_pending = 0;           // pairs recorded by asynchronous bench calls and not collected yet
   float last_kernel_ms = 0.f;

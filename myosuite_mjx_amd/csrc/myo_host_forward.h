@@ -34,7 +34,7 @@ static int launch_forward(myo_batch* b, hipStream_t s) {
   const myo_model* m = b->model;
   static OncePerDevice attr;
   int rc = fwd_check(b);
-  if (rc || (rc = fwd_start(b)) || (rc = set_lds_limit(attr, forward_kernels, 64 * 1024, m->device))) return rc;
+  if (rc || (rc = fwd_start(b)) || (rc = set_lds_limit(attr, forward_kernels, 64 * 1024, m->device)) || (rc = obj_compose(b, s))) return rc;
   FwdDev F{};
   F.nbody = m->fwd_nbody; F.nsite = m->fwd_nsite; F.ngeom = m->fwd_ngeom; F.ncap = m->fwd_ncap; F.has_site_mat = m->fwd_site_mat;
   F.bq_body = b->bq_body;

@@ -28,20 +28,22 @@ enum WaveKernelId {
 #define X(id, name, ...) id,
   MYO_WAVE_KERNELS(X)
 #undef X
+  WK_TRK_OBJ
 };
 static const WaveKernel wave_kernels[] = {
 #define X(id, name, ...) {name, step_kernel_w<__VA_ARGS__>},
   MYO_WAVE_KERNELS(X)
 #undef X
+  {"step_kernel_obj<36,20,32,2,2,false,0,false,true,false>", step_kernel_obj<36, 20, 32, 2, 2, false, 0, false, true, false>},   // WK_TRK_OBJ: the TRK kernel with the per-env object parameters (myo_host_objects.h)
 };
 
 // the instantiation a launch of model m runs: bm = the per-env body-mass override is on (only the run-time-sized instantiations read its
 // link tables), sched = the substep scheduler is on (large-kernel models without RK4; terrain models only with their specialised sizes)
-static WaveKernelId select_wave_kernel(const myo_model* m, bool bm, bool sched) {
+static WaveKernelId select_wave_kernel(const myo_model* m, bool bm, bool sched, bool obj = false) {
   const bool hand_sizes = m->hand_sizes && !bm, leg_sizes = m->leg_sizes && !bm;
   if (sched) return m->dw.hf.on ? WK_TERRAIN_SPEC_SCHED : (leg_sizes ? WK_LEG_SPEC_SCHED : WK_LEG_SCHED);
   if (m->rk4) return m->wave_cfg == 0 ? WK_HAND_RK4 : WK_LEG_RK4;
-  if (m->wave_cfg == 2) return WK_TRK;   // TrackEnv model class
+  if (m->wave_cfg == 2) return obj ? WK_TRK_OBJ : WK_TRK;   // TrackEnv model class (obj: the batch carries per-env object parameters)
   if (m->wave_cfg == 0) return hand_sizes ? WK_HAND_SPEC : WK_HAND;
   if (m->dw.hf.on) return m->terrain_sizes ? WK_TERRAIN_SPEC : WK_TERRAIN;   // terrain models: the instantiations with the height-field narrow phase
   return leg_sizes ? WK_LEG_SPEC : WK_LEG;
@@ -97,7 +99,7 @@ static int launch_wave(myo_batch* b, const float* action, int actmap, int nsub, 
     hipLaunchKernelGGL(balance_kernel, dim3(1), dim3(1024), 0, s, (const int*)b->db.diag, Bn, b->d_order, Bn / 4, prio_mode);
     order = b->d_order;
   }
-  const WaveKernel& k = wave_kernels[select_wave_kernel(m, b->bm_on, P.on)];
+  const WaveKernel& k = wave_kernels[select_wave_kernel(m, b->bm_on, P.on, b->obj_on)];
   if (!kflags) b->last_kernel = k.name;
   if (P.on) hipLaunchKernelGGL(sched_init_kernel, dim3(1), dim3(1024), 0, s, (const int*)b->db.diag, Bn, P.S);
   hipLaunchKernelGGL(k.fn, dim3(P.grid), dim3(64), (size_t)m->env_lds_bytes_w, s, (const DevModel*)m->d_dm, (const DevModelW*)m->d_dw, b->db, action, actmap,
@@ -151,6 +153,8 @@ static int launch_step(myo_batch* b, const float* action, int actmap, int nsub, 
     const int n = b->db.B * m->dm.nl;
     hipLaunchKernelGGL(link_compose_kernel, dim3((n + 255) / 256), dim3(256), 0, s, b->db, m->dm.nl, m->d_lm_adr, m->d_lm_body, m->d_lm_tab);
   }
+  // per-env object parameters: the rows the TRK kernel reads, composed from the batch's tables once per launch
+  if ((rc = obj_compose(b, s))) return rc;
   return wave ? launch_wave(b, action, actmap, nsub, s, kflags, wk) : launch_lanes(b, G, action, actmap, nsub, s);
 }
 

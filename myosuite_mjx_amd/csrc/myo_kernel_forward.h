@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(64, WPE) forward_kernel_w(const DevModel* __re
   const DevModel& M = *Mp;
   const DevModelW& W = *Wp;
   const LayW& Y = W.lay;
-  typedef WaveCfg<NVT, KC, NC, NTR, WPE, false, 0, HF, TRK, false> C;
+  typedef WaveCfg<NVT, KC, NC, NTR, WPE, false, 0, HF, TRK, false, TRK> C;   // (OBJ = TRK: the forward twin shows the per-env object parameters)
   constexpr bool FULL = C::FULL;
   constexpr int NCXK = C::NCXK;
   const int env = blockIdx.x;
@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(64, WPE) forward_kernel_w(const DevModel* __re
   w_kinematics<C>(X, lane, 0);
   {  // frames: lane = item
     const float org[3] = {M.origin[0], M.origin[1], M.origin[2]};
-    const BodyRot BR{TRK && Bt.bquat ? Bt.bquat + 4 * (size_t)env : nullptr, Bt.bq_c, Bt.bq_flag};
+    const BodyRot BR = body_rot_of(Bt, env, TRK, TRK);
     // (The goal offset moves the exported frames only: the collision stages turn the body's geoms with BodyRot and do not translate them.  The
     // die task's target carries no collision geom -- launch_forward passes goal_off only then -- so geom_xpos and contact.pos cannot disagree.)
     const float* const off = TRK && F.goal_off ? F.goal_off + 3 * (size_t)env : nullptr;
@@ -135,7 +135,11 @@ __global__ void __launch_bounds__(64, WPE) forward_kernel_w(const DevModel* __re
       fwd_store(sxpos, sxmat, i, org, x, R);
     }
     WFOR(i, F.ngeom) {
-      const FwdItem I = fwd_item(F.geom_rec, i);
+      FwdItem I = fwd_item(F.geom_rec, i);
+      if (BR.og) {   // per-env centre of a selected geom (DevBatch.objk): the row the collision stages place it with
+        const int s = Bt.obj_slot[Bt.obj_ncg + i];
+        if (s >= 0) { I.p[0] = BR.og[12 * s + 4]; I.p[1] = BR.og[12 * s + 5]; I.p[2] = BR.og[12 * s + 6]; }
+      }
       const bool moved = TRK && I.link < 0 && __float_as_int(I.a[0]) == F.bq_body;
       float x[3], R[9];
       fwd_world(Y, E, I, BR, moved, off, x, R);

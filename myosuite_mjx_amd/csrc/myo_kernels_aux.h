@@ -205,6 +205,20 @@ __device__ __forceinline__ bool reset_body(const DevBatch& Bt, const TaskDev& T,
       euler2quat(Bt.bquat + (size_t)e * 4, a);
     }
   }
+  if (Bt.obj_draw) {
+    // per-env object parameters (myo_objects_set_draws; BaodingEnvV1.reset baoding_v1.py:360-385, ReorientEnvV0.reset reorient_v0.py:221-247):
+    // scalar parameter p = base + scale * u, u one of the env's shared draws or the parameter's own; scale 0: the parameter stays
+    const int ng3 = 3 * Bt.obj_ng, np = 9 * Bt.obj_ng + Bt.obj_nb;
+    for (int p = lane; p < np; p += 64) {
+      const float base = Bt.obj_draw[2 * p], scale = Bt.obj_draw[2 * p + 1];
+      if (scale == 0.f) continue;
+      const float v = fmaf(scale, obj_draw_u(seed, ge, Bt.obj_draw_k[p], p), base);   // (one rounding: the host twin computes it in float64)
+      if (p < ng3) Bt.obj_size[(size_t)e * ng3 + p] = v;
+      else if (p < 2 * ng3) Bt.obj_pos[(size_t)e * ng3 + p - ng3] = v;
+      else if (p < 3 * ng3) Bt.obj_fric[(size_t)e * ng3 + p - 2 * ng3] = v;
+      else Bt.obj_mass[(size_t)e * Bt.obj_nb + p - 3 * ng3] = v;
+    }
+  }
   if (T.terrain && Bt.hfield) {
     // TerrainEnvV0.reset (walk_v0.py:563-622): a fresh 100 x 100 elevation grid per episode (in units of the height field's z scale).
     // Distribution parity only for the random draws, as for every reset.

@@ -11,8 +11,9 @@ template <class C, class LY> __device__ __forceinline__ int w_broad_phase(const 
   constexpr bool HF = C::HF, TRK = C::TRK, FULL = C::FULL;
   const DevModel& M = X.M; const DevModelW& W = X.W; const LY& Y = X.Y; extern __shared__ __align__(16) float E[]; const DevBatch& Bt = X.Bt; int* const ovf_cand = X.ovf_cand;
   const int env = X.env, ncg_ = X.ncg_, npair_ = X.npair_;
-  // TRK: per-env orientation of one world-welded body (MYO_F_BODYQUAT), applied wherever a geom frame is built; a constant nullptr elsewhere
-  const BodyRot BR{TRK && Bt.bquat ? Bt.bquat + 4 * (size_t)env : nullptr, Bt.bq_c, Bt.bq_flag};
+  // TRK: per-env orientation of one world-welded body (MYO_F_BODYQUAT) and per-env centres of the selected geoms (DevBatch.objk), applied
+  // wherever a geom frame is built; constant nullptrs elsewhere
+  const BodyRot BR = body_rot_of(Bt, env, TRK, C::OBJ);
   const BodyRot* const brp = TRK ? &BR : nullptr;
   int ncand = 0;
   int* cand = (int*)(E + Y.cand);
@@ -174,8 +175,9 @@ template <class C, class LY> __device__ __forceinline__ int w_narrow_phase(const
   constexpr bool HF = C::HF, TRK = C::TRK, FULL = C::FULL;
   const DevModelW& W = X.W; const LY& Y = X.Y; extern __shared__ __align__(16) float E[]; const DevBatch& Bt = X.Bt; float* const ovf_env = X.ovf_env; int* const ovf_cand = X.ovf_cand;
   const int env = X.env, ovf_row = X.ovf_row, nct = X.nct;
-  // TRK: per-env orientation of one world-welded body (MYO_F_BODYQUAT), applied wherever a geom frame is built; a constant nullptr elsewhere
-  const BodyRot BR{TRK && Bt.bquat ? Bt.bquat + 4 * (size_t)env : nullptr, Bt.bq_c, Bt.bq_flag};
+  // TRK: per-env orientation of one world-welded body (MYO_F_BODYQUAT) and per-env centres of the selected geoms (DevBatch.objk), applied
+  // wherever a geom frame is built; constant nullptrs elsewhere
+  const BodyRot BR = body_rot_of(Bt, env, TRK, C::OBJ);
   const BodyRot* const brp = TRK ? &BR : nullptr;
   int* cand = (int*)(E + Y.cand);
   int ncon = 0;

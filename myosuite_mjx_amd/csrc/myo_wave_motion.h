@@ -325,6 +325,9 @@ template <class C, class LY> __device__ __forceinline__ bool w_dynamics(const Wa
       for (int j = 0; j < 3; j++) Iw[3 * i + j] = T[3 * i] * R[3 * j] + T[3 * i + 1] * R[3 * j + 1] + T[3 * i + 2] * R[3 * j + 2];
     matvec(com, R, lcom);
     float mass = *lmass;
+    if constexpr (C::OBJ) {   // per-env mass of a selected body (DevBatch.obj_mass): the body is its link's only one, so the link's mass is the env's scalar
+      if (Bt.obj_mass) { const int s = Bt.obj_slot[Bt.obj_ncg + Bt.obj_ngeom + l]; if (s >= 0) mass = Bt.obj_mass[(size_t)env * Bt.obj_nb + s]; }
+    }
     float dif[3] = {E[Y.lpos + 3 * l] + com[0] - c0[0], E[Y.lpos + 3 * l + 1] + com[1] - c0[1], E[Y.lpos + 3 * l + 2] + com[2] - c0[2]};
     float ci[10];
     ci[0] = Iw[0] + mass * (dif[1] * dif[1] + dif[2] * dif[2]);

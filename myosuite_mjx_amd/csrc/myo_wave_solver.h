@@ -176,6 +176,11 @@ template <class C, class LY> __device__ __forceinline__ int w_contact_rows(const
       ckc = P[3];
       const float incl = F[0] - F[1];
       cmu = F[2];
+      float tors = 0.f;
+      if constexpr (C::OBJ) {   // per-env friction of the selected geoms (DevBatch.objk): the pair's sliding and torsional coefficients mixed again
+        tors = F[11];
+        if (X.Bt.objk) obj_pair_friction(X.Bt, X.env, P[0], P[1], cmu, tors);
+      }
       float imp = impedance(F + 6, dist, incl), K, B;
       kbi(F[4], F[5], F[7], M.timestep, &K, &B);
       if (P[5] == 1) {
@@ -190,7 +195,7 @@ template <class C, class LY> __device__ __forceinline__ int w_contact_rows(const
       caref[0] = -B * (vn_c + cmu * vt1_c) + pos; caref[1] = -B * (vn_c - cmu * vt1_c) + pos;
       caref[2] = -B * (vn_c + cmu * vt2_c) + pos; caref[3] = -B * (vn_c - cmu * vt2_c) + pos;
       if constexpr (TRK) {
-        if (P[5] == 4) { cmut = F[11]; cD2 = cD; caref[4] = -B * (vn_c + cmut * vs_c) + pos; caref[5] = -B * (vn_c - cmut * vs_c) + pos; }
+        if (P[5] == 4) { cmut = C::OBJ ? tors : F[11]; cD2 = cD; caref[4] = -B * (vn_c + cmut * vs_c) + pos; caref[5] = -B * (vn_c - cmut * vs_c) + pos; }
       }
     };
     if (lane < ncon) row_consts(lane, vn_c, vt1_c, vt2_c, vs_c, con.aref, con.D, con.mu, con.mut, con.D2, con.kc);

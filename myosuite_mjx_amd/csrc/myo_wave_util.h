@@ -164,7 +164,15 @@ struct BodyRot {
   const float* q;      // this env's quaternion (NULL: off)
   const float* c;      // R(q0)^T (9, row-major) | p_b (3)
   const int* flag;     // per collision geom: 1 on that body
+  // per-env object parameters (DevBatch.objk; TRK instantiation only): this env's rows and the slot table; og NULL: off.  Wave-uniform too
+  const float* og;     // [obj_ng][12]
+  const int* oslot;    // per collision geom: its row, -1: not selected
 };
+// the BodyRot of env `env` (trk / obj: WaveCfg's TRK and OBJ; where they are false the members are constant nullptrs and the code behind them goes away)
+__device__ __forceinline__ BodyRot body_rot_of(const DevBatch& Bt, int env, bool trk, bool obj) {
+  return BodyRot{trk && Bt.bquat ? Bt.bquat + 4 * (size_t)env : nullptr, Bt.bq_c, Bt.bq_flag,
+                 obj && Bt.objk ? Bt.objk + 12 * (size_t)env * Bt.obj_ng : nullptr, obj ? Bt.obj_slot : nullptr};
+}
 __device__ __forceinline__ void body_rot(const BodyRot& br, float* D) {
   const float q[4] = {br.q[0], br.q[1], br.q[2], br.q[3]};
   float Rq[9];
@@ -199,6 +207,15 @@ template <class LY> __device__ __forceinline__ void geom_world_mat(const DevMode
 }
 // ... with the per-env orientation of BodyRot (br: a constant nullptr outside the TRK instantiation, which leaves the two calls above)
 template <class LY> __device__ __forceinline__ void geom_world_pos(const DevModelW& W, const LY& Y, const float* E, int g, float* out, const BodyRot* br) {
+  if (br && br->og) {   // a selected geom's centre is the env's (a geom of a moving link: myo_objects_enable refuses world-welded ones)
+    const int s = br->oslot[g];
+    if (s >= 0) {
+      const float* o = br->og + 12 * s + 4;
+      const float lp[3] = {o[0], o[1], o[2]};
+      frame_point(Y, E, __float_as_int(W.cg_rec[4 * g].x), lp, out);
+      return;
+    }
+  }
   geom_world_pos(W, Y, E, g, out);
   if (br && br->q && __float_as_int(W.cg_rec[4 * g].x) < 0 && br->flag[g]) body_rot_point(*br, out);
 }
@@ -302,9 +319,12 @@ template <bool S> __device__ __forceinline__ int ldstatei(const int* p) {
 }
 
 // Everything the wave kernel and its stage functions derive from the ten template parameters, in one place.
-template <int NVT_, int KC_, int NC_, int NTR_, int WPE_, bool SCHED_, int SPEC_, bool HF_, bool TRK_, bool RK4_> struct WaveCfg {
+template <int NVT_, int KC_, int NC_, int NTR_, int WPE_, bool SCHED_, int SPEC_, bool HF_, bool TRK_, bool RK4_, bool OBJ_ = false> struct WaveCfg {
   static constexpr int NVT = NVT_, KC = KC_, NC = NC_, NTR = NTR_, WPE = WPE_, SPEC = SPEC_;
   static constexpr bool SCHED = SCHED_, HF = HF_, TRK = TRK_, RK4 = RK4_;
+  // per-env object parameters (DevBatch.objk / obj_mass): step_kernel_obj and the TRK forward twin; everywhere else the reads are not compiled
+  static constexpr bool OBJ = OBJ_;
+  static_assert(!OBJ || (TRK && !RK4 && !SCHED && SPEC == 0), "per-env object parameters: the run-time-sized Euler TRK instantiation only");
   static constexpr int CDW = (KC + 3) / 4;   // ints per contact holding its KC byte-packed dof ids
   static constexpr int NJ = TRK ? 4 : 3;     // jacobian rows per contact: normal, two tangents (, spin about the normal)
   static constexpr int NR = TRK ? 6 : 4;     // pyramid rows per contact
@@ -354,7 +374,8 @@ template <class C, class LY, class F> __device__ __forceinline__ void con_row(co
 // second-bank state block of contact c (TRK, c >= 64)
 template <class C> __device__ __forceinline__ float* bank1_state(float* ovf_env, int ovf_row, int c) { return ovf_env + (size_t)(c - C::NC) * ovf_row + C::ROWS; }
 
-// pair record -> locals.  (OVR: one geom's size / bounding radius may be a per-env value, DevBatch.gsize)
+// pair record -> locals.  (OVR: one geom's size / bounding radius may be a per-env value, DevBatch.gsize; TRK: those of the selected geoms
+// are the env's rows, DevBatch.objk -- the OVR idea with a slot table, collision geom -> row or -1, instead of one geom id)
 struct PairL { int g1, g2, dl, kc, pt, cd, t1, t2; float margin, gap, rb1, rb2, s1[3], s2[3]; };
 struct PairRaw { float4 q0, q1, q2, q3; };
 __device__ __forceinline__ PairRaw pair_raw(const DevModelW& W, int p) { const gpf4 Q = W.pair_rec + 4 * (size_t)p; return PairRaw{Q[0], Q[1], Q[2], Q[3]}; }
@@ -371,7 +392,30 @@ template <class C> __device__ __forceinline__ PairL pair_decode(const DevBatch& 
     if (L.g1 == Bt.gsize_cg) { L.s1[0] = G[0]; L.s1[1] = G[1]; L.s1[2] = G[2]; L.rb1 = G[3]; }
     if (L.g2 == Bt.gsize_cg) { L.s2[0] = G[0]; L.s2[1] = G[1]; L.s2[2] = G[2]; L.rb2 = G[3]; }
   }
+  if (C::OBJ && Bt.objk) {
+    const float* G = Bt.objk + 12 * (size_t)env * Bt.obj_ng;
+    const int a = Bt.obj_slot[L.g1], b = Bt.obj_slot[L.g2];
+    if (a >= 0) { const float* S = G + 12 * a; L.s1[0] = S[0]; L.s1[1] = S[1]; L.s1[2] = S[2]; L.rb1 = S[3]; }
+    if (b >= 0) { const float* S = G + 12 * b; L.s2[0] = S[0]; L.s2[1] = S[1]; L.s2[2] = S[2]; L.rb2 = S[3]; }
+  }
   return L;
+}
+// per-env friction of the pair (g1, g2) when one of its geoms is selected (Bt.objk set): lowering._contact_params' mix with the env's
+// rows in place of the selected geoms' compiled friction -- priorities differ: the higher priority's, else the component-wise maximum; both
+// floored at 1e-5 as MuJoCo floors them.  mu:
+// sliding, mut: torsional (the caller uses it for condim-4 pairs only).  A pair without a selected geom keeps the pair table's values
+__device__ __forceinline__ void obj_pair_friction(const DevBatch& Bt, int env, int g1, int g2, float& mu, float& mut) {
+  const int a = Bt.obj_slot[g1], b = Bt.obj_slot[g2];
+  if (a < 0 && b < 0) return;
+  const float* G = Bt.objk + 12 * (size_t)env * Bt.obj_ng;
+  const float *c1 = Bt.obj_cgf + 4 * g1, *c2 = Bt.obj_cgf + 4 * g2;
+  const float *f1 = a >= 0 ? G + 12 * a + 8 : c1, *f2 = b >= 0 ? G + 12 * b + 8 : c2;
+  const float p1 = c1[3], p2 = c2[3];
+  if (p1 != p2) { const float* f = p1 > p2 ? f1 : f2; mu = f[0]; mut = f[1]; }
+  else { mu = fmaxf(f1[0], f2[0]); mut = fmaxf(f1[1], f2[1]); }
+  // mj_contactParam's floor (mjMINMU): a row of zeros must not turn a frictional pair into a frictionless one (mu == 0 is how the row stage
+  // and the efc count recognise a condim-1 pair)
+  mu = fmaxf(mu, 1e-5f); mut = fmaxf(mut, 1e-5f);
 }
 template <class C> __device__ __forceinline__ PairL pair_load(const DevModelW& W, const DevBatch& Bt, int env, int p) { return pair_decode<C>(Bt, env, pair_raw(W, p)); }
 

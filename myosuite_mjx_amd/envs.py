@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import capi, rewards, tasks, track
+from . import capi, objects, rewards, tasks, track
 from . import model as _model
 from .capi import _DevArray  # noqa: F401  (sim.py takes it from here)
 
@@ -206,6 +206,17 @@ UNSUPPORTED = {
 for _id in ("myoChallengeBaodingP2-v1", "myoSarcChallengeBaodingP2-v1", "myoFatiChallengeBaodingP2-v1"):
     UNSUPPORTED[_id] = ("re-draws the balls' size, mass and friction per episode (obj_size_range, obj_mass_range, obj_friction_change): "
                         "the TrackEnv-class step kernel has no per-env ball size, mass or friction")
+# The registered numbers of the two P2 ids as (P1 id, make kwargs the P1 id honours, set_object_randomization kwargs): data only.  The ids
+# themselves still raise (above): what runs a P2 configuration is
+#     env = make(p1_id, num_envs, **make_kwargs); env.set_object_randomization(**randomization); env.reset()
+P2_CONFIGS = {
+    "myoChallengeBaodingP2-v1": ("myoChallengeBaodingP1-v1",
+                                 dict(task_choice="random", goal_time_period=(4, 6), goal_xrange=(0.020, 0.030), goal_yrange=(0.022, 0.032)),
+                                 dict(obj_size_range=(0.018, 0.024), obj_mass_range=(0.030, 0.300), obj_friction_change=(0.2, 0.001, 0.00002))),
+    "myoChallengeDieReorientP2-v0": ("myoChallengeDieReorientP1-v0",
+                                     dict(goal_pos=(-0.020, 0.020), goal_rot=(-3.14, 3.14)),
+                                     dict(obj_size_change=0.007, obj_mass_range=(0.050, 0.250), obj_friction_change=(0.2, 0.001, 0.00002))),
+}
 # myoChallengeDieReorientP2-v0 (envs/myo/myochallenge/__init__.py:336-353) and its muscle-condition variants
 for _id in ("myoChallengeDieReorientP2-v0", "myoSarcChallengeDieReorientP2-v0", "myoFatiChallengeDieReorientP2-v0"):
     UNSUPPORTED[_id] = ("re-draws the die's size, mass and friction per episode (obj_size_change, obj_mass_range, obj_friction_change): "
@@ -370,6 +381,45 @@ class BatchedMyoEnv(capi.FieldViews):
         = goal_init_pos + ...` of ReorientEnvV0.reset, as an offset); its orientation is `body_quat`.  A torch view of the library's buffer
         (no copy; writes move the goal from the next observation on, until the env's next reset re-draws it).  With as_torch=False: a
         numpy copy (assign the property to write it).""")
+
+    # -- per-env object parameters (include/myo_hip_objects.h, objects.py): size / position / friction of geoms, mass of bodies --------------
+    def enable_object_params(self, geoms=(), bodies=()):
+        """Select the geoms and bodies (names or ids; up to 16 and 4) whose size / position / friction and mass become per-env values, and
+        return the ObjectParams.  TrackEnv-class models only; everything else raises capi.MyoError with the library's reason.  The baoding
+        and die tasks need no call: `object_params` selects their objects by itself."""
+        if getattr(self, "_objects", None) is None:
+            self._objects = objects.ObjectParams(self.batch, self.mjmodel, list(geoms), list(bodies), self._torch, self.device)
+        elif (geoms or bodies) and (self._objects.geom_ids, self._objects.body_ids) != objects.resolve_ids(self.mjmodel, geoms, bodies):
+            raise ValueError("object parameters are already enabled with another selection")
+        return self._objects
+
+    @property
+    def object_params(self):
+        """The ObjectParams of this env: `.size` / `.pos` / `.friction` [num_envs, ng, 3] and `.mass` [num_envs, nb] of the task's objects,
+        torch views of the library's device memory (writes take effect at the next step / forward); with as_torch=False numpy copies,
+        written back by assignment.  The first access enables the subsystem: baoding -- the geoms and bodies of ball1 and ball2; die -- the
+        15 geoms and the body of `Object`; any other TrackEnv-class task after `enable_object_params(geoms=..., bodies=...)`."""
+        if getattr(self, "_objects", None) is None:
+            sel = objects.task_objects(self.mjmodel, self.spec["task"])
+            if sel is None:
+                raise AttributeError(f"{self.id}: no default objects for the {self.spec['task']} task; call enable_object_params(geoms=[...], bodies=[...]) first")
+            self.enable_object_params(*sel)
+        return self._objects
+
+    def set_object_randomization(self, **kw):
+        """Re-draw the objects' parameters at every reset of an env, with the reference's names and meaning: baoding -- obj_size_range,
+        obj_mass_range, obj_friction_change (baoding_v1.py:115-135, 360-385); die -- obj_size_change, obj_mass_range, obj_friction_change
+        (reorient_v0.py:94-101, 221-247; its visual `target_dice` geom collides with nothing and is not modelled).  Arguments left out are
+        not re-drawn; no argument switches the draws off.  ValueError on lo > hi or a negative value, before any library call.  The draws
+        happen in the reset kernel: call reset() to start the first randomised episode."""
+        task = self.spec["task"]
+        sel = objects.task_objects(self.mjmodel, task)
+        table = objects.task_draws(self.mjmodel, task, *(sel or ((), ())), **kw)      # (raises before the subsystem is touched)
+        if not kw and getattr(self, "_objects", None) is None:                        # nothing to switch off: the subsystem stays off
+            return None
+        self.object_params.set_draws(table if kw else None)
+        self._object_draws = table if kw else None
+        return table
 
     # -- touch sensors and contact forces (make(..., sensors=True)) ---------------------------------------
     def _need_sensors(self):

@@ -128,6 +128,36 @@ class Model:
         li.reshape(-1, 6)[link] = [I[0, 0], I[1, 1], I[2, 2], I[0, 1], I[0, 2], I[1, 2]]
         return out
 
+    def with_geom_params(self, geoms, size=None, pos=None, friction=None) -> "Model":
+        """Copy of the model with `geom_size[geoms]`, `geom_pos[geoms]` and / or `geom_friction[geoms]` set for every env (`geoms`: ids or
+        names; each array [len(geoms), 3], None: unchanged), as BaodingEnvV1.reset and ReorientEnvV0.reset edit a compiled MuJoCo model
+        (baoding_v1.py:360-385, reorient_v0.py:221-247).  geom_rbound follows the new size as the compiler would set it; the HIP tables
+        are lowered again from the edited arrays.  Nothing else changes (masses, inertias, invweights keep their values, as without
+        mj_setConst).  Primitive geoms only (a mesh's shape is its vertex table)."""
+        from .lowering import lower
+        from .mjcf import GEOM_BOX, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_ELLIPSOID, GEOM_SPHERE, CompiledModel, geom_rbound
+        ids = [self.geom_name2id(g) if isinstance(g, str) else int(g) for g in geoms]
+        for g in ids:
+            if not 0 <= g < self.ngeom:
+                raise ValueError(f"no geom {g!r}")
+        arrays = {k: np.array(v, copy=True) for k, v in self.arrays.items()}
+        for name, val, nonneg in (("geom_size", size, True), ("geom_pos", pos, False), ("geom_friction", friction, True)):
+            if val is None:
+                continue
+            val = np.asarray(val, float).reshape(len(ids), 3)
+            if not np.isfinite(val).all() or (nonneg and (val < 0).any()):
+                raise ValueError(f"{name} must be finite" + (" and >= 0" if nonneg else ""))
+            arrays[name][ids] = val
+        for g in ids:
+            if int(arrays["geom_type"][g]) not in (GEOM_SPHERE, GEOM_CAPSULE, GEOM_ELLIPSOID, GEOM_CYLINDER, GEOM_BOX):
+                raise NotImplementedError("with_geom_params: sphere / capsule / ellipsoid / cylinder / box geoms only")
+            arrays["geom_rbound"][g] = geom_rbound(int(arrays["geom_type"][g]), arrays["geom_size"][g])
+        if "hip_cg_link" in arrays:
+            cm = CompiledModel(arrays={k: v for k, v in arrays.items() if not k.startswith("hip_")}, names=self.names)
+            lower(cm)
+            arrays = cm.arrays
+        return Model(arrays, self.names, self.source)
+
     def with_body_pos(self, body, pos) -> "Model":
         """Copy of the model with `body_pos[body] = pos` (`body`: id or name), as KeyTurnEnvV0.reset moves the key
         (envs/myo/myobase/key_turn_v0.py:164-167).  The HIP tables follow for a body that heads a kinematic root link (its link origin moves

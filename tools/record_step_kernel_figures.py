@@ -4,6 +4,9 @@ tests/test_forward_resources.py compares the current build with (no GPU needed).
     python tools/record_step_kernel_figures.py [path/to/libmyo_hip.so]          # print
     python tools/record_step_kernel_figures.py path/to/libmyo_hip.so --write    # refresh tests/golden/step_kernel_figures.json
 
+The record holds the step_kernel_w instantiations only.  step_kernel_obj (the TrackEnv-class body with the per-env object parameters compiled in,
+csrc/myo_kernel_wave.h) is deliberately not in it: it is new code with nothing to be equal to; tests/test_object_params_resources.py bounds it.
+
 The committed record is made from a build of the commit BEFORE a change that must leave the step kernels' code alone (same compiler, same
 flags): check the parent out somewhere, build it there, and point this tool at that library."""
 import json

@@ -30,6 +30,7 @@ FLAG_BAD_STATE, FLAG_BAD_QACC, FLAG_CONTACT_OVERFLOW, FLAG_CAND_OVERFLOW, FLAG_S
 RWD_DENSE, RWD_SPARSE = 0, 1
 EP_RUNNING, EP_LAST, EP_FINISHED, EP_COUNT = range(4)
 _EP_DTYPE = {EP_RUNNING: np.float32, EP_LAST: np.float32, EP_FINISHED: np.uint8, EP_COUNT: np.int32}
+_EP_ITEM = {EP_RUNNING: (4,), EP_LAST: (4,), EP_FINISHED: (), EP_COUNT: ()}
 # forward pass (include/myo_hip_forward.h): buffer ids, words of a contact record, and the per-item shape of each buffer
 FWD_XPOS, FWD_XMAT, FWD_XIPOS, FWD_SITE_XPOS, FWD_SITE_XMAT, FWD_GEOM_XPOS, FWD_GEOM_XMAT, FWD_NCON, FWD_CONTACT = range(9)
 FWD_COUNT = 9
@@ -38,6 +39,7 @@ FWD_NAMES = {"xpos": FWD_XPOS, "xmat": FWD_XMAT, "xipos": FWD_XIPOS, "site_xpos"
              "geom_xpos": FWD_GEOM_XPOS, "geom_xmat": FWD_GEOM_XMAT, "ncon": FWD_NCON, "contact": FWD_CONTACT}
 _FWD_ITEM = {FWD_XPOS: (3,), FWD_XMAT: (3, 3), FWD_XIPOS: (3,), FWD_SITE_XPOS: (3,), FWD_SITE_XMAT: (3, 3), FWD_GEOM_XPOS: (3,),
              FWD_GEOM_XMAT: (3, 3), FWD_NCON: (), FWD_CONTACT: (FWD_CONTACT_WORDS,)}
+_FWD_DTYPE = {which: np.int32 if which == FWD_NCON else np.float32 for which in _FWD_ITEM}
 
 
 class Dims(C.Structure):
@@ -274,6 +276,45 @@ def _ptr(a, ctype=C.c_float):
     return a.ctypes.data_as(C.POINTER(ctype)) if a is not None else None
 
 
+# ---- device buffers: the one lookup, host copy and zero-copy view every buffer family goes through (objects.py and ppo.py use them too)
+def buffer_lookup(fn, *args):
+    """Call a lookup `fn(*args, void**, size_t*, size_t*)`: (device pointer, pitch, width), the last two in elements per env row."""
+    p, pitch, width = C.c_void_p(), C.c_size_t(), C.c_size_t()
+    _chk(fn(*args, C.byref(p), C.byref(pitch), C.byref(width)))
+    return p.value, pitch.value, width.value
+
+
+def host_read(fn, *args, shape, dtype, sized=True):
+    """A fresh host array filled by a read `fn(*args, void* host[, size_t nbytes])`."""
+    out = np.empty(shape, dtype)
+    _chk(fn(*args, out.ctypes.data, out.nbytes) if sized else fn(*args, out.ctypes.data))
+    return out
+
+
+class _DevArray:
+    """__cuda_array_interface__ holder so torch can view library-owned device memory without a copy."""
+
+    def __init__(self, ptr, shape, typestr, owner):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+        self._owner = owner
+
+
+def device_view(torch, ptr, shape, dtype, owner, device):
+    """Zero-copy torch tensor over library-owned device memory; `owner` (the batch, the learner) stays alive as long as the tensor."""
+    return torch.as_tensor(_DevArray(ptr, shape, np.dtype(dtype).str, owner), device=f"cuda:{device}")
+
+
+# The buffer families of a batch: (lookup function, read function, spec).  spec(B, id, width) -> (dtype, shape) is the one statement of a
+# family's element type and per-env item shape; width() gives the elements per env row and is called only where the shape depends on it
+FAMILIES = {
+    "field": ("myo_batch_field", "myo_batch_read", lambda B, f, width: (np.int32 if f in INT_FIELDS else np.float32, (B, width()))),
+    "rwd": ("myo_batch_rwd_row", "myo_batch_rwd_read", lambda B, _, width: (np.float32, (B, width()))),
+    "episode": ("myo_batch_episode_buffer", "myo_batch_episode_read", lambda B, which, width: (_EP_DTYPE[which], (B, *_EP_ITEM[which]))),
+    "forward": ("myo_forward_buffer", "myo_forward_read", lambda B, which, width: (
+        _FWD_DTYPE[which], (B, width() // int(np.prod(_FWD_ITEM[which])), *_FWD_ITEM[which]) if _FWD_ITEM[which] else (B,))),
+}
+
+
 class HipModel:
     """Device-resident model (mjx.put_model counterpart, mjx/play.py:10)."""
 
@@ -435,28 +476,20 @@ class HipBatch:
         _chk(lib().myo_batch_enable_rewards(self.h, _ptr(w), w.size, int(mode)))
 
     def rwd_row_ptr(self):
-        p, pitch, width = C.c_void_p(), C.c_size_t(), C.c_size_t()
-        _chk(lib().myo_batch_rwd_row(self.h, C.byref(p), C.byref(pitch), C.byref(width)))
-        return p.value, pitch.value, width.value
+        return self.buffer_ptr("rwd")
 
     def read_rwd(self) -> np.ndarray:
-        out = np.empty((self.B, lib().myo_batch_rwd_ncol(self.h)), np.float32)
-        _chk(lib().myo_batch_rwd_read(self.h, out.ctypes.data, out.nbytes))
-        return out
+        return self.buffer_read("rwd")
 
     def enable_episode_stats(self):
         _chk(lib().myo_batch_enable_episode_stats(self.h))
 
     def episode_ptr(self, which):
-        p, pitch, width = C.c_void_p(), C.c_size_t(), C.c_size_t()
-        _chk(lib().myo_batch_episode_buffer(self.h, int(which), C.byref(p), C.byref(pitch), C.byref(width)))
-        return p.value, pitch.value, width.value
+        return self.buffer_ptr("episode", which)
 
     def read_episode(self, which) -> np.ndarray:
         """Host copy of an episode buffer: EP_RUNNING / EP_LAST [B, 4] float32, EP_FINISHED [B] uint8, EP_COUNT [B] int32."""
-        out = np.empty((self.B, 4) if which in (EP_RUNNING, EP_LAST) else (self.B,), _EP_DTYPE[which])
-        _chk(lib().myo_batch_episode_read(self.h, int(which), out.ctypes.data, out.nbytes))
-        return out
+        return self.buffer_read("episode", which)
 
     def episode_update(self, max_episode_steps, stream=None):
         _chk(lib().myo_episode_update(self.h, int(max_episode_steps), stream))
@@ -483,24 +516,41 @@ class HipBatch:
         (MYO_F_BODYQUAT_RANGE); starts the per-env orientation."""
         self._set_range(F_BODYQUAT_RANGE, 3, lo, hi)
 
-    def field_ptr(self, field):
-        p, pitch, width = C.c_void_p(), C.c_size_t(), C.c_size_t()
-        _chk(lib().myo_batch_field(self.h, field, C.byref(p), C.byref(pitch), C.byref(width)))
-        return p.value, pitch.value, width.value
+    # -- device buffers by family (FAMILIES) and id (None: the family has one buffer); the per-family methods below are these four --
+    def _args(self, i):
+        return (self.h,) if i is None else (self.h, int(i))
 
-    def _width(self, field):
-        per_body, fixed = _OVERRIDE_WIDTH.get(field, (0, 0))
-        return per_body * self.model.dims.nbody + fixed if per_body or fixed else self.field_ptr(field)[2]
+    def buffer_ptr(self, family, i=None):
+        """(device pointer, pitch, width); MyoError with the library's reason where the buffer does not exist (yet)."""
+        return buffer_lookup(getattr(lib(), FAMILIES[family][0]), *self._args(i))
+
+    def _width(self, family, i):
+        per_body, fixed = _OVERRIDE_WIDTH.get(i, (0, 0)) if family == "field" else (0, 0)
+        return per_body * self.model.dims.nbody + fixed if per_body or fixed else self.buffer_ptr(family, i)[2]
+
+    def buffer_spec(self, family, i=None, width=None):
+        """(dtype, shape) of a buffer; `width`: its row's elements where a lookup has just reported them."""
+        return FAMILIES[family][2](self.B, i, (lambda: self._width(family, i)) if width is None else (lambda: width))
+
+    def buffer_read(self, family, i=None) -> np.ndarray:
+        dtype, shape = self.buffer_spec(family, i)
+        return host_read(getattr(lib(), FAMILIES[family][1]), *self._args(i), shape=shape, dtype=dtype)
+
+    def buffer_view(self, torch, device, family, i=None):
+        """Zero-copy torch view of a buffer in its shape: one library call."""
+        ptr, _, width = self.buffer_ptr(family, i)
+        dtype, shape = self.buffer_spec(family, i, width)
+        return device_view(torch, ptr, shape, dtype, self, device)
+
+    def field_ptr(self, field):
+        return self.buffer_ptr("field", field)
 
     def read(self, field) -> np.ndarray:
-        width = self._width(field)
-        out = np.empty((self.B, width), np.int32 if field in INT_FIELDS else np.float32)
-        _chk(lib().myo_batch_read(self.h, field, out.ctypes.data, out.nbytes))
-        return out
+        return self.buffer_read("field", field)
 
     def write(self, field, arr):
-        width = self._width(field)
-        a = np.ascontiguousarray(arr, np.int32 if field in INT_FIELDS else np.float32).reshape(self.B, width)
+        dtype, shape = self.buffer_spec("field", field)
+        a = np.ascontiguousarray(arr, dtype).reshape(shape)
         _chk(lib().myo_batch_write(self.h, field, a.ctypes.data, a.nbytes))
 
     def reset(self, mask_ptr=None, seed=0, stream=None):
@@ -519,26 +569,18 @@ class HipBatch:
 
     def forward_ptr(self, which):
         """(device pointer, pitch, width) of forward buffer FWD_*; MyoError before the first forward()."""
-        p, pitch, width = C.c_void_p(), C.c_size_t(), C.c_size_t()
-        _chk(lib().myo_forward_buffer(self.h, int(which), C.byref(p), C.byref(pitch), C.byref(width)))
-        return p.value, pitch.value, width.value
+        return self.buffer_ptr("forward", which)
 
     def forward_shape(self, which):
         """Shape of forward buffer FWD_*: [B, n, 3], [B, n, 3, 3], [B] (ncon) or [B, ncon_max, 16] (contact)."""
-        width = self.forward_ptr(which)[2]
-        item = _FWD_ITEM[which]
-        return (self.B, width // int(np.prod(item)), *item) if item else (self.B,)
+        return self.buffer_spec("forward", which)[1]
 
     def forward_read(self, which) -> np.ndarray:
         """Host copy of forward buffer FWD_* in its shape; FWD_NCON is int32, FWD_CONTACT float32 (words 13..15 of a record are int32 bits)."""
-        out = np.empty(self.forward_shape(which), np.int32 if which == FWD_NCON else np.float32)
-        _chk(lib().myo_forward_read(self.h, int(which), out.ctypes.data, out.nbytes))
-        return out
+        return self.buffer_read("forward", which)
 
     def status(self) -> np.ndarray:
-        out = np.zeros(self.B, np.int32)
-        _chk(lib().myo_status(self.h, out.ctypes.data))
-        return out
+        return host_read(lib().myo_status, self.h, shape=self.B, dtype=np.int32, sized=False)
 
     def random_action(self, action_ptr, seed, step, env_offset=0, stream=None):
         _chk(lib().myo_random_action(self.h, action_ptr, seed, step, env_offset, stream))
@@ -575,26 +617,18 @@ class HipBatch:
         _chk(lib().myo_bench_rollout(self.h, steps, nsub, seed, mode, max_episode_steps, stream, None))
 
 
-class _DevArray:
-    """__cuda_array_interface__ holder so torch can view library-owned device memory without a copy."""
-
-    def __init__(self, ptr, shape, typestr, owner):
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
-        self._owner = owner
-
-
 class FieldViews:
-    """`view` / `_stream` of the env classes: the env has batch, num_envs, device, _views = {} and _torch (the module, or None for numpy I/O)."""
+    """`view` / `_stream` of the env classes: the env has batch, device, _views = {} and _torch (the module, or None for numpy I/O)."""
 
-    def view(self, field):
-        """torch view (zero copy, cached) of a per-env field; without torch a numpy copy."""
+    def view(self, i, family="field"):
+        """torch view (zero copy, cached under (family, id): the first use makes one library call, later uses none) of a per-env field,
+        or of buffer `i` of another family of FAMILIES; without torch a numpy copy."""
         if self._torch is None:
-            return self.batch.read(field)
-        if field not in self._views:
-            ptr, pitch, width = self.batch.field_ptr(field)
-            arr = _DevArray(ptr, (self.num_envs, width), "<i4" if field in INT_FIELDS else "<f4", self.batch)
-            self._views[field] = self._torch.as_tensor(arr, device=f"cuda:{self.device}")
-        return self._views[field]
+            return self.batch.buffer_read(family, i)
+        v = self._views.get((family, i))
+        if v is None:
+            v = self._views[family, i] = self.batch.buffer_view(self._torch, self.device, family, i)
+        return v
 
     def _stream(self):
         return self._torch.cuda.current_stream(self.device).cuda_stream if self._torch is not None else None
@@ -632,12 +666,9 @@ class ForwardRecord:
         self.refresh()
 
     def _get(self, which):
-        b = self._batch
         if self._torch is None:
-            return b.forward_read(which)
-        ptr = b.forward_ptr(which)[0]
-        arr = _DevArray(ptr, b.forward_shape(which), "<i4" if which == FWD_NCON else "<f4", b)
-        return self._torch.as_tensor(arr, device=f"cuda:{self._device}")
+            return self._batch.forward_read(which)
+        return self._batch.buffer_view(self._torch, self._device, "forward", which)
 
     def refresh(self):
         if self._torch is not None and hasattr(self, "xpos"):

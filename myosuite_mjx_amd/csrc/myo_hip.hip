@@ -17,7 +17,8 @@
 //   myo_kernels_learner.h  the PPO SGD step: both MLPs forward and backward on the FP32 MFMA, loss, Adam (include/myo_hip_ppo.h)
 // Host side: a subsystem's host record, its launches and the entry points of its public header live in one file
 //   myo_host.h          shared by all of them: error reporting, device-memory pool (DevPool), use_device, blob view (Blob, blob_open), kernel
-//                       attributes once per device (set_lds_limit), myo_model, myo_batch, the per-task hook record (TaskHooks) and its launchers
+//                       attributes once per device (set_lds_limit), myo_model, myo_batch, the device buffers handed to callers (DevBuf, buf_lookup,
+//                       buf_read, the blocking copies), the per-task hook record (TaskHooks) and its launchers
 //   myo_rewards.h       reward-term rows and episode statistics (include/myo_hip_rewards.h): column table per task, walk term kernel, statistics kernel, entry points
 //   myo_host_tasks.h    the task table: includes the task files below, task_hooks, launch_obs
 //   myo_task_util.h     what the task files share: link-chain walk, row prologue, site gather, activation term, the common configure checks
@@ -94,8 +95,7 @@ int myo_model_nsensor(const myo_model* m) { return m ? m->dw.ntouch : 0; }
 int myo_model_set_switch(myo_model* m, int dc, int dl, int de) {
   if (!m) return fail(MYO_E_ARG, "null model");
   m->dm.disable_contact = dc; m->dm.disable_limit = dl; m->dm.disable_ellipsoid = de;
-  if (m->d_dm) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipMemcpy(m->d_dm, &m->dm, sizeof(DevModel), hipMemcpyHostToDevice)); }
-  return MYO_OK;
+  return m->d_dm ? copy_to_device(m->device, m->d_dm, &m->dm, sizeof(DevModel)) : MYO_OK;
 }
 
 // batches, per-env fields and overrides: myo_host_batch.h
@@ -231,16 +231,14 @@ int myo_batch_set_condition(myo_batch* b, int frame_skip, int epl_actuator, int 
 int myo_batch_set_fatigue_reset(myo_batch* b, int mode, const float* fatigue_vec) {
   if (!b || mode < 0 || mode > 2 || (mode == 2 && !fatigue_vec)) return fail(MYO_E_ARG, "myo_batch_set_fatigue_reset: mode 0 / 1 / 2 (+ vector)");
   HIPCHK(hipSetDevice(b->model->device));
-  if (mode == 2) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipMemcpy(b->d_fatvec, fatigue_vec, (size_t)b->model->dm.nu * 4, hipMemcpyHostToDevice)); }
+  if (mode == 2) { const int rc = copy_to_device(b->model->device, b->d_fatvec, fatigue_vec, (size_t)b->model->dm.nu * 4); if (rc) return rc; }
   b->task.fatigue_mode = mode; b->task.fatigue_vec = mode == 2 ? b->d_fatvec : nullptr;
   return MYO_OK;
 }
 
 int myo_status(myo_batch* b, int32_t* host_flags) {
   if (!b || !host_flags) return fail(MYO_E_ARG, "myo_status: null");
-  HIPCHK(hipSetDevice(b->model->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(host_flags, b->db.flags, (size_t)b->db.B * 4, hipMemcpyDeviceToHost));
+  if (const int rc = copy_to_host(b->model->device, host_flags, b->db.flags, (size_t)b->db.B * 4)) return rc;
   HIPCHK(hipMemset(b->db.flags, 0, (size_t)b->db.B * 4));
   return MYO_OK;
 }
@@ -269,8 +267,7 @@ int myo_set_lanes(int lanes) {
 /* diagnostic build only (MYO_STAMPS=1): per-workgroup clock64 totals of the 10 stages of the last myo_step */
 int myo_read_stamps(myo_batch* b, long long* host, int nwg) {
   if (!b || !host) return fail(MYO_E_ARG, "myo_read_stamps: null");
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(host, b->d_stamps, (size_t)nwg * 12 * sizeof(long long), hipMemcpyDeviceToHost));
+  if (const int rc = copy_to_host(b->model->device, host, b->d_stamps, (size_t)nwg * 12 * sizeof(long long))) return rc;
   return MYO_STAMPS ? MYO_OK : 1;
 }
 

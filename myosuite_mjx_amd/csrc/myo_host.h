@@ -199,6 +199,37 @@ struct myo_batch {
   }
 };
 
+// ---- device buffers handed to the caller.  Every family (batch fields, reward row, episode buffers, forward buffers, object tables) keeps
+// one function with its own refusals that yields a DevBuf; the lookup, read and write entry points are argument checks plus the pieces below.
+struct DevBuf { void* p; size_t width, elem; };   // device pointer, elements per env row (pitch = width everywhere), bytes per element
+typedef int (*BufFamily)(const myo_batch*, int which, DevBuf*);
+static int buf_out(const DevBuf& d, void** dev_ptr, size_t* pitch, size_t* width) { *dev_ptr = d.p; *pitch = *width = d.width; return MYO_OK; }
+// blocking copies: after everything enqueued on `device` has run.  Zero bytes: the wait alone
+static int copy_blocking(int device, void* dst, const void* src, size_t nbytes, hipMemcpyKind kind) {
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(hipDeviceSynchronize());
+  if (nbytes) HIPCHK(hipMemcpy(dst, src, nbytes, kind));
+  return MYO_OK;
+}
+static int copy_to_host(int device, void* host, const void* dev, size_t nbytes) { return copy_blocking(device, host, dev, nbytes, hipMemcpyDeviceToHost); }
+static int copy_to_device(int device, void* dev, const void* host, size_t nbytes) { return copy_blocking(device, dev, host, nbytes, hipMemcpyHostToDevice); }
+// a host array of the whole buffer: B rows of width elements.  `mismatch` is the caller's error text
+static int buf_check(const myo_batch* b, const DevBuf& d, const void* host, size_t nbytes, const char* mismatch) {
+  return host && nbytes == (size_t)b->db.B * d.width * d.elem ? MYO_OK : fail(MYO_E_ARG, mismatch);
+}
+// the lookup and the read of a family (a write validates between buf_check and copy_to_device)
+static int buf_lookup(BufFamily family, const myo_batch* b, int which, void** dev_ptr, size_t* pitch, size_t* width, const char* null_text) {
+  if (!b || !dev_ptr || !pitch || !width) return fail(MYO_E_ARG, null_text);
+  DevBuf d;
+  const int rc = family(b, which, &d);
+  return rc ? rc : buf_out(d, dev_ptr, pitch, width);
+}
+static int buf_read(BufFamily family, const myo_batch* b, int which, void* host, size_t nbytes, const char* mismatch) {
+  DevBuf d; int rc;
+  if ((rc = family(b, which, &d)) || (rc = buf_check(b, d, host, nbytes, mismatch))) return rc;
+  return copy_to_host(b->model->device, host, d.p, nbytes);
+}
+
 // What differs per task on the host, indexed by task id (task_hooks in myo_host_tasks.h); a task's record lives next to its kernel.
 struct TaskHooks {
   int (*configure)(myo_batch*, const myo_task_config*);                    // argument and model checks, obs_dim, task-specific TaskDev fields; null: no observation row,

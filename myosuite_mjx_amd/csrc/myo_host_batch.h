@@ -289,44 +289,35 @@ static_assert(N_FIELDS == MYO_F_CFRC + 1 && field_rows_in_id_order(), "field_row
 
 static const FieldRow* field_row(int f) { return f >= 0 && f < N_FIELDS ? &field_rows[f] : nullptr; }
 // pointer and width of a field as they are now (a write looks them up again after it has started an override)
-static int field_info(const myo_batch* b, const FieldRow* row, void** p, size_t* width) {
+static int field_info(const myo_batch* b, const FieldRow* row, DevBuf* d) {
   if (!row) return fail(MYO_E_ARG, "unknown field");
-  *p = row->ptr(b);
-  if (!*p && row->absent) return fail(MYO_E_ARG, row->absent);
-  *width = row->width(b);
+  void* p = row->ptr(b);
+  if (!p && row->absent) return fail(MYO_E_ARG, row->absent);
+  *d = {p, row->width(b), 4};
   return MYO_OK;
 }
 
 static int batch_field(myo_batch* b, int field, void** dev_ptr, size_t* pitch, size_t* width) {
   const FieldRow* row = field_row(field);
-  int rc;
-  if ((row && row->ov && (rc = override_start(b, *row->ov))) || (rc = field_info(b, row, dev_ptr, width))) return rc;
-  *pitch = *width;
-  return MYO_OK;
+  DevBuf d; int rc;
+  if ((row && row->ov && (rc = override_start(b, *row->ov))) || (rc = field_info(b, row, &d))) return rc;
+  return buf_out(d, dev_ptr, pitch, width);
 }
 static int batch_read(myo_batch* b, int field, void* host, size_t nbytes) {
   const FieldRow* row = field_row(field);
-  void* p; size_t width; int rc;
-  if ((rc = field_info(b, row, &p, &width))) return rc;
-  if (nbytes != (size_t)b->db.B * width * 4) return fail(MYO_E_ARG, "myo_batch_read: size mismatch");
-  if (row->ov && !(b->*row->ov->on)) return row->ov->fill_default(b, field, (float*)host, b->db.B, width);   // not started: a read starts nothing
-  HIPCHK(hipSetDevice(b->model->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(host, p, nbytes, hipMemcpyDeviceToHost));
-  return MYO_OK;
+  DevBuf d; int rc;
+  if ((rc = field_info(b, row, &d)) || (rc = buf_check(b, d, host, nbytes, "myo_batch_read: size mismatch"))) return rc;
+  if (row->ov && !(b->*row->ov->on)) return row->ov->fill_default(b, field, (float*)host, b->db.B, d.width);   // not started: a read starts nothing
+  return copy_to_host(b->model->device, host, d.p, nbytes);
 }
 static int batch_write(myo_batch* b, int field, const void* host, size_t nbytes) {
   const FieldRow* row = field_row(field);
-  void* p; size_t width; int rc;
+  DevBuf d; int rc;
   if (row && row->read_only) return fail(MYO_E_ARG, row->read_only);
-  if ((rc = field_info(b, row, &p, &width))) return rc;
-  if (nbytes != (size_t)b->db.B * width * 4) return fail(MYO_E_ARG, "myo_batch_write: size mismatch");
+  if ((rc = field_info(b, row, &d)) || (rc = buf_check(b, d, host, nbytes, "myo_batch_write: size mismatch"))) return rc;
   // a rejected write starts nothing; the start allocates, so the pointer is looked up again
-  if (row->ov && ((rc = row->ov->validate(b, field, (const float*)host, b->db.B, width)) || (rc = override_start(b, *row->ov)) || (rc = field_info(b, row, &p, &width)))) return rc;
-  HIPCHK(hipSetDevice(b->model->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(p, host, nbytes, hipMemcpyHostToDevice));
-  return MYO_OK;
+  if (row->ov && ((rc = row->ov->validate(b, field, (const float*)host, b->db.B, d.width)) || (rc = override_start(b, *row->ov)) || (rc = field_info(b, row, &d)))) return rc;
+  return copy_to_device(b->model->device, d.p, host, nbytes);
 }
 
 #endif  // MYO_HOST_BATCH_H

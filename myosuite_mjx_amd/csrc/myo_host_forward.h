@@ -71,26 +71,21 @@ int myo_model_forward_dims(const myo_model* m, int* nbody, int* nsite, int* ngeo
   return MYO_OK;
 }
 
-int myo_forward_buffer(myo_batch* b, int which, void** dev_ptr, size_t* pitch, size_t* width) {
-  if (!b || !dev_ptr || !pitch || !width) return fail(MYO_E_ARG, "myo_forward_buffer: null");
+static int fwd_buffer(const myo_batch* b, int which, DevBuf* d) {
   if (which < 0 || which >= MYO_FWD_COUNT) return fail(MYO_E_ARG, "myo_forward_buffer: unknown buffer id");
   if (!b->fwd_on) return fail(MYO_E_ARG, "myo_forward_buffer: no forward pass has run on this batch (myo_forward)");
   if (which == MYO_FWD_SITE_XMAT && !b->model->fwd_site_mat) return fail(MYO_E_UNSUPPORTED, "MYO_FWD_SITE_XMAT: the model blob carries no site_quat");
-  *dev_ptr = b->fwd_buf[which];
-  *pitch = *width = fwd_width(b->model, which);
+  *d = {b->fwd_buf[which], (size_t)fwd_width(b->model, which), 4};
   return MYO_OK;
+}
+
+int myo_forward_buffer(myo_batch* b, int which, void** dev_ptr, size_t* pitch, size_t* width) {
+  return buf_lookup(fwd_buffer, b, which, dev_ptr, pitch, width, "myo_forward_buffer: null");
 }
 
 int myo_forward_read(myo_batch* b, int which, void* host, size_t nbytes) {
   if (!b || !host) return fail(MYO_E_ARG, "myo_forward_read: null");
-  void* p; size_t pitch, width;
-  const int rc = myo_forward_buffer(b, which, &p, &pitch, &width);
-  if (rc) return rc;
-  if (nbytes != (size_t)b->db.B * width * 4) return fail(MYO_E_ARG, "myo_forward_read: size mismatch");
-  HIPCHK(hipSetDevice(b->model->device));
-  HIPCHK(hipDeviceSynchronize());
-  if (nbytes) HIPCHK(hipMemcpy(host, p, nbytes, hipMemcpyDeviceToHost));
-  return MYO_OK;
+  return buf_read(fwd_buffer, b, which, host, nbytes, "myo_forward_read: size mismatch");
 }
 
 int myo_forward_host_tables(const void* blobv, size_t nbytes, int table, double* out, size_t capacity, int* n) {

@@ -146,13 +146,13 @@ static int obj_enable(myo_batch* b, const int* geoms, int ng, const int* bodies,
 }
 
 // pointer and width of table `which`
-static int obj_table(const myo_batch* b, int which, float** p, size_t* width) {
+static int obj_table(const myo_batch* b, int which, DevBuf* t) {
   if (which < 0 || which >= MYO_OBJ_COUNT) return fail(MYO_E_ARG, "object parameters: unknown table id");
   if (!b->obj_on) return fail(MYO_E_ARG, "object parameters: absent (the batch is not enabled, myo_objects_enable)");
   const DevBatch& d = b->db;
-  *p = which == MYO_OBJ_SIZE ? d.obj_size : (which == MYO_OBJ_POS ? d.obj_pos : (which == MYO_OBJ_FRICTION ? d.obj_fric : d.obj_mass));
-  *width = which == MYO_OBJ_MASS ? (size_t)d.obj_nb : 3 * (size_t)d.obj_ng;
-  if (!*p) return fail(MYO_E_ARG, which == MYO_OBJ_MASS ? "object parameters: no body is selected" : "object parameters: no geom is selected");
+  float* p = which == MYO_OBJ_SIZE ? d.obj_size : (which == MYO_OBJ_POS ? d.obj_pos : (which == MYO_OBJ_FRICTION ? d.obj_fric : d.obj_mass));
+  if (!p) return fail(MYO_E_ARG, which == MYO_OBJ_MASS ? "object parameters: no body is selected" : "object parameters: no geom is selected");
+  *t = {p, which == MYO_OBJ_MASS ? (size_t)d.obj_nb : 3 * (size_t)d.obj_ng, 4};
   return MYO_OK;
 }
 
@@ -171,38 +171,24 @@ int myo_objects_count(const myo_batch* b, int* ngeom, int* nbody) {
 }
 
 int myo_objects_table(myo_batch* b, int which, void** dev_ptr, size_t* pitch, size_t* width) {
-  if (!b || !dev_ptr || !pitch || !width) return fail(MYO_E_ARG, "myo_objects_table: null");
-  float* p;
-  if (const int rc = obj_table(b, which, &p, width)) return rc;
-  *dev_ptr = p; *pitch = *width;
-  return MYO_OK;
+  return buf_lookup(obj_table, b, which, dev_ptr, pitch, width, "myo_objects_table: null");
 }
 
 int myo_objects_read(myo_batch* b, int which, void* host, size_t nbytes) {
   if (!b || !host) return fail(MYO_E_ARG, "myo_objects_read: null");
-  float* p; size_t width;
-  if (const int rc = obj_table(b, which, &p, &width)) return rc;
-  if (nbytes != (size_t)b->db.B * width * 4) return fail(MYO_E_ARG, "myo_objects_read: size mismatch");
-  HIPCHK(hipSetDevice(b->model->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(host, p, nbytes, hipMemcpyDeviceToHost));
-  return MYO_OK;
+  return buf_read(obj_table, b, which, host, nbytes, "myo_objects_read: size mismatch");
 }
 
 int myo_objects_write(myo_batch* b, int which, const void* host, size_t nbytes) {
   if (!b || !host) return fail(MYO_E_ARG, "myo_objects_write: null");
-  float* p; size_t width;
-  if (const int rc = obj_table(b, which, &p, &width)) return rc;
-  if (nbytes != (size_t)b->db.B * width * 4) return fail(MYO_E_ARG, "myo_objects_write: size mismatch");
+  DevBuf t; int rc;
+  if ((rc = obj_table(b, which, &t)) || (rc = buf_check(b, t, host, nbytes, "myo_objects_write: size mismatch"))) return rc;
   const float* h = (const float*)host;
-  for (size_t i = 0; i < (size_t)b->db.B * width; i++) {
+  for (size_t i = 0; i < (size_t)b->db.B * t.width; i++) {
     if (!std::isfinite(h[i])) return fail(MYO_E_ARG, "myo_objects_write: values must be finite");
     if (which != MYO_OBJ_POS && !(h[i] >= 0.f)) return fail(MYO_E_ARG, "myo_objects_write: sizes, frictions and masses must be >= 0");
   }
-  HIPCHK(hipSetDevice(b->model->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(p, host, nbytes, hipMemcpyHostToDevice));
-  return MYO_OK;
+  return copy_to_device(b->model->device, t.p, host, nbytes);
 }
 
 int myo_objects_set_draws(myo_batch* b, int ndraw, int n, const float* base, const float* scale, const int* draw) {
@@ -226,9 +212,7 @@ int myo_objects_set_draws(myo_batch* b, int ndraw, int n, const float* base, con
   HIPCHK(hipSetDevice(b->model->device));
   int rc;
   if (!b->d_obj_draw && ((rc = b->pool.alloc(&b->d_obj_draw, 2 * (size_t)np * 4)) || (rc = b->pool.alloc(&b->d_obj_draw_k, (size_t)np * 4)))) return rc;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(b->d_obj_draw, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(b->d_obj_draw_k, draw, (size_t)np * 4, hipMemcpyHostToDevice));
+  if ((rc = copy_to_device(b->model->device, b->d_obj_draw, tab.data(), tab.size() * 4)) || (rc = copy_to_device(b->model->device, b->d_obj_draw_k, draw, (size_t)np * 4))) return rc;
   d.obj_draw = b->d_obj_draw; d.obj_draw_k = b->d_obj_draw_k;
   return MYO_OK;
 }

@@ -95,8 +95,7 @@ static int rewards_enable(myo_batch* b, const float* w, int nw, int mode) {
     if ((rc = b->pool.alloc(&row, (size_t)d.B * c.n * 4)) || (rc = b->pool.alloc(&wd, (size_t)nw * 4))) return rc;
     d.rwd = row; d.rwd_w = wd; d.rwd_n = c.n;
   }
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy((void*)d.rwd_w, w, (size_t)nw * 4, hipMemcpyHostToDevice));
+  if ((rc = copy_to_device(b->model->device, (void*)d.rwd_w, w, (size_t)nw * 4))) return rc;
   d.rwd_sparse = mode == MYO_RWD_SPARSE;
   return MYO_OK;
 }
@@ -129,43 +128,36 @@ const char* myo_batch_rwd_name(const myo_batch* b, int col) {
 int myo_batch_enable_rewards(myo_batch* b, const float* weights, int nweights, int mode) {
   return b ? rewards_enable(b, weights, nweights, mode) : fail(MYO_E_ARG, "myo_batch_enable_rewards: null");
 }
-int myo_batch_rwd_row(myo_batch* b, void** dev_ptr, size_t* pitch, size_t* width) {
-  if (!b || !dev_ptr || !pitch || !width) return fail(MYO_E_ARG, "myo_batch_rwd_row: null");
+// the two families' refusals ("host copy" is the size error of both reads)
+static int rwd_buf(const myo_batch* b, int, DevBuf* d) {
   if (!b->db.rwd) return fail(MYO_E_ARG, "reward terms are not enabled (myo_batch_enable_rewards)");
-  *dev_ptr = b->db.rwd; *pitch = *width = (size_t)b->db.rwd_n;
+  *d = {b->db.rwd, (size_t)b->db.rwd_n, 4};
   return MYO_OK;
 }
-static int host_copy(myo_batch* b, const void* dev, void* host, size_t nbytes, size_t want) {
-  if (!host || nbytes != want) return fail(MYO_E_ARG, "host copy: size mismatch");
-  HIPCHK(hipSetDevice(b->model->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(host, dev, nbytes, hipMemcpyDeviceToHost));
-  return MYO_OK;
-}
-int myo_batch_rwd_read(myo_batch* b, void* host, size_t nbytes) {
-  void* p; size_t pitch, width;
-  const int rc = myo_batch_rwd_row(b, &p, &pitch, &width);
-  return rc ? rc : host_copy(b, p, host, nbytes, (size_t)b->db.B * width * 4);
-}
-int myo_batch_enable_episode_stats(myo_batch* b) { return b ? episode_enable(b) : fail(MYO_E_ARG, "myo_batch_enable_episode_stats: null"); }
-int myo_batch_episode_buffer(myo_batch* b, int which, void** dev_ptr, size_t* pitch, size_t* width) {
-  if (!b || !dev_ptr || !pitch || !width) return fail(MYO_E_ARG, "myo_batch_episode_buffer: null");
+static int episode_buf(const myo_batch* b, int which, DevBuf* d) {
   const myo_episode* ep = &b->episode;
   if (!ep->run) return fail(MYO_E_ARG, "episode statistics are not enabled (myo_batch_enable_episode_stats)");
   switch (which) {
-    case MYO_EP_RUNNING: *dev_ptr = ep->run; *width = 4; break;
-    case MYO_EP_LAST: *dev_ptr = ep->last; *width = 4; break;
-    case MYO_EP_FINISHED: *dev_ptr = ep->finished; *width = 1; break;
-    case MYO_EP_COUNT: *dev_ptr = ep->count; *width = 1; break;
+    case MYO_EP_RUNNING: *d = {ep->run, 4, 4}; break;
+    case MYO_EP_LAST: *d = {ep->last, 4, 4}; break;
+    case MYO_EP_FINISHED: *d = {ep->finished, 1, 1}; break;
+    case MYO_EP_COUNT: *d = {ep->count, 1, 4}; break;
     default: return fail(MYO_E_ARG, "myo_batch_episode_buffer: unknown buffer");
   }
-  *pitch = *width;
   return MYO_OK;
 }
+int myo_batch_rwd_row(myo_batch* b, void** dev_ptr, size_t* pitch, size_t* width) {
+  return buf_lookup(rwd_buf, b, 0, dev_ptr, pitch, width, "myo_batch_rwd_row: null");
+}
+int myo_batch_rwd_read(myo_batch* b, void* host, size_t nbytes) {
+  return b ? buf_read(rwd_buf, b, 0, host, nbytes, "host copy: size mismatch") : fail(MYO_E_ARG, "myo_batch_rwd_row: null");
+}
+int myo_batch_enable_episode_stats(myo_batch* b) { return b ? episode_enable(b) : fail(MYO_E_ARG, "myo_batch_enable_episode_stats: null"); }
+int myo_batch_episode_buffer(myo_batch* b, int which, void** dev_ptr, size_t* pitch, size_t* width) {
+  return buf_lookup(episode_buf, b, which, dev_ptr, pitch, width, "myo_batch_episode_buffer: null");
+}
 int myo_batch_episode_read(myo_batch* b, int which, void* host, size_t nbytes) {
-  void* p; size_t pitch, width;
-  const int rc = myo_batch_episode_buffer(b, which, &p, &pitch, &width);
-  return rc ? rc : host_copy(b, p, host, nbytes, (size_t)b->db.B * width * (which == MYO_EP_FINISHED ? 1 : 4));
+  return b ? buf_read(episode_buf, b, which, host, nbytes, "host copy: size mismatch") : fail(MYO_E_ARG, "myo_batch_episode_buffer: null");
 }
 int myo_episode_update(myo_batch* b, int max_episode_steps, void* stream) {
   if (!b || max_episode_steps <= 0) return fail(MYO_E_ARG, "myo_episode_update: bad arguments");

@@ -36,9 +36,7 @@ static int walk_configure(myo_batch* b, const myo_walk_config* c) {
   if (c->terrain != MYO_TERRAIN_NONE && !(m->dw.hf.on && m->dw.hf.nrow == 100 && m->dw.hf.ncol == 100))
     return fail(MYO_E_UNSUPPORTED, "terrain walk needs a model with a colliding 100 x 100 height field");
   if (c->terrain < 0 || c->terrain > MYO_TERRAIN_STAIRS) return fail(MYO_E_ARG, "walk task: bad terrain kind");
-  HIPCHK(hipSetDevice(m->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(b->d_walk, &w, sizeof w, hipMemcpyHostToDevice));
+  if (const int rc = copy_to_device(m->device, b->d_walk, &w, sizeof w)) return rc;
   HIPCHK(hipMemcpy(b->d_init, c->init_qpos, (size_t)nq * 4, hipMemcpyHostToDevice));
   if (c->init_qvel) HIPCHK(hipMemcpy(b->d_initv, c->init_qvel, (size_t)nv * 4, hipMemcpyHostToDevice));
   TaskDev& T = b->task;

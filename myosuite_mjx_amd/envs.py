@@ -17,7 +17,6 @@ import numpy as np
 
 from . import capi, objects, rewards, tasks, track
 from . import model as _model
-from .capi import _DevArray  # noqa: F401  (sim.py takes it from here)
 
 # ASL pose table (envs/myo/myobase/__init__.py:326-376): target joint vectors of myoHandPose{k}Fixed-v0;
 # the per-joint min/max over the ten rows is the target range of myoHandPoseRandom-v0 (:396-399)
@@ -459,32 +458,19 @@ class BatchedMyoEnv(capi.FieldViews):
             raise AttributeError(f"{self.id}: made without rwd_dict=True")
         return {k: float(w) for k, w in zip(self.rwd_keys, self._rwd[1]) if w != 0}
 
-    def _dev_view(self, name, ptr, shape, typestr):
-        if name not in self._views:
-            self._views[name] = self._torch.as_tensor(capi._DevArray(ptr, shape, typestr, self.batch), device=f"cuda:{self.device}")
-        return self._views[name]
-
     @property
     def rwd_terms(self):
         """[num_envs, len(rwd_keys)] term row of the last step: a torch view of the library's buffer (no copy); as_torch=False: a numpy copy."""
         if not self.rwd_dict:
             raise AttributeError(f"{self.id}: made without rwd_dict=True")
-        if self._torch is None:
-            return self.batch.read_rwd()
-        return self._dev_view("rwd", self.batch.rwd_row_ptr()[0], (self.num_envs, len(self.rwd_keys)), "<f4")
-
-    def _episode_buffer(self, which):
-        if self._torch is None:
-            return self.batch.read_episode(which)
-        shape = (self.num_envs, 4) if which in (capi.EP_RUNNING, capi.EP_LAST) else (self.num_envs,)
-        return self._dev_view(("episode", which), self.batch.episode_ptr(which)[0], shape, {capi.EP_FINISHED: "|u1", capi.EP_COUNT: "<i4"}.get(which, "<f4"))
+        return self.view(None, "rwd")
 
     @property
     def episode_count(self):
         """[num_envs] int32 episodes ended so far per env (episode_stats=True)."""
         if not self.episode_stats:
             raise AttributeError(f"{self.id}: made without episode_stats=True")
-        return self._episode_buffer(capi.EP_COUNT)
+        return self.view(capi.EP_COUNT, "episode")
 
     def _reward_info(self, info):
         """info["rwd_dict"] / ["rwd_dense"] / ["rwd_sparse"] (env_base.py:559-570) from the term row: one column view per key."""
@@ -494,7 +480,7 @@ class BatchedMyoEnv(capi.FieldViews):
 
     def _episode_info(self, info):
         """info["episode"]: which envs' episodes the step ended and the statistics of each env's last finished episode."""
-        last, fin = self._episode_buffer(capi.EP_LAST), self._episode_buffer(capi.EP_FINISHED)
+        last, fin = self.view(capi.EP_LAST, "episode"), self.view(capi.EP_FINISHED, "episode")
         i32 = (lambda x: x.to(self._torch.int32)) if self._torch is not None else (lambda x: x.astype(np.int32))
         info["episode"] = {"finished": fin > 0, "r": last[:, 0], "r_sparse": last[:, 1], "l": i32(last[:, 2]), "solved": i32(last[:, 3])}
 
@@ -522,17 +508,12 @@ class BatchedMyoEnv(capi.FieldViews):
             self.batch.step(self.batch.field_ptr(capi.F_ACTION)[0], self.actmap, self.frame_skip, s)
         if not self._obs_in_step:
             self.batch.obs(s)
-        if self.as_torch:
-            reward = self.view(capi.F_REWARD)[:, 0].clone()
-            done = self.view(capi.F_DONE)[:, 0] > 0
-            elapsed = self.view(capi.F_ELAPSED)[:, 0]
-            truncated = (elapsed >= self.max_episode_steps) & ~done
-            solved = self.view(capi.F_SOLVED)[:, 0] > 0
-        else:
-            reward = self.batch.read(capi.F_REWARD)[:, 0]
-            done = self.batch.read(capi.F_DONE)[:, 0] > 0
-            truncated = (self.batch.read(capi.F_ELAPSED)[:, 0] >= self.max_episode_steps) & ~done
-            solved = self.batch.read(capi.F_SOLVED)[:, 0] > 0
+        reward = self.view(capi.F_REWARD)[:, 0]
+        if self.as_torch:          # (a view: the auto-reset's observation pass writes the row again)
+            reward = reward.clone()
+        done = self.view(capi.F_DONE)[:, 0] > 0
+        truncated = (self.view(capi.F_ELAPSED)[:, 0] >= self.max_episode_steps) & ~done
+        solved = self.view(capi.F_SOLVED)[:, 0] > 0
         info = {"solved": solved}
         if self.rwd_dict:
             self._reward_info(info)

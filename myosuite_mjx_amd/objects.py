@@ -206,14 +206,10 @@ class ObjectParams:
         return (self._batch.B, self.nb) if which == OBJ_MASS else (self._batch.B, self.ng, 3)
 
     def table_ptr(self, which):
-        p, pitch, width = C.c_void_p(), C.c_size_t(), C.c_size_t()
-        capi._chk(lib().myo_objects_table(self._batch.h, int(which), C.byref(p), C.byref(pitch), C.byref(width)))
-        return p.value, pitch.value, width.value
+        return capi.buffer_lookup(lib().myo_objects_table, self._batch.h, int(which))
 
     def read(self, which):
-        out = np.empty(self._shape(which), np.float32)
-        capi._chk(lib().myo_objects_read(self._batch.h, int(which), out.ctypes.data, out.nbytes))
-        return out
+        return capi.host_read(lib().myo_objects_read, self._batch.h, int(which), shape=self._shape(which), dtype=np.float32)
 
     def write(self, which, value):
         a = np.ascontiguousarray(np.broadcast_to(np.asarray(value, np.float32), self._shape(which)))
@@ -223,8 +219,7 @@ class ObjectParams:
         if self._torch is None:
             return self.read(which)
         if which not in self._views:
-            arr = capi._DevArray(self.table_ptr(which)[0], self._shape(which), "<f4", self._batch)
-            self._views[which] = self._torch.as_tensor(arr, device=f"cuda:{self._device}")
+            self._views[which] = capi.device_view(self._torch, self.table_ptr(which)[0], self._shape(which), np.float32, self._batch, self._device)
         return self._views[which]
 
     def _set(self, which, value):

@@ -308,7 +308,7 @@ class Learner:
                         p, n = C.c_void_p(), C.c_size_t()
                         capi._chk(L.myo_ppo_learner_tensor(self.h, net, layer, what, self.WHICH[which], C.byref(p), C.byref(n)))
                         assert n.value == int(np.prod(shape))
-                        dst.append(torch.as_tensor(capi._DevArray(p.value, shape, "<f4", self), device=f"cuda:{self.device}"))
+                        dst.append(capi.device_view(torch, p.value, shape, np.float32, self, self.device))
                     nin = nout
                 out += [ws, bs]
             self._views[which] = tuple(out)

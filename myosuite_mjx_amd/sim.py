@@ -119,14 +119,11 @@ class _DeviceData:
 
     def __init__(self, batch, B, device, mj=None, sensors=False):
         import torch
-        from .envs import _DevArray
         self._keep = batch
         T = _dev_tensor_type()
 
         def view(field):
-            ptr, pitch, width = batch.field_ptr(field)
-            ts = "<i4" if field in capi.INT_FIELDS else "<f4"
-            return torch.as_tensor(_DevArray(ptr, (B, width), ts, batch), device=f"cuda:{device}").as_subclass(T)
+            return batch.buffer_view(torch, device, "field", field).as_subclass(T)
         self.qpos, self.qvel, self.act, self.ctrl = view(capi.F_QPOS), view(capi.F_QVEL), view(capi.F_ACT), view(capi.F_CTRL)
         self.time, self.qacc, self.qacc_warmstart = view(capi.F_TIME), view(capi.F_QACC), view(capi.F_WARMSTART)
         self.actuator_length, self.actuator_force = view(capi.F_TENLEN), view(capi.F_ACTFORCE)
@@ -162,6 +159,7 @@ class HipSimScene:
         self.num_envs = int(num_envs)
         self.device = device
         self.as_torch = as_torch
+        self._torch = __import__("torch") if as_torch else None
         self.sim = self._load_simulation(model_handle, device)
         self.model = self.sim.mj
         self.sensors = bool(sensors)
@@ -262,11 +260,7 @@ class HipSimScene:
         if self.sensors:
             self.data.sensordata[:] = b.read(capi.F_SENSORDATA)
 
-    def _stream(self):
-        if self.as_torch:
-            import torch
-            return torch.cuda.current_stream(self.device).cuda_stream
-        return None
+    _stream = capi.FieldViews._stream      # torch's current stream on self.device (None without torch)
 
     def advance(self, substeps: int = 1, render: bool = False):
         if self.as_torch:                      # device-resident: the controls and the state are already where the kernel reads them
@@ -308,10 +302,7 @@ class HipSimScene:
         self._batch.forward(self._stream())
         self._flags_stale = True
         if self._fwd is None:
-            torch = None
-            if self.as_torch:
-                import torch
-            self._fwd = capi.ForwardRecord(self._batch, torch, self.device)
+            self._fwd = capi.ForwardRecord(self._batch, self._torch, self.device)
         else:
             self._fwd.refresh()
         for k in ("xpos", "xmat", "xipos", "site_xpos", "site_xmat", "geom_xpos", "geom_xmat", "ncon", "contact", "body_xpos", "body_xmat"):

@@ -180,6 +180,49 @@ def test_capi_constants_equal_the_header_enums():
     assert sorted(capi.INT_FIELDS) == sorted(enums[n] for n, i32 in documented if i32) and capi.F_FLAGS in capi.INT_FIELDS
 
 
+def _documented_buffers(header, prefix):
+    """{id: (dtype name, elements per item)} from the comments of an `enum { MYO_EP_* / MYO_FWD_* }`: `/* [B][n][3] ...`, `/* [B] uint8: ...`;
+    a comment that names no type documents float32, a [B] one an item of no dimensions."""
+    hdr = open(os.path.join(ROOT, "include", header)).read()
+    enums = _header_enums(hdr)
+    out = {}
+    for name, dims, dtype in re.findall(r"\b(%s[A-Z_]+) = \d+,?\s*/\*\s*((?:\[[^\]]*\])+):?\s*(float32|int32|uint8)?" % prefix, hdr):
+        dims = re.findall(r"\[([^\]]*)\]", dims)
+        assert dims[0] == "B", name
+        out[enums[name]] = (dtype or "float32", int(dims[-1]) if len(dims) > 1 else 0)
+    return out, enums
+
+
+def test_buffer_family_tables_say_what_the_headers_say():
+    """capi's one statement of element type and per-env item shape per episode and forward buffer, against the comments of
+    include/myo_hip_rewards.h and include/myo_hip_forward.h: uint8 for MYO_EP_FINISHED, int32 for MYO_EP_COUNT and MYO_FWD_NCON, float32 for
+    the rest, [4] / [3] / [9] / [16] elements per item ([B] alone: a scalar per env), 16 words per contact record; what the family table
+    hands out is that statement, and every dtype's typestr is one of the three a view can have."""
+    from myosuite_mjx_amd import capi
+    ep, ep_enums = _documented_buffers("myo_hip_rewards.h", "MYO_EP_")
+    fwd, fwd_enums = _documented_buffers("myo_hip_forward.h", "MYO_FWD_")
+    assert ep == {0: ("float32", 4), 1: ("float32", 4), 2: ("uint8", 0), 3: ("int32", 0)}                      # (the parser parses)
+    assert len(fwd) == fwd_enums["MYO_FWD_COUNT"] == capi.FWD_COUNT == 9 and fwd[7] == ("int32", 0) and fwd[8] == ("float32", 16) and fwd[1] == ("float32", 9)
+    for n, v in list(ep_enums.items()) + list(fwd_enums.items()):
+        if n.startswith(("MYO_EP_", "MYO_FWD_")):
+            assert getattr(capi, n[4:]) == v, n
+    assert (capi.EP_FINISHED, capi.EP_COUNT, capi.FWD_NCON, capi.FWD_CONTACT) == (2, 3, 7, 8)
+    assert capi.FWD_CONTACT_WORDS == 16 and "#define MYO_FWD_CONTACT_WORDS 16" in open(os.path.join(ROOT, "include", "myo_hip_forward.h")).read()
+    for family, doc, dtypes, items in (("episode", ep, capi._EP_DTYPE, capi._EP_ITEM), ("forward", fwd, capi._FWD_DTYPE, capi._FWD_ITEM)):
+        assert sorted(dtypes) == sorted(items) == sorted(doc), family
+        for i, (dtype, n) in doc.items():
+            assert np.dtype(dtypes[i]) == np.dtype(dtype) and int(np.prod(items[i])) == (n or 1) and (items[i] == ()) == (n == 0), (family, i)
+            assert np.dtype(dtypes[i]).str in ("<f4", "<i4", "|u1"), (family, i)
+            got_dtype, shape = capi.FAMILIES[family][2](3, i, lambda: 5 * (n or 1))                           # B = 3, rows of 5 items
+            assert got_dtype is dtypes[i], (family, i)
+            assert shape == ((3, *items[i]) if family == "episode" else ((3, 5, *items[i]) if items[i] else (3,))), (family, i, shape)
+    assert capi._FWD_ITEM[capi.FWD_CONTACT] == (16,) and capi._FWD_ITEM[capi.FWD_XMAT] == (3, 3) and capi._EP_ITEM[capi.EP_LAST] == (4,)
+    for f in range(capi.F_CFRC + 1):                                                                           # fields: int32 for INT_FIELDS, else float32
+        dtype, shape = capi.FAMILIES["field"][2](3, f, lambda: 7)
+        assert dtype is (np.int32 if f in capi.INT_FIELDS else np.float32) and shape == (3, 7) and np.dtype(dtype).str in ("<f4", "<i4")
+    assert capi.FAMILIES["rwd"][2](3, None, lambda: 9) == (np.float32, (3, 9))
+
+
 # capi name, value, and the text the header must spell it with (None: its place in a list gives the value).  Ids are appended, never
 # renumbered: a feature that adds a field or a task adds its row at the end of its block, and changes no other row.
 ABI_PINS = (

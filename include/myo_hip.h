@@ -413,6 +413,7 @@ int myo_policy_act(myo_policy*, const float* obs_dev, int B, float* action_dev, 
 
 #include "myo_hip_sensors.h"
 #include "myo_hip_rewards.h"
+#include "myo_hip_obs.h"
 #include "myo_hip_ppo.h"
 
 #ifdef __cplusplus

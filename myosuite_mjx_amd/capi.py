@@ -31,6 +31,8 @@ RWD_DENSE, RWD_SPARSE = 0, 1
 EP_RUNNING, EP_LAST, EP_FINISHED, EP_COUNT = range(4)
 _EP_DTYPE = {EP_RUNNING: np.float32, EP_LAST: np.float32, EP_FINISHED: np.uint8, EP_COUNT: np.int32}
 _EP_ITEM = {EP_RUNNING: (4,), EP_LAST: (4,), EP_FINISHED: (), EP_COUNT: ()}
+# observation terms (include/myo_hip_obs.h): the three rows of a batch with the terms on
+OBS_TERMS, OBS_SELECTED, OBS_PROPRIO = range(3)
 # forward pass (include/myo_hip_forward.h): buffer ids, words of a contact record, and the per-item shape of each buffer
 FWD_XPOS, FWD_XMAT, FWD_XIPOS, FWD_SITE_XPOS, FWD_SITE_XMAT, FWD_GEOM_XPOS, FWD_GEOM_XMAT, FWD_NCON, FWD_CONTACT = range(9)
 FWD_COUNT = 9
@@ -178,6 +180,16 @@ SIGNATURES = {
     "myo_ppo_learner_tensor": (_I, [_V, _I, _I, _I, _I, _pV, C.POINTER(_SZ)]),
 }
 
+# include/myo_hip_obs.h, in a table of its own: SIGNATURES stays the table of the five core headers.  lib() applies both
+OBS_SIGNATURES = {
+    "myo_batch_obs_nterm": (_I, [_V]),
+    "myo_batch_obs_term_name": (_STR, [_V, _I]),
+    "myo_batch_obs_term_width": (_I, [_V, _I]),
+    "myo_batch_enable_obs_terms": (_I, [_V, _pI, _I, _pI, _I]),
+    "myo_batch_obs_buffer": (_I, [_V, _I, *_BUF]),
+    "myo_batch_obs_read": (_I, [_V, _I, _V, _SZ]),
+}
+
 
 # -mllvm -disable-machine-licm: the post-ISel loop-invariant code motion hoists constant materialisations (polynomial coefficients, masks) out
 # of the 10-substep loop into the kernel prologue, where a dozen of them stay live in VGPRs for the whole kernel and push other values into
@@ -251,7 +263,7 @@ def lib():
             except ImportError:
                 pass
         L = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in SIGNATURES.items():
+        for name, (restype, argtypes) in {**SIGNATURES, **OBS_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = L
@@ -310,6 +322,7 @@ FAMILIES = {
     "field": ("myo_batch_field", "myo_batch_read", lambda B, f, width: (np.int32 if f in INT_FIELDS else np.float32, (B, width()))),
     "rwd": ("myo_batch_rwd_row", "myo_batch_rwd_read", lambda B, _, width: (np.float32, (B, width()))),
     "episode": ("myo_batch_episode_buffer", "myo_batch_episode_read", lambda B, which, width: (_EP_DTYPE[which], (B, *_EP_ITEM[which]))),
+    "obs": ("myo_batch_obs_buffer", "myo_batch_obs_read", lambda B, _, width: (np.float32, (B, width()))),
     "forward": ("myo_forward_buffer", "myo_forward_read", lambda B, which, width: (
         _FWD_DTYPE[which], (B, width() // int(np.prod(_FWD_ITEM[which])), *_FWD_ITEM[which]) if _FWD_ITEM[which] else (B,))),
 }
@@ -496,6 +509,18 @@ class HipBatch:
 
     def episode_clear(self, stream=None):
         _chk(lib().myo_episode_clear(self.h, stream))
+
+    # -- observation terms (include/myo_hip_obs.h) --
+    def obs_terms(self):
+        """((name, width), ...) of the configured task's term table, in the order of the reference's obs_dict (empty: the task has none)."""
+        n = lib().myo_batch_obs_nterm(self.h)
+        return tuple((lib().myo_batch_obs_term_name(self.h, k).decode(), int(lib().myo_batch_obs_term_width(self.h, k))) for k in range(n))
+
+    def enable_obs_terms(self, obs_terms, proprio_terms=()):
+        """Turn the rows on: OBS_TERMS (every term), OBS_SELECTED (the concatenation of the terms `obs_terms`, indices into the table) and,
+        with proprio_terms, OBS_PROPRIO.  Once per batch, after the task was configured; MyoError with the library's reason otherwise."""
+        o, p = np.ascontiguousarray(obs_terms, np.int32).ravel(), np.ascontiguousarray(proprio_terms, np.int32).ravel()
+        _chk(lib().myo_batch_enable_obs_terms(self.h, _ptr(o, C.c_int), o.size, _ptr(p, C.c_int) if p.size else None, p.size))
 
     def _set_range(self, field, width, lo, hi):
         lo, hi = (np.broadcast_to(np.asarray(a, np.float32), (self.B, width)) for a in (lo, hi))

@@ -20,6 +20,7 @@
 //                       attributes once per device (set_lds_limit), myo_model, myo_batch, the device buffers handed to callers (DevBuf, buf_lookup,
 //                       buf_read, the blocking copies), the per-task hook record (TaskHooks) and its launchers
 //   myo_rewards.h       reward-term rows and episode statistics (include/myo_hip_rewards.h): column table per task, walk term kernel, statistics kernel, entry points
+//   myo_obs_terms.h     observation-term rows (include/myo_hip_obs.h): term table per task, column program, obs_terms_kernel, entry points
 //   myo_host_tasks.h    the task table: includes the task files below, task_hooks, launch_obs
 //   myo_task_util.h     what the task files share: link-chain walk, row prologue, site gather, activation term, the common configure checks
 //   myo_task_<name>.h   pose, reach, walk, stand, hold, keyturn, pen, baoding, die, myodm: a task's observation body, its configure and its hook record
@@ -53,6 +54,7 @@
 #include "myo_host.h"
 #include "myo_rewards.h"
 #include "myo_host_tasks.h"
+#include "myo_obs_terms.h"
 #include "myo_host_model.h"
 #include "myo_host_batch.h"
 #include "../../include/myo_hip_objects.h"
@@ -110,6 +112,7 @@ int myo_batch_size(const myo_batch* b) { return b ? b->db.B : 0; }
 
 int myo_batch_configure(myo_batch* b, const myo_task_config* c) {
   if (!b || !c) return fail(MYO_E_ARG, "myo_batch_configure: null");
+  if (b->obs_terms.terms) return fail(MYO_E_ARG, OBS_TERMS_CONFIGURED);
   if (b->bm_on && c->task == MYO_TASK_STAND) return fail(MYO_E_UNSUPPORTED, "per-env body masses: the stand task uses model-wide mass totals");
   const DevModel& dm = b->model->dm;
   TaskDev& T = b->task;
@@ -169,8 +172,14 @@ int myo_batch_set_geom_override(myo_batch* b, int geom_id, const float* lo, cons
 }
 
 // the two tasks with a config record of their own: myo_task_walk.h, myo_task_myodm.h
-int myo_batch_configure_walk(myo_batch* b, const myo_walk_config* c) { return b && c ? walk_configure(b, c) : fail(MYO_E_ARG, "myo_batch_configure_walk: null"); }
-int myo_batch_configure_track(myo_batch* b, const myo_track_config* c) { return b && c ? track_configure(b, c) : fail(MYO_E_ARG, "myo_batch_configure_track: null"); }
+int myo_batch_configure_walk(myo_batch* b, const myo_walk_config* c) {
+  if (!b || !c) return fail(MYO_E_ARG, "myo_batch_configure_walk: null");
+  return b->obs_terms.terms ? fail(MYO_E_ARG, OBS_TERMS_CONFIGURED) : walk_configure(b, c);
+}
+int myo_batch_configure_track(myo_batch* b, const myo_track_config* c) {
+  if (!b || !c) return fail(MYO_E_ARG, "myo_batch_configure_track: null");
+  return b->obs_terms.terms ? fail(MYO_E_ARG, OBS_TERMS_CONFIGURED) : track_configure(b, c);
+}
 
 int myo_reset(myo_batch* b, const uint8_t* mask_dev, uint64_t seed, void* stream) {
   if (!b) return fail(MYO_E_ARG, "myo_reset: null");
@@ -213,7 +222,9 @@ int myo_step(myo_batch* b, const float* action_dev, int actmap, int nsubsteps, v
 static int obs_entry(myo_batch* b, void* stream, int obs_only, int reset_only, const char* null_text) {
   if (!b) return fail(MYO_E_ARG, null_text);
   HIPCHK(hipSetDevice(b->model->device));
-  return launch_obs(b, (hipStream_t)stream, obs_only, reset_only);
+  const int rc = launch_obs(b, (hipStream_t)stream, obs_only, reset_only);
+  // the observation-term rows follow MYO_F_OBS (the walk task's observation is a step launch: launch_wave has run the kernel)
+  return !rc && b->obs_terms.terms && b->task.task != MYO_TASK_WALK ? obs_terms_launch(b, (hipStream_t)stream) : rc;
 }
 int myo_obs(myo_batch* b, void* stream) { return obs_entry(b, stream, 0, 0, "myo_obs: null"); }
 int myo_obs_only(myo_batch* b, void* stream) { return obs_entry(b, stream, 1, 0, "myo_obs_only: null"); }

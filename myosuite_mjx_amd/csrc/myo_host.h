@@ -153,6 +153,11 @@ struct myo_model {
 // steps; a byte per env raised by the update that ended its episode; episodes ended per env.  run == nullptr: off
 struct myo_episode { float *run = nullptr, *last = nullptr; uint8_t* finished = nullptr; int* count = nullptr; };
 
+// observation terms (myo_batch_enable_obs_terms, myo_obs_terms.h): the three rows [B][wt] all terms, [B][ws] the obs_keys concatenation, [B][wp]
+// the proprio_keys one (prop == nullptr, wp == 0: none), the column program (one (source, index) record per float of the three rows laid
+// end to end) and the constant table.  terms == nullptr: off
+struct myo_obs_terms { float *terms = nullptr, *sel = nullptr, *prop = nullptr; const int2* prog = nullptr; const float* cst = nullptr; int wt = 0, ws = 0, wp = 0; };
+
 struct myo_batch {
   const myo_model* model = nullptr;
   DevBatch db{};
@@ -182,6 +187,7 @@ struct myo_batch {
   int bq_body = -1;              // body of MYO_F_BODYQUAT (myo_task_config.quat_body; -1: none selected)
   bool sens_on = false;          // touch sensors / contact forces enabled (DevBatch.sens / cfrc allocated)
   myo_episode episode;           // episode statistics (device buffers in pool)
+  myo_obs_terms obs_terms;       // observation-term rows (device buffers in pool)
   bool bq_on = false;            // per-env body orientation started (DevBatch.bquat / bquat_range / bq_c / bq_flag allocated)
   bool fwd_on = false;           // forward buffers allocated (the first myo_forward)
   void* fwd_buf[16] = {};        // ... one per MYO_FWD_* id
@@ -199,7 +205,7 @@ struct myo_batch {
   }
 };
 
-// ---- device buffers handed to the caller.  Every family (batch fields, reward row, episode buffers, forward buffers, object tables) keeps
+// ---- device buffers handed to the caller.  Every family (batch fields, reward row, episode buffers, observation-term rows, forward buffers, object tables) keeps
 // one function with its own refusals that yields a DevBuf; the lookup, read and write entry points are argument checks plus the pieces below.
 struct DevBuf { void* p; size_t width, elem; };   // device pointer, elements per env row (pitch = width everywhere), bytes per element
 typedef int (*BufFamily)(const myo_batch*, int which, DevBuf*);

@@ -106,7 +106,9 @@ static int launch_wave(myo_batch* b, const float* action, int actmap, int nsub, 
                      nsub, b->d_stamps, order, wk, kflags, P.S);
   HIPCHK(hipGetLastError());
   // walk task with the term row on: the row and MYO_F_REWARD of every launch whose fused pass wrote the reward
-  if (wk && b->db.rwd && !(kflags & KF_OBS_ONLY)) return walk_terms_launch(b, s);
+  if (wk && b->db.rwd && !(kflags & KF_OBS_ONLY)) { if ((rc = walk_terms_launch(b, s))) return rc; }
+  // ... and with the observation-term rows on, those rows of every launch: each of them wrote MYO_F_OBS
+  if (wk && b->obs_terms.terms) return obs_terms_launch(b, s);
   return MYO_OK;
 }
 

@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import capi, objects, rewards, tasks, track
+from . import capi, objects, observations, rewards, tasks, track
 from . import model as _model
 
 # ASL pose table (envs/myo/myobase/__init__.py:326-376): target joint vectors of myoHandPose{k}Fixed-v0;
@@ -268,6 +268,15 @@ class BatchedMyoEnv(capi.FieldViews):
     weights re-weight or drop terms (None: the registered ones), rwd_mode picks the column step() returns.  episode_stats=True adds
     info["episode"] = {"finished", "r", "r_sparse", "l", "solved"}: the statistics of each env's last finished episode, which the in-place
     reset would otherwise wipe.  With the defaults nothing is allocated and no launch is added.
+
+    obs_dict=True (implied by obs_keys=[...] or proprio_keys=[...]) adds the reference's observation dictionary: `obs_dict` /
+    info["obs_dict"] = {key: [B, width]} for every key of the task's get_obs_dict (`observations.OBS_TERMS`), and reset() / step() return
+    the concatenation of `obs_keys` instead of the canonical row (None: the class's DEFAULT_OBS_KEYS, i.e. the canonical row; `act` is
+    appended for a model with muscles as base_v0.py:34-38 does), so `obs_dim` is that selection's width and a policy trains on it with no
+    further change; `canonical_obs` stays the registered row.  proprio_keys adds get_proprioception() and info["proprio_dict"].  All of
+    them describe the observation step() returns: with `autoreset`, an env that was just reset shows its first observation and
+    obs_dict["time"] is 0 there -- unlike rwd_dict, which describes the transition just made.  One small launch per observation pass
+    fills them; with the defaults nothing is allocated and no launch is added.
     """
 
     # env kwargs of the reference that gym.make forwards to the env class and that are honoured here (others raise): the task records' tables
@@ -277,7 +286,8 @@ class BatchedMyoEnv(capi.FieldViews):
     _target_jnt_range = staticmethod(tasks.target_jnt_range)
 
     def __init__(self, env_id, num_envs=1, device=0, seed=0, env_offset=0, autoreset=True, as_torch=True, sensors=False,
-                 rwd_dict=False, weighted_reward_keys=None, rwd_mode="dense", episode_stats=False, **env_kwargs):
+                 rwd_dict=False, weighted_reward_keys=None, rwd_mode="dense", episode_stats=False, obs_keys=None, proprio_keys=None,
+                 obs_dict=False, **env_kwargs):
         if env_id in UNSUPPORTED:
             raise NotImplementedError(f"{env_id}: {UNSUPPORTED[env_id]}")
         if env_id not in REGISTRY:
@@ -288,6 +298,8 @@ class BatchedMyoEnv(capi.FieldViews):
         # reward terms: any of the four parameters turns the term row on (rewards.resolve: KeyError / ValueError before anything is loaded)
         self._rwd = rewards.resolve(env_id, spec, rwd_dict, weighted_reward_keys, rwd_mode, episode_stats)
         self.rwd_dict, self.episode_stats, self.rwd_mode = self._rwd is not None, bool(episode_stats), rwd_mode
+        # observation terms: any of the three parameters turns the rows on (observations.resolve: KeyError / ValueError before anything is loaded)
+        self._obs_sel = observations.resolve(env_id, spec, obs_keys, proprio_keys, obs_dict)
         self.num_envs, self.device, self.seed, self.autoreset, self.as_torch = int(num_envs), device, int(seed), autoreset, as_torch
         self.mjmodel = m = _model.load_asset(spec["model"])
         self.muscle_condition = spec.get("muscle_condition", "")
@@ -314,6 +326,7 @@ class BatchedMyoEnv(capi.FieldViews):
             self.batch.enable_rewards(w, capi.RWD_SPARSE if mode == "sparse" else capi.RWD_DENSE)
             if self.episode_stats:
                 self.batch.enable_episode_stats()
+        self._setup_obs_terms(m, spec, s.obs_dim)
         self._obs_in_step = s.call == "configure_walk"                 # the walk task's observation / reward pass is fused into the step kernel
         self._set_condition(m, spec)
         self.act_dim = m.nu
@@ -326,6 +339,28 @@ class BatchedMyoEnv(capi.FieldViews):
             import torch
             self._torch = torch
             self._action_buf = torch.empty((self.num_envs, m.nu), dtype=torch.float32, device=f"cuda:{device}")
+
+    def _setup_obs_terms(self, m, spec, canonical_dim):
+        """obs_keys / proprio_keys / obs_dim of this env, and with any of the three parameters given the library's rows.  The default keys
+        must restate the canonical row (host arithmetic, checked for every env)."""
+        task, d = spec["task"], observations.dims(m, spec)
+        self._obs_width = width = observations.widths(task, d)
+        default = observations.default_keys(task, d["na"])
+        assert sum(width[k] for k in default) == canonical_dim, (self.id, default, width, canonical_dim)
+        self.canonical_obs_dim = canonical_dim
+        sel = self._obs_sel
+        self.obs_keys = list(default if sel is None or sel.obs_keys is None else observations.with_act(task, sel.obs_keys, d["na"]))
+        self.proprio_keys = None if sel is None or sel.proprio_keys is None else list(sel.proprio_keys)
+        for k in self.obs_keys + (self.proprio_keys or []):
+            if width[k] <= 0:
+                raise KeyError(f"{self.id}: the model has no obs_dict term {k!r} (no muscles)")
+        self.obs_dim = sum(width[k] for k in self.obs_keys)
+        self._obs_views = None
+        if sel is None:         # nothing is allocated and no launch is added without the parameters
+            return
+        names = list(width)
+        assert self.batch.obs_terms() == tuple(width.items()), (self.batch.obs_terms(), width)
+        self.batch.enable_obs_terms([names.index(k) for k in self.obs_keys], [names.index(k) for k in self.proprio_keys or []])
 
     def _set_condition(self, m, spec):
         """The action map of the id's muscle condition and the library calls that go with it (base_v0.py:64-80, 100-109)."""
@@ -484,6 +519,55 @@ class BatchedMyoEnv(capi.FieldViews):
         i32 = (lambda x: x.to(self._torch.int32)) if self._torch is not None else (lambda x: x.astype(np.int32))
         info["episode"] = {"finished": fin > 0, "r": last[:, 0], "r_sparse": last[:, 1], "l": i32(last[:, 2]), "solved": i32(last[:, 3])}
 
+    # -- observation terms (make(..., obs_dict=True / obs_keys=[...] / proprio_keys=[...])) ------------------------------------------------
+    @property
+    def canonical_obs(self):
+        """[num_envs, canonical_obs_dim] the registered row of the id (MYO_F_OBS), whatever `obs_keys` selects."""
+        return self.view(capi.F_OBS)
+
+    @property
+    def obs_slices(self):
+        """{key: slice} of each of `obs_keys` in the row reset() / step() return."""
+        return observations.slices(self.obs_keys, self._obs_width)
+
+    def obsvec2obsdict(self, obs):
+        """{key: obs[..., its columns]} of a row (or a stack of rows) [..., obs_dim] by `obs_keys`: slicing only, numpy or torch."""
+        return observations.obsvec2obsdict(obs, self.obs_keys, self._obs_width)
+
+    @property
+    def obs_dict(self):
+        """{key: [num_envs, width]} for every key of the task's get_obs_dict, of the observation last returned: column views of the
+        library's term row (no copy); as_torch=False: slices of one numpy copy."""
+        if self._obs_sel is None:
+            raise AttributeError(f"{self.id}: made without obs_dict=True")
+        if self._obs_views is not None:
+            return self._obs_views
+        row, sl = self.view(capi.OBS_TERMS, "obs"), observations.slices(self._obs_width, self._obs_width)
+        out = {k: row[:, s] for k, s in sl.items() if s.stop > s.start}
+        if self.as_torch:       # views of one buffer: they stay current
+            self._obs_views = out
+        return out
+
+    def _proprio_dict(self, obs_dict):
+        return {"time": obs_dict["time"], **{k: obs_dict[k] for k in self.proprio_keys}}
+
+    def get_proprioception(self):
+        """(time, vec, dict) of env_base.py:512-531: vec [num_envs, proprio width] is the concatenation of `proprio_keys` (a view of the
+        library's row), dict = {"time": ..., key: ...}.  None when the env was made without proprio_keys."""
+        if self.proprio_keys is None:
+            return None
+        d = self._proprio_dict(self.obs_dict)
+        return d["time"], self.view(capi.OBS_PROPRIO, "obs"), d
+
+    def _returned_obs(self, info=None):
+        if self._obs_sel is None:
+            return self.view(capi.F_OBS)
+        if info is not None:
+            info["obs_dict"] = od = self.obs_dict
+            if self.proprio_keys is not None:
+                info["proprio_dict"] = self._proprio_dict(od)
+        return self.view(capi.OBS_SELECTED, "obs")
+
     # -- gym API -------------------------------------------------------------------------------------------
     def reset(self, seed=None):
         if seed is not None:
@@ -493,7 +577,7 @@ class BatchedMyoEnv(capi.FieldViews):
         if self.episode_stats:
             self.batch.episode_clear(s)
         self.batch.obs(s)
-        return self.view(capi.F_OBS)
+        return self._returned_obs()
 
     def step(self, action):
         s = self._stream()
@@ -524,7 +608,7 @@ class BatchedMyoEnv(capi.FieldViews):
             self.batch.autoreset(self.max_episode_steps, self._episode_seed, s)
             self.batch.obs_reset_only(s)
         info["time"] = self.view(capi.F_TIME)
-        return self.view(capi.F_OBS), reward, done, truncated, info
+        return self._returned_obs(info), reward, done, truncated, info
 
     # -- state access (env_base.py:643-705 get_env_state / set_env_state) ----------------------------------
     def get_env_state(self):
@@ -549,7 +633,11 @@ def _enable_sensors(env_id, batch):
         raise NotImplementedError(f"{env_id}: sensors=True is not available: {e}") from None
 
 
-def _make_track(env_id, num_envs, reference=None, flavour="mjx", sensors=False, rwd_dict=False, episode_stats=False, **kw):
+def _make_track(env_id, num_envs, reference=None, flavour="mjx", sensors=False, rwd_dict=False, episode_stats=False, obs_keys=None,
+                proprio_keys=None, obs_dict=False, **kw):
+    if obs_keys is not None or proprio_keys is not None or obs_dict:
+        raise NotImplementedError(f"{env_id}: obs_keys / proprio_keys / obs_dict are not offered for the MyoDM ids; their observation is the "
+                                  "TrackEnv row (qpos, qvel and, in the classic flavour, the tracking errors and act) as one vector")
     if rwd_dict or episode_stats:
         raise NotImplementedError(f"{env_id}: rwd_dict / episode_stats are not offered for the MyoDM ids; their reward terms (pose, object, bonus, "
                                   'penalty) are info["metrics"] of every step')

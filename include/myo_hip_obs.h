@@ -37,6 +37,12 @@ enum { MYO_OBS_TERMS = 0,      /* [B][sum of all term widths] float32: every ter
 int myo_batch_obs_nterm(const myo_batch*);
 const char* myo_batch_obs_term_name(const myo_batch*, int k);
 int myo_batch_obs_term_width(const myo_batch*, int k);
+/* The same table by value, with no batch and no device: the table of `task` (a MYO_TASK_* id) for a model of the given dimensions -- nq, nv,
+ * nu, na (its muscles), ntip (reach tips; 1 for the stand task) and pose_act (na, or nq for a model without muscles).  Returns the number of
+ * terms (0: the task has no table) and, for term k, its name (NULL out of range), its width (-1 out of range) and its offset in the canonical
+ * row MYO_F_OBS (-1: the term comes from outside the row, or k is out of range); *row_dim = the width of the canonical row.  Any out-pointer
+ * may be NULL.  The three calls above answer from this table, with the dimensions of the batch's model */
+int myo_obs_term_table(int task, int nq, int nv, int nu, int na, int ntip, int pose_act, int k, const char** name, int* width, int* offset, int* row_dim);
 /* Allocates the three rows and turns the extra launch on, after the task was configured.  obs_terms[nobs] / proprio_terms[nproprio]: indices
  * into the table, in concatenation order; an index may repeat; nobs >= 1; nproprio == 0 (proprio_terms may be NULL): no MYO_OBS_PROPRIO.
  * Refused: no task or the MyoDM track task (MYO_E_UNSUPPORTED), the walk task with myo_set_lanes != 64 (MYO_E_UNSUPPORTED), an index out

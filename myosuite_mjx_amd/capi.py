@@ -185,6 +185,7 @@ OBS_SIGNATURES = {
     "myo_batch_obs_nterm": (_I, [_V]),
     "myo_batch_obs_term_name": (_STR, [_V, _I]),
     "myo_batch_obs_term_width": (_I, [_V, _I]),
+    "myo_obs_term_table": (_I, [_I] * 8 + [C.POINTER(_STR), _pI, _pI, _pI]),
     "myo_batch_enable_obs_terms": (_I, [_V, _pI, _I, _pI, _I]),
     "myo_batch_obs_buffer": (_I, [_V, _I, *_BUF]),
     "myo_batch_obs_read": (_I, [_V, _I, _V, _SZ]),
@@ -272,6 +273,18 @@ def lib():
 
 class MyoError(RuntimeError):
     pass
+
+
+def obs_term_table(task, nq, nv, nu, na, ntip, pose_act):
+    """The library's observation-term table of task id `task` for a model of these dimensions, without a batch or a GPU:
+    (((name, width, offset in the canonical row or -1), ...), width of the canonical row)."""
+    name, width, offset, dim = _STR(), _I(), _I(), _I()
+    ask = lambda k: lib().myo_obs_term_table(task, nq, nv, nu, na, ntip, pose_act, k, C.byref(name), C.byref(width), C.byref(offset), C.byref(dim))
+    terms = []
+    for k in range(ask(-1)):
+        ask(k)
+        terms.append((name.value.decode(), width.value, offset.value))
+    return tuple(terms), dim.value
 
 
 def _chk(rc):

@@ -224,6 +224,23 @@ struct DevWalk {
   float mass_total, static_mcom[3];
   float knee_height;   // > 0 (TerrainEnvV0): also done when COM height - mean feet height falls below it
 };
+// A task's canonical observation row (MYO_F_OBS) is stated once, as a record of its blocks in row order: each block names its width and
+// follows the one before it, and the record ends with the row's width.  The task's observation body, its configure, its term table
+// (myo_task_<name>.h) and whatever reads the row back index it through the record.
+struct Blk {
+  int at, n;   // first float of the block in the row, floats
+  __host__ __device__ constexpr Blk then(int width) const { return {at + n, width}; }   // the block after this one
+  __host__ __device__ constexpr int end() const { return at + n; }
+};
+// walk_v0.py WalkEnvV0 / TerrainEnvV0 (DEFAULT_OBS_KEYS, then act).  Written by the step kernel's walk pass (myo_wave_motion.h), read back
+// by walk_terms_kernel (myo_rewards.h); beside DevWalk because that pass sees nothing of the task files
+struct WalkRow {
+  int nq, nv, nu;
+  Blk qpos_without_xy = {0, nq - 2}, qvel = qpos_without_xy.then(nv), com_vel = qvel.then(2), torso_angle = com_vel.then(4),
+      feet_heights = torso_angle.then(2), height = feet_heights.then(1), feet_rel_positions = height.then(6), phase_var = feet_rel_positions.then(1),
+      muscle_length = phase_var.then(nu), muscle_velocity = muscle_length.then(nu), muscle_force = muscle_velocity.then(nu), act = muscle_force.then(nu);
+  int dim = act.end();
+};
 enum { KF_AUX = 1, KF_OBS_ONLY = 2, KF_RESET_ONLY = 4 };   // step_kernel_w flags: observation pass without stepping / without reward / only for just-reset envs
 
 // ------------------------------------------------------------------------------------------------

@@ -19,11 +19,13 @@
 //   myo_host.h          shared by all of them: error reporting, device-memory pool (DevPool), use_device, blob view (Blob, blob_open), kernel
 //                       attributes once per device (set_lds_limit), myo_model, myo_batch, the device buffers handed to callers (DevBuf, buf_lookup,
 //                       buf_read, the blocking copies), the per-task hook record (TaskHooks) and its launchers
-//   myo_rewards.h       reward-term rows and episode statistics (include/myo_hip_rewards.h): column table per task, walk term kernel, statistics kernel, entry points
-//   myo_obs_terms.h     observation-term rows (include/myo_hip_obs.h): term table per task, column program, obs_terms_kernel, entry points
-//   myo_host_tasks.h    the task table: includes the task files below, task_hooks, launch_obs
-//   myo_task_util.h     what the task files share: link-chain walk, row prologue, site gather, activation term, the common configure checks
-//   myo_task_<name>.h   pose, reach, walk, stand, hold, keyturn, pen, baoding, die, myodm: a task's observation body, its configure and its hook record
+//   myo_rewards.h       reward-term rows and episode statistics (include/myo_hip_rewards.h): walk term kernel, statistics kernel, entry points (a task's columns: its hook record)
+//   myo_obs_terms.h     observation-term rows (include/myo_hip_obs.h): column program, obs_terms_kernel, entry points (a task's term table: its hook record)
+//   myo_host_tasks.h    the task table: includes the task files below, task_hooks, launch_obs; what a new task consists of
+//   myo_task_util.h     what the task files share: link-chain walk, row prologue, site gather, activation term, the table macros, the common configure checks
+//   myo_task_<name>.h   pose, reach, walk, stand, hold, keyturn, pen, baoding, die, myodm: a task's row record (the blocks of its observation row; the walk
+//                       task's is in myo_common.h), the observation body that writes through it, its configure, its reward columns and observation-term
+//                       table, and the hook record that carries them
 //   myo_host_model.h    myo_model_load in pieces: table upload, packing of the per-lane records, kernel class
 //   myo_host_batch.h    batch creation, the per-env override records, the table of fields behind myo_batch_field / read / write
 //   myo_host_objects.h  per-env object parameters (include/myo_hip_objects.h): selection, tables, the per-launch compose kernel, draw table, entry points

@@ -236,13 +236,31 @@ static int buf_read(BufFamily family, const myo_batch* b, int which, void* host,
   return copy_to_host(b->model->device, host, d.p, nbytes);
 }
 
+// the two tables a task states beside its row record.  Reward columns (include/myo_hip_rewards.h): the keys of the reference's rwd_dict, in
+// its order.  Observation terms (include/myo_hip_obs.h): the keys of its get_obs_dict, in its order, one ObsTerm per key: name, width, source,
+// index of the term's first float inside the source's row; `dim` is the width of the canonical row.  Widths and indices are arithmetic on
+// ObsDims only, so the table needs no batch and no device (myo_obs_term_table)
+struct RwdCols { const char* const* name; int n; };
+struct ObsDims { int nq, nv, nu, na, ntip, pose_act; };   // na: muscles (MuJoCo's na); pose_act: na, or nq when the model has no muscles
+enum { OBS_SRC_ROW = 0,      // MYO_F_OBS, the canonical row (values already scaled: qvel * dt)
+       OBS_SRC_TIME = 1,     // MYO_F_TIME
+       OBS_SRC_TARGET = 2,   // MYO_F_TARGET
+       OBS_SRC_QPOS = 3,     // MYO_F_QPOS
+       OBS_SRC_ACT = 4,      // MYO_F_ACT; index = slot in sim.data.act order, mapped to its actuator when the program is built
+       OBS_SRC_CONST = 5 };  // the batch's constant table: [0, 3) the pen's eps_ball site, [3, 3 + nq) zeros
+struct ObsTerm { const char* name; int width, src, idx; };
+struct ObsTable : std::vector<ObsTerm> { int dim = 0; };
+
 // What differs per task on the host, indexed by task id (task_hooks in myo_host_tasks.h); a task's record lives next to its kernel.
 struct TaskHooks {
   int (*configure)(myo_batch*, const myo_task_config*);                    // argument and model checks, obs_dim, task-specific TaskDev fields; null: no observation row,
                                                                            // or a task with a config record of its own (walk_configure, track_configure)
   int (*obs)(myo_batch*, hipStream_t, int obs_only, int reset_only);       // observation launch; null: the task has none
   int (*post)(myo_batch*, hipStream_t, uint64_t seed, int auto_max);       // myo_bench_rollout's fused epilogue; null: observation, auto-reset and re-observation are three launches
+  RwdCols rwd;                                                             // reward-term columns, `dense` last; {null, 0}: the task has no term row (the MyoDM track task)
+  void (*obs_terms)(const ObsDims&, ObsTable&);                            // fills the observation-term table from the task's row record; null: no table (track)
 };
+static const TaskHooks* task_hooks(int task);   // myo_host_tasks.h
 // the step launch (myo_host_step.h): the walk task observes through it
 static int launch_step(myo_batch* b, const float* action, int actmap, int nsub, hipStream_t s, int kflags = 0);
 

@@ -1,5 +1,10 @@
 // myo_host_tasks.h -- the table of all tasks: every myo_task_<name>.h, the lookup of a task's hook record and the observation launch that
-// goes through it.  A new task is its file, its #include here and its row in task_hooks.
+// goes through it.  A new task is its file, its #include here and its row in task_hooks.  The file holds the task's row record (the
+// blocks of its canonical observation row, each width once), the observation body that writes through it, the configure that takes obs_dim
+// from it, the reward column names, the observation-term table built from it, and the hook record that hands all of these to the host:
+// myo_rewards.h and myo_obs_terms.h look a task's tables up through task_hooks and name no task.  (The walk row is written inside the step
+// kernel, so its record sits beside DevWalk in myo_common.h.)  On the Python side the task adds its setup to tasks.py, its reward keys to
+// rewards.py and its term names and width expressions to observations.py; tests/test_obs_terms_host.py holds those to the tables here by value.
 #ifndef MYO_HOST_TASKS_H
 #define MYO_HOST_TASKS_H
 
@@ -14,6 +19,10 @@
 #include "myo_task_baoding.h"
 #include "myo_task_die.h"
 #include "myo_task_myodm.h"
+#undef RWD_TAIL
+#undef RWD_COLS
+#undef ROW
+#undef TERM
 
 static const TaskHooks* task_hooks(int task) {
   switch (task) {

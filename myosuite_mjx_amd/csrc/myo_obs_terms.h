@@ -1,132 +1,23 @@
-// myo_obs_terms.h -- observation terms (include/myo_hip_obs.h): the term table per task, the column program the host builds from it, the
-// one kernel that runs the program and the host entry points.  Included by myo_hip.hip after myo_host_tasks.h, before myo_host_step.h
-// (the walk task's step launch runs the kernel).
+// myo_obs_terms.h -- observation terms (include/myo_hip_obs.h): the lookup of a task's term table, the column program the host builds from
+// it, the one kernel that runs the program and the host entry points.  Included by myo_hip.hip after myo_host_tasks.h, before
+// myo_host_step.h (the walk task's step launch runs the kernel).
 #ifndef MYO_OBS_TERMS_H
 #define MYO_OBS_TERMS_H
 
-// ---- the table: the keys of the reference's get_obs_dict per env class, in its order.  One TERM per key: name, width, source, index of the
-// term's first float inside the source's row.  Widths and indices are arithmetic on ObsDims only (observations.py carries the same names and
-// width expressions; tests/test_obs_terms_host.py compares the two texts)
-struct ObsDims { int nq, nv, nu, na, ntip, pose_act; };   // na: muscles (MuJoCo's na); pose_act: na, or nq when the model has no muscles
-enum { OBS_SRC_ROW = 0,      // MYO_F_OBS, the canonical row (values already scaled: qvel * dt)
-       OBS_SRC_TIME = 1,     // MYO_F_TIME
-       OBS_SRC_TARGET = 2,   // MYO_F_TARGET
-       OBS_SRC_QPOS = 3,     // MYO_F_QPOS
-       OBS_SRC_ACT = 4,      // MYO_F_ACT; index = slot in sim.data.act order, mapped to its actuator when the program is built
-       OBS_SRC_CONST = 5 };  // the batch's constant table: [0, 3) the pen's eps_ball site, [3, 3 + nq) zeros
-struct ObsTerm { const char* name; int width, src, idx; };
-typedef std::vector<ObsTerm> ObsTable;
-#define TERM(name, width, src, idx) t.push_back(ObsTerm{name, width, src, idx});
-
-static void obs_terms_pose(const ObsDims& D, ObsTable& t) {      // pose_v0.py get_obs_dict; row: qpos, qvel, pose_err, act
-  TERM("time", 1, OBS_SRC_TIME, 0)
-  TERM("qpos", D.nq, OBS_SRC_ROW, 0)
-  TERM("qvel", D.nv, OBS_SRC_ROW, D.nq)
-  TERM("act", D.pose_act, D.na > 0 ? OBS_SRC_ROW : OBS_SRC_CONST, D.na > 0 ? 3 * D.nq : 3)   // no muscles: zeros_like(qpos), the constant table's zeros
-  TERM("pose_err", D.nq, OBS_SRC_ROW, 2 * D.nq)
+// ---- the table (ObsTable, myo_host.h) of a task for the dimensions D, built by the task's own function (myo_task_<name>.h) from its row
+// record.  Empty: no task, or the MyoDM track task, whose terms live in its own kernels
+static ObsTable obs_table(int task, const ObsDims& D) {
+  ObsTable t;
+  const TaskHooks* hooks = task_hooks(task);
+  if (hooks && hooks->obs_terms) hooks->obs_terms(D, t);
+  for (ObsTerm& x : t) if (x.width < 0) x.width = 0;   // (a model too small for the task: its configure has refused it)
+  return t;
 }
-static void obs_terms_reach(const ObsDims& D, ObsTable& t) {     // reach_v0.py and walk_v0.py ReachEnvV0; row: qpos, qvel, tip_pos, reach_err, act
-  TERM("time", 1, OBS_SRC_TIME, 0)
-  TERM("qpos", D.nq, OBS_SRC_ROW, 0)
-  TERM("qvel", D.nv, OBS_SRC_ROW, D.nq)
-  TERM("act", D.na, OBS_SRC_ROW, D.nq + D.nv + 6 * D.ntip)
-  TERM("tip_pos", 3 * D.ntip, OBS_SRC_ROW, D.nq + D.nv)
-  TERM("target_pos", 3 * D.ntip, OBS_SRC_TARGET, 0)
-  TERM("reach_err", 3 * D.ntip, OBS_SRC_ROW, D.nq + D.nv + 3 * D.ntip)
-}
-static void obs_terms_hold(const ObsDims& D, ObsTable& t) {      // obj_hold_v0.py; row: hand_qpos, hand_qvel, obj_pos, obj_err, act
-  TERM("time", 1, OBS_SRC_TIME, 0)
-  TERM("hand_qpos", D.nq - 7, OBS_SRC_ROW, 0)
-  TERM("hand_qvel", D.nv - 6, OBS_SRC_ROW, D.nq - 7)
-  TERM("obj_pos", 3, OBS_SRC_ROW, D.nq - 7 + D.nv - 6)
-  TERM("obj_err", 3, OBS_SRC_ROW, D.nq - 7 + D.nv - 6 + 3)
-  TERM("act", D.na, OBS_SRC_ROW, D.nq - 7 + D.nv - 6 + 6)
-}
-static void obs_terms_keyturn(const ObsDims& D, ObsTable& t) {   // key_turn_v0.py; row: hand_qpos, hand_qvel, key_qpos, key_qvel, the approaches, act
-  TERM("time", 1, OBS_SRC_TIME, 0)
-  TERM("hand_qpos", D.nq - 1, OBS_SRC_ROW, 0)
-  TERM("hand_qvel", D.nv - 1, OBS_SRC_ROW, D.nq - 1)
-  TERM("key_qpos", 1, OBS_SRC_ROW, D.nq - 1 + D.nv - 1)
-  TERM("key_qvel", 1, OBS_SRC_ROW, D.nq - 1 + D.nv - 1 + 1)
-  TERM("IFtip_approach", 3, OBS_SRC_ROW, D.nq + D.nv)
-  TERM("THtip_approach", 3, OBS_SRC_ROW, D.nq + D.nv + 3)
-  TERM("act", D.na, OBS_SRC_ROW, D.nq + D.nv + 6)
-}
-static void obs_terms_pen(const ObsDims& D, ObsTable& t) {       // pen_v0.py; row: hand_jnt, obj_pos, obj_vel, obj_rot, obj_des_rot, obj_err_pos, obj_err_rot, act
-  TERM("time", 1, OBS_SRC_TIME, 0)
-  TERM("hand_jnt", D.nq - 6, OBS_SRC_ROW, 0)
-  TERM("obj_pos", 3, OBS_SRC_ROW, D.nq - 6)
-  TERM("obj_des_pos", 3, OBS_SRC_CONST, 0)
-  TERM("obj_vel", 6, OBS_SRC_ROW, D.nq - 6 + 3)
-  TERM("obj_rot", 3, OBS_SRC_ROW, D.nq - 6 + 9)
-  TERM("obj_des_rot", 3, OBS_SRC_ROW, D.nq - 6 + 12)
-  TERM("obj_err_pos", 3, OBS_SRC_ROW, D.nq - 6 + 15)
-  TERM("obj_err_rot", 3, OBS_SRC_ROW, D.nq - 6 + 18)
-  TERM("act", D.na, OBS_SRC_ROW, D.nq - 6 + 21)
-}
-static void obs_terms_walk(const ObsDims& D, ObsTable& t) {      // walk_v0.py WalkEnvV0 (TerrainEnvV0 inherits it); row: the terms from qpos_without_xy on
-  TERM("t", 1, OBS_SRC_TIME, 0)
-  TERM("time", 1, OBS_SRC_TIME, 0)
-  TERM("qpos_without_xy", D.nq - 2, OBS_SRC_ROW, 0)
-  TERM("qvel", D.nv, OBS_SRC_ROW, D.nq - 2)
-  TERM("com_vel", 2, OBS_SRC_ROW, D.nq - 2 + D.nv)
-  TERM("torso_angle", 4, OBS_SRC_ROW, D.nq - 2 + D.nv + 2)
-  TERM("feet_heights", 2, OBS_SRC_ROW, D.nq - 2 + D.nv + 6)
-  TERM("height", 1, OBS_SRC_ROW, D.nq - 2 + D.nv + 8)
-  TERM("feet_rel_positions", 6, OBS_SRC_ROW, D.nq - 2 + D.nv + 9)
-  TERM("phase_var", 1, OBS_SRC_ROW, D.nq - 2 + D.nv + 15)
-  TERM("muscle_length", D.nu, OBS_SRC_ROW, D.nq - 2 + D.nv + 16)
-  TERM("muscle_velocity", D.nu, OBS_SRC_ROW, D.nq - 2 + D.nv + 16 + D.nu)
-  TERM("muscle_force", D.nu, OBS_SRC_ROW, D.nq - 2 + D.nv + 16 + 2 * D.nu)
-  TERM("act", D.nu, OBS_SRC_ROW, D.nq - 2 + D.nv + 16 + 3 * D.nu)
-}
-static void obs_terms_baoding(const ObsDims& D, ObsTable& t) {   // baoding_v1.py; row: the terms in the order of its DEFAULT_OBS_KEYS (velp between the positions), no act
-  TERM("time", 1, OBS_SRC_TIME, 0)
-  TERM("hand_pos", D.nq - 14, OBS_SRC_ROW, 0)
-  TERM("object1_pos", 3, OBS_SRC_ROW, D.nq - 14)
-  TERM("object2_pos", 3, OBS_SRC_ROW, D.nq - 14 + 6)
-  TERM("object1_velp", 3, OBS_SRC_ROW, D.nq - 14 + 3)
-  TERM("object2_velp", 3, OBS_SRC_ROW, D.nq - 14 + 9)
-  TERM("target1_pos", 3, OBS_SRC_ROW, D.nq - 14 + 12)
-  TERM("target2_pos", 3, OBS_SRC_ROW, D.nq - 14 + 15)
-  TERM("target1_err", 3, OBS_SRC_ROW, D.nq - 14 + 18)
-  TERM("target2_err", 3, OBS_SRC_ROW, D.nq - 14 + 21)
-  TERM("act", D.na, OBS_SRC_ACT, 0)
-}
-static void obs_terms_die(const ObsDims& D, ObsTable& t) {       // reorient_v0.py; row: hand_qpos_noMD5, hand_qvel, obj_pos .. rot_err, no act
-  TERM("time", 1, OBS_SRC_TIME, 0)
-  TERM("hand_qpos_noMD5", D.nq - 7, OBS_SRC_ROW, 0)
-  TERM("hand_qpos", D.nq - 6, OBS_SRC_QPOS, 0)
-  TERM("hand_qvel", D.nv - 6, OBS_SRC_ROW, D.nq - 7)
-  TERM("obj_pos", 3, OBS_SRC_ROW, D.nq - 7 + D.nv - 6)
-  TERM("goal_pos", 3, OBS_SRC_ROW, D.nq - 7 + D.nv - 6 + 3)
-  TERM("pos_err", 3, OBS_SRC_ROW, D.nq - 7 + D.nv - 6 + 6)
-  TERM("obj_rot", 3, OBS_SRC_ROW, D.nq - 7 + D.nv - 6 + 9)
-  TERM("goal_rot", 3, OBS_SRC_ROW, D.nq - 7 + D.nv - 6 + 12)
-  TERM("rot_err", 3, OBS_SRC_ROW, D.nq - 7 + D.nv - 6 + 15)
-  TERM("act", D.na, OBS_SRC_ACT, 0)
-}
-#undef TERM
-
-// the table of the batch's configured task (empty: no task, or the MyoDM track task, whose terms live in its own kernels)
+// ... of the batch's configured task
 static ObsTable obs_table(const myo_batch* b) {
   const myo_model* m = b->model;
   const int na = m->dm.na_obs;
-  const ObsDims D{m->nq, m->dm.nv, m->dm.nu, na, b->task.task == MYO_TASK_STAND ? 1 : b->task.ntip, na > 0 ? na : m->nq};
-  ObsTable t;
-  switch (b->task.task) {
-    case MYO_TASK_POSE: obs_terms_pose(D, t); break;
-    case MYO_TASK_REACH: case MYO_TASK_STAND: obs_terms_reach(D, t); break;
-    case MYO_TASK_HOLD: obs_terms_hold(D, t); break;
-    case MYO_TASK_KEYTURN: obs_terms_keyturn(D, t); break;
-    case MYO_TASK_PEN: obs_terms_pen(D, t); break;
-    case MYO_TASK_WALK: obs_terms_walk(D, t); break;
-    case MYO_TASK_BAODING: obs_terms_baoding(D, t); break;
-    case MYO_TASK_DIE: obs_terms_die(D, t); break;
-    default: break;
-  }
-  for (ObsTerm& x : t) if (x.width < 0) x.width = 0;   // (a model too small for the task: its configure has refused it)
-  return t;
+  return obs_table(b->task.task, ObsDims{m->nq, m->dm.nv, m->dm.nu, na, b->task.task == MYO_TASK_STAND ? 1 : b->task.ntip, na > 0 ? na : m->nq});
 }
 
 // ---- the kernel.  One thread per output float of the three rows of one env laid end to end ([terms | selected | proprio], W floats): thread
@@ -250,16 +141,29 @@ static int obs_terms_buf(const myo_batch* b, int which, DevBuf* d) {
   return MYO_OK;
 }
 
+// one term of a table: its name (a string literal: outlives the table), width and offset in the canonical row (-1: from outside the row)
+static int obs_term_out(const ObsTable& t, int k, const char** name, int* width, int* offset) {
+  const bool in = k >= 0 && k < (int)t.size();
+  if (name) *name = in ? t[k].name : nullptr;
+  if (width) *width = in ? t[k].width : -1;
+  if (offset) *offset = in && t[k].src == OBS_SRC_ROW ? t[k].idx : -1;
+  return (int)t.size();
+}
+int myo_obs_term_table(int task, int nq, int nv, int nu, int na, int ntip, int pose_act, int k, const char** name, int* width, int* offset, int* row_dim) {
+  const ObsTable t = obs_table(task, ObsDims{nq, nv, nu, na, ntip, pose_act});
+  if (row_dim) *row_dim = t.dim;
+  return obs_term_out(t, k, name, width, offset);
+}
 int myo_batch_obs_nterm(const myo_batch* b) { return b ? (int)obs_table(b).size() : 0; }
 const char* myo_batch_obs_term_name(const myo_batch* b, int k) {
-  if (!b) return nullptr;
-  const ObsTable t = obs_table(b);
-  return k >= 0 && k < (int)t.size() ? t[k].name : nullptr;   // (a string literal: outlives the table)
+  const char* name = nullptr;
+  if (b) obs_term_out(obs_table(b), k, &name, nullptr, nullptr);
+  return name;
 }
 int myo_batch_obs_term_width(const myo_batch* b, int k) {
-  if (!b) return -1;
-  const ObsTable t = obs_table(b);
-  return k >= 0 && k < (int)t.size() ? t[k].width : -1;
+  int width = -1;
+  if (b) obs_term_out(obs_table(b), k, nullptr, &width, nullptr);
+  return width;
 }
 int myo_batch_enable_obs_terms(myo_batch* b, const int* obs_terms, int nobs, const int* proprio_terms, int nproprio) {
   return b ? obs_terms_enable(b, obs_terms, nobs, proprio_terms, nproprio) : fail(MYO_E_ARG, "myo_batch_enable_obs_terms: null");

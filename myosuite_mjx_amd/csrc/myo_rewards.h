@@ -1,36 +1,15 @@
-// myo_rewards.h -- reward-term rows and episode statistics (include/myo_hip_rewards.h): the column table per task, the walk task's term
-// kernel, the episode-statistics kernel and the host entry points.  The other tasks write their rows in their own observation kernels
-// (rwd_row, myo_common.h).  Included by myo_hip.hip after myo_host.h, before the task files (their configure reads rwd_cols).
+// myo_rewards.h -- reward-term rows and episode statistics (include/myo_hip_rewards.h): the lookup of a task's columns, the walk task's
+// term kernel, the episode-statistics kernel and the host entry points.  The other tasks write their rows in their own observation kernels
+// (rwd_row, myo_common.h).  Included by myo_hip.hip after myo_host.h, before the task files (walk_configure reads rwd_cols).
 #ifndef MYO_REWARDS_H
 #define MYO_REWARDS_H
 
-// ---- columns: the keys of the reference's rwd_dict per env class, in its order; every row ends sparse, solved, done, dense
-#define RWD_TAIL "sparse", "solved", "done", "dense"
-static const char* const rwd_pose[] = {"pose", "bonus", "penalty", "act_reg", RWD_TAIL};                                        // pose_v0.py:118-135
-static const char* const rwd_reach[] = {"reach", "bonus", "act_reg", "penalty", RWD_TAIL};                                      // reach_v0.py:126-141, walk_v0.py:117-133
-static const char* const rwd_hold[] = {"goal_dist", "bonus", "act_reg", "penalty", RWD_TAIL};                                   // obj_hold_v0.py:102-117
-static const char* const rwd_keyturn[] = {"key_turn", "IFtip_approach", "THtip_approach", "act_reg", "bonus", "penalty", RWD_TAIL};   // key_turn_v0.py:134-152
-static const char* const rwd_pen[] = {"pos_align", "rot_align", "act_reg", "drop", "bonus", RWD_TAIL};                          // pen_v0.py:150-167
-static const char* const rwd_walk[] = {"vel_reward", "cyclic_hip", "ref_rot", "joint_angle_rew", "act_mag", RWD_TAIL};          // walk_v0.py:298-311
-static const char* const rwd_baoding[] = {"pos_dist_1", "pos_dist_2", "act_reg", RWD_TAIL};                                     // baoding_v1.py:239-262
-static const char* const rwd_die[] = {"pos_dist", "rot_dist", "bonus", "act_reg", "penalty", RWD_TAIL};                         // reorient_v0.py:148-176
-#undef RWD_TAIL
-struct RwdCols { const char* const* name; int n; };
-#define RWD_COLS(a) RwdCols{a, (int)(sizeof a / sizeof a[0])}
+// ---- columns: the keys of the reference's rwd_dict per env class, in its order; a task's names live in its hook record (myo_task_<name>.h).
+// No task, and the MyoDM track task (its terms are MYO_F_METRICS), have none
 static RwdCols rwd_cols(int task) {
-  switch (task) {
-    case MYO_TASK_POSE: return RWD_COLS(rwd_pose);
-    case MYO_TASK_REACH: case MYO_TASK_STAND: return RWD_COLS(rwd_reach);
-    case MYO_TASK_HOLD: return RWD_COLS(rwd_hold);
-    case MYO_TASK_KEYTURN: return RWD_COLS(rwd_keyturn);
-    case MYO_TASK_PEN: return RWD_COLS(rwd_pen);
-    case MYO_TASK_WALK: return RWD_COLS(rwd_walk);
-    case MYO_TASK_BAODING: return RWD_COLS(rwd_baoding);
-    case MYO_TASK_DIE: return RWD_COLS(rwd_die);
-    default: return RwdCols{nullptr, 0};   // no task, or the MyoDM track task (its terms are MYO_F_METRICS)
-  }
+  const TaskHooks* hooks = task_hooks(task);
+  return hooks ? hooks->rwd : RwdCols{nullptr, 0};
 }
-#undef RWD_COLS
 
 // ---- walk task: the step kernel's fused pass keeps its fixed-weight sum; with the term row on, this kernel follows every launch of it
 // that wrote MYO_F_REWARD and restates the terms from what that pass stored -- the observation row (qpos[2:], COM velocity, feet heights, COM
@@ -43,10 +22,11 @@ __global__ void __launch_bounds__(64) walk_terms_kernel(DevBatch Bt, const DevWa
   for (int i = lane; i < nu; i += 64) { const float ai = a[i]; act2 += ai * ai; }
   const float act_mag = sqrtf(wave_sum(act2)) / (float)(na > 0 ? na : 1);   // walk_v0.py:291-295 (0 without muscles: act stays zero)
   if (lane != 0) return;
+  const WalkRow R{nq, nv, nu};
   const float* o = Bt.obs + (size_t)e * wk->obs_dim;
-  auto qp = [&](int i) { return o[i - 2]; };    // qpos[i], i >= 2: the row starts with qpos_without_xy
-  const int sb = nq - 2 + nv;
-  const float cvx = o[sb], cvy = o[sb + 1], fl = o[sb + 6], fr = o[sb + 7], height = o[sb + 8], phase = o[sb + 15];
+  auto qp = [&](int i) { return o[R.qpos_without_xy.at + i - 2]; };    // qpos[i], i >= 2
+  const float cvx = o[R.com_vel.at], cvy = o[R.com_vel.at + 1], fl = o[R.feet_heights.at], fr = o[R.feet_heights.at + 1], height = o[R.height.at],
+              phase = o[R.phase_var.at];
   const float q[4] = {qp(3), qp(4), qp(5), qp(6)};
   const float dvy = wk->target_y_vel - cvy, dvx = wk->target_x_vel - cvx;
   const float vel_reward = expf(-dvy * dvy) + expf(-dvx * dvx);

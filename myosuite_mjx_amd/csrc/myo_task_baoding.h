@@ -7,22 +7,31 @@
 #ifndef MYO_TASK_BAODING_H
 #define MYO_TASK_BAODING_H
 
-// baoding_v1.py:147-246.  Row: hand qpos (nq - 14), ball1 position, ball1 linear qvel * dt, ball2 position, ball2 linear qvel * dt, target1,
-// target2, target1 - ball1, target2 - ball2 (47 floats for myohand_baoding; act is not observed).  T.tip_site = ball1, ball2, target1,
-// target2; Bt.target row = start angle, sign, x radius, y radius, period.
+// baoding_v1.py:147-246.  Row, in the order of its DEFAULT_OBS_KEYS: hand qpos (the balls' two free joints come last), ball1 position, ball1
+// linear qvel * dt, ball2 position, ball2 linear qvel * dt, target1, target2, target1 - ball1, target2 - ball2 (47 floats for
+// myohand_baoding; act is not observed).  T.tip_site = ball1, ball2, target1, target2; Bt.target row = start angle, sign, x radius, y
+// radius, period.
+struct BaodingRow {
+  int nq;
+  Blk hand_pos = {0, nq - 14}, object1_pos = hand_pos.then(3), object1_velp = object1_pos.then(3), object2_pos = object1_velp.then(3),
+      object2_velp = object2_pos.then(3), target1_pos = object2_velp.then(3), target2_pos = target1_pos.then(3), target1_err = target2_pos.then(3),
+      target2_err = target1_err.then(3);
+  int dim = target2_err.end();
+};
 __device__ __forceinline__ void baoding_obs_body(const DevModel& M, const DevBatch& Bt, const TaskDev& T, int obs_only, const int e, const int lane) {
   const int nv = M.nv, nq = nv + 2, nh = nv - 12;
+  const BaodingRow R{nq};
   const auto [o, q, v, a, dt] = task_row(M, Bt, T, e, nq);
   float p[3] = {0.f, 0.f, 0.f}, x[4][3];
   if (lane < 4) {
     const int s = T.tip_site[lane];
     if (lane < 2) {   // ball site: its free joint's position + R(quat) site_lpos
       const float* qb = q + nh + 7 * lane;
-      float qq[4] = {qb[3], qb[4], qb[5], qb[6]}, R[9], w[3];
+      float qq[4] = {qb[3], qb[4], qb[5], qb[6]}, Rb[9], w[3];
       const float qn = 1.0f / sqrtf(qq[0] * qq[0] + qq[1] * qq[1] + qq[2] * qq[2] + qq[3] * qq[3]);
       qq[0] *= qn; qq[1] *= qn; qq[2] *= qn; qq[3] *= qn;
-      quat2mat(R, qq);
-      matvec(w, R, M.site_lpos + 3 * s);
+      quat2mat(Rb, qq);
+      matvec(w, Rb, M.site_lpos + 3 * s);
       p[0] = qb[0] + w[0]; p[1] = qb[1] + w[1]; p[2] = qb[2] + w[2];
     } else {          // target: the goal point goal[k - 1] on its ellipse, in the targets' body frame, carried to the world
       const float* g = Bt.target + (size_t)e * 5;
@@ -40,16 +49,16 @@ __device__ __forceinline__ void baoding_obs_body(const DevModel& M, const DevBat
   }
   site_gather<4>(M, Bt, e, lane, 4, p, x);
   if (lane < 3) {
-    o[nh + lane] = x[0][lane];
-    o[nh + 3 + lane] = v[nh + lane] * dt;
-    o[nh + 6 + lane] = x[1][lane];
-    o[nh + 9 + lane] = v[nh + 6 + lane] * dt;
-    o[nh + 12 + lane] = x[2][lane];
-    o[nh + 15 + lane] = x[3][lane];
-    o[nh + 18 + lane] = x[2][lane] - x[0][lane];
-    o[nh + 21 + lane] = x[3][lane] - x[1][lane];
+    o[R.object1_pos.at + lane] = x[0][lane];
+    o[R.object1_velp.at + lane] = v[nh + lane] * dt;
+    o[R.object2_pos.at + lane] = x[1][lane];
+    o[R.object2_velp.at + lane] = v[nh + 6 + lane] * dt;
+    o[R.target1_pos.at + lane] = x[2][lane];
+    o[R.target2_pos.at + lane] = x[3][lane];
+    o[R.target1_err.at + lane] = x[2][lane] - x[0][lane];
+    o[R.target2_err.at + lane] = x[3][lane] - x[1][lane];
   }
-  for (int i = lane; i < nh; i += 64) o[i] = q[i];
+  for (int i = lane; i < nh; i += 64) o[R.hand_pos.at + i] = q[i];
   if (obs_only) return;
   // act_reg (baoding_v1.py:220-222) is a column of the term row only: the registered reward does not weigh it
   const float actn = Bt.rwd ? act_norm(M, act_sq(M, a, lane)) : 0.f;
@@ -93,9 +102,25 @@ static int baoding_configure(myo_batch* b, const myo_task_config* c) {
     const double z = m->site_pos0[3 * (size_t)c->tip_site[2 + t] + 2];
     for (int k = 0; k < 3; k++) T.bd_frame[6 + 3 * t + k] = (float)(m->body_lpos[3 * (size_t)tb + k] + R[3 * k + 2] * z);
   }
-  T.obs_dim = (nv - 12) + 24;
+  T.obs_dim = BaodingRow{m->nq}.dim;
   return MYO_OK;
 }
-static const TaskHooks baoding_hooks = {baoding_configure, launch_task_obs<BaodingTask>, launch_task_post<BaodingTask>};
+static const char* const rwd_baoding[] = {"pos_dist_1", "pos_dist_2", "act_reg", RWD_TAIL};   // baoding_v1.py:239-262
+static void obs_terms_baoding(const ObsDims& D, ObsTable& t) {   // baoding_v1.py get_obs_dict (the positions before the velocities)
+  const BaodingRow R{D.nq};
+  TERM("time", 1, OBS_SRC_TIME, 0)
+  ROW(R, hand_pos)
+  ROW(R, object1_pos)
+  ROW(R, object2_pos)
+  ROW(R, object1_velp)
+  ROW(R, object2_velp)
+  ROW(R, target1_pos)
+  ROW(R, target2_pos)
+  ROW(R, target1_err)
+  ROW(R, target2_err)
+  TERM("act", D.na, OBS_SRC_ACT, 0)
+  t.dim = R.dim;
+}
+static const TaskHooks baoding_hooks = {baoding_configure, launch_task_obs<BaodingTask>, launch_task_post<BaodingTask>, RWD_COLS(rwd_baoding), obs_terms_baoding};
 
 #endif  // MYO_TASK_BAODING_H

@@ -22,12 +22,19 @@ __device__ __forceinline__ void die_mat2euler(float* eu, const float* cx, const 
   }
 }
 
-// reorient_v0.py:111-176.  Row: qpos[:-7] (nq - 7: the reference's off-by-one is kept), qvel[:-6] * dt (nv - 6), obj_pos (3), goal_pos (3),
-// pos_err = goal_pos - obj_pos - goal_obj_offset (3), obj_rot (3), goal_rot (3), rot_err = goal_rot - obj_rot (3); act is not observed.
+// reorient_v0.py:111-176.  Row: qpos[:-7] (the reference's off-by-one is kept: the hand's last joint is missing), qvel[:-6] * dt, obj_pos,
+// goal_pos, pos_err = goal_pos - obj_pos - goal_obj_offset, obj_rot, goal_rot, rot_err = goal_rot - obj_rot; act is not observed.
 // T.tip_site = object_o, object_x, object_y, object_z, target_o, target_x, target_y, target_z; T.tip_lpos = goal_obj_offset; Bt.target row =
 // the goal offset from the compiled target position.
+struct DieRow {
+  int nq, nv;
+  Blk hand_qpos_noMD5 = {0, nq - 7}, hand_qvel = hand_qpos_noMD5.then(nv - 6), obj_pos = hand_qvel.then(3), goal_pos = obj_pos.then(3),
+      pos_err = goal_pos.then(3), obj_rot = pos_err.then(3), goal_rot = obj_rot.then(3), rot_err = goal_rot.then(3);
+  int dim = rot_err.end();
+};
 __device__ __forceinline__ void die_obs_body(const DevModel& M, const DevBatch& Bt, const TaskDev& T, int obs_only, const int e, const int lane) {
-  const int nv = M.nv, nh = nv - 6, b0 = 2 * nh - 1;
+  const int nv = M.nv;
+  const DieRow R{nv, nv};   // nq == nv (die_configure)
   const auto [o, q, v, a, dt] = task_row(M, Bt, T, e, nv);
   float p[3] = {0.f, 0.f, 0.f}, x[8][3];
   if (lane < 8) {   // lanes 0-3: the die's sites, 4-7: the target's
@@ -57,16 +64,16 @@ __device__ __forceinline__ void die_obs_body(const DevModel& M, const DevBatch& 
 #pragma unroll
   for (int k = 0; k < 3; k++) { perr[k] = x[4][k] - x[0][k] - T.tip_lpos[k]; rerr[k] = grot[k] - orot[k]; }
   if (lane < 3) {
-    o[b0 + lane] = x[0][lane];
-    o[b0 + 3 + lane] = x[4][lane];
-    o[b0 + 6 + lane] = perr[lane];
-    o[b0 + 9 + lane] = orot[lane];
-    o[b0 + 12 + lane] = grot[lane];
-    o[b0 + 15 + lane] = rerr[lane];
+    o[R.obj_pos.at + lane] = x[0][lane];
+    o[R.goal_pos.at + lane] = x[4][lane];
+    o[R.pos_err.at + lane] = perr[lane];
+    o[R.obj_rot.at + lane] = orot[lane];
+    o[R.goal_rot.at + lane] = grot[lane];
+    o[R.rot_err.at + lane] = rerr[lane];
   }
-  for (int i = lane; i < nh; i += 64) {
-    if (i < nh - 1) o[i] = q[i];
-    o[nh - 1 + i] = v[i] * dt;
+  for (int i = lane; i < R.hand_qvel.n; i += 64) {
+    if (i < R.hand_qpos_noMD5.n) o[R.hand_qpos_noMD5.at + i] = q[i];
+    o[R.hand_qvel.at + i] = v[i] * dt;
   }
   if (obs_only) return;
   const float actn = act_norm(M, act_sq(M, a, lane));
@@ -117,9 +124,25 @@ static int die_configure(myo_batch* b, const myo_task_config* c) {
   site_world0(ob, c->tip_site[0], wo);
   site_world0(tb, c->tip_site[4], wt);
   for (int k = 0; k < 3; k++) T.tip_lpos[k] = (float)(wt[k] - wo[k]);
-  T.obs_dim = (nv - 7) + (nv - 6) + 18;
+  T.obs_dim = DieRow{m->nq, nv}.dim;
   return MYO_OK;
 }
-static const TaskHooks die_hooks = {die_configure, launch_task_obs<DieTask>, launch_task_post<DieTask>};
+static const char* const rwd_die[] = {"pos_dist", "rot_dist", "bonus", "act_reg", "penalty", RWD_TAIL};   // reorient_v0.py:148-176
+static void obs_terms_die(const ObsDims& D, ObsTable& t) {       // reorient_v0.py get_obs_dict
+  const DieRow R{D.nq, D.nv};
+  TERM("time", 1, OBS_SRC_TIME, 0)
+  ROW(R, hand_qpos_noMD5)
+  TERM("hand_qpos", D.nq - 6, OBS_SRC_QPOS, 0)
+  ROW(R, hand_qvel)
+  ROW(R, obj_pos)
+  ROW(R, goal_pos)
+  ROW(R, pos_err)
+  ROW(R, obj_rot)
+  ROW(R, goal_rot)
+  ROW(R, rot_err)
+  TERM("act", D.na, OBS_SRC_ACT, 0)
+  t.dim = R.dim;
+}
+static const TaskHooks die_hooks = {die_configure, launch_task_obs<DieTask>, launch_task_post<DieTask>, RWD_COLS(rwd_die), obs_terms_die};
 
 #endif  // MYO_TASK_DIE_H

@@ -7,11 +7,18 @@
 #ifndef MYO_TASK_PEN_H
 #define MYO_TASK_PEN_H
 
-// pen_v0.py:98-170 (+ act, base_v0.py:34-38).  Row: hand qpos (nq - 6), object position (3), object qvel * dt (6), obj_rot (3), obj_des_rot
-// (3), object position - eps_ball (3), obj_rot - obj_des_rot (3), act (na).  T.tip_site = object top, object bottom, target top, target
-// bottom, eps_ball; T.tip_lpos = the object body's origin in the frame of the link of the last dof.
+// pen_v0.py:98-170 (+ act, base_v0.py:34-38).  Row: hand qpos, object position, object qvel * dt, obj_rot, obj_des_rot, obj_err_pos = object
+// position - eps_ball, obj_err_rot = obj_rot - obj_des_rot, act.  T.tip_site = object top, object bottom, target top, target bottom,
+// eps_ball; T.tip_lpos = the object body's origin in the frame of the link of the last dof.
+struct PenRow {
+  int nq, na;
+  Blk hand_jnt = {0, nq - 6}, obj_pos = hand_jnt.then(3), obj_vel = obj_pos.then(6), obj_rot = obj_vel.then(3), obj_des_rot = obj_rot.then(3),
+      obj_err_pos = obj_des_rot.then(3), obj_err_rot = obj_err_pos.then(3), act = obj_err_rot.then(na);
+  int dim = act.end();
+};
 __device__ __forceinline__ void pen_obs_body(const DevModel& M, const DevBatch& Bt, const TaskDev& T, int obs_only, const int e, const int lane) {
   const int nv = M.nv, nh = nv - 6;
+  const PenRow R{nv, M.na_obs};   // nq == nv (pen_configure)
   const auto [o, q, v, a, dt] = task_row(M, Bt, T, e, nv);
   float p[3] = {0.f, 0.f, 0.f}, x[6][3];
   if (lane < 6) {   // lanes 0-4: the sites, 5: the object body's origin
@@ -31,17 +38,17 @@ __device__ __forceinline__ void pen_obs_body(const DevModel& M, const DevBatch& 
 #pragma unroll
   for (int k = 0; k < 3; k++) { rot[k] = (x[0][k] - x[1][k]) / plen; drot[k] = (x[2][k] - x[3][k]) / tlen; epos[k] = x[5][k] - x[4][k]; }
   if (lane < 3) {
-    o[nh + lane] = x[5][lane];
-    o[nh + 9 + lane] = rot[lane];
-    o[nh + 12 + lane] = drot[lane];
-    o[nh + 15 + lane] = epos[lane];
-    o[nh + 18 + lane] = rot[lane] - drot[lane];
+    o[R.obj_pos.at + lane] = x[5][lane];
+    o[R.obj_rot.at + lane] = rot[lane];
+    o[R.obj_des_rot.at + lane] = drot[lane];
+    o[R.obj_err_pos.at + lane] = epos[lane];
+    o[R.obj_err_rot.at + lane] = rot[lane] - drot[lane];
   }
   for (int i = lane; i < nv; i += 64) {
-    if (i < nh) o[i] = q[i];
-    else o[nh + 3 + (i - nh)] = v[i] * dt;
+    if (i < nh) o[R.hand_jnt.at + i] = q[i];
+    else o[R.obj_vel.at + (i - nh)] = v[i] * dt;
   }
-  const float act2 = act_sq(M, a, lane, o + nh + 21);
+  const float act2 = act_sq(M, a, lane, o + R.act.at);
   if (obs_only) return;
   const float actn = act_norm(M, act2);
   if (lane == 0) {
@@ -72,9 +79,24 @@ static int pen_configure(myo_batch* b, const myo_task_config* c) {
   if (!sites_in_range(m, c, 5)) return fail(MYO_E_ARG, "pen task: site id out of range");
   for (int k = 0; k < 3; k++) if (!std::isfinite(c->tip_lpos[k])) return fail(MYO_E_ARG, "pen task: tip_lpos must be finite");
   if (!(c->far_th > 0.f) || !is_number(c->pose_thd)) return fail(MYO_E_ARG, "pen task: far_th > 0, pose_thd a number");
-  b->task.obs_dim = (nv - 6) + 21 + m->dm.na_obs;
+  b->task.obs_dim = PenRow{m->nq, m->dm.na_obs}.dim;
   return MYO_OK;
 }
-static const TaskHooks pen_hooks = {pen_configure, launch_task_obs<PenTask>, launch_task_post<PenTask>};
+static const char* const rwd_pen[] = {"pos_align", "rot_align", "act_reg", "drop", "bonus", RWD_TAIL};   // pen_v0.py:150-167
+static void obs_terms_pen(const ObsDims& D, ObsTable& t) {       // pen_v0.py get_obs_dict
+  const PenRow R{D.nq, D.na};
+  TERM("time", 1, OBS_SRC_TIME, 0)
+  ROW(R, hand_jnt)
+  ROW(R, obj_pos)
+  TERM("obj_des_pos", 3, OBS_SRC_CONST, 0)
+  ROW(R, obj_vel)
+  ROW(R, obj_rot)
+  ROW(R, obj_des_rot)
+  ROW(R, obj_err_pos)
+  ROW(R, obj_err_rot)
+  ROW(R, act)
+  t.dim = R.dim;
+}
+static const TaskHooks pen_hooks = {pen_configure, launch_task_obs<PenTask>, launch_task_post<PenTask>, RWD_COLS(rwd_pen), obs_terms_pen};
 
 #endif  // MYO_TASK_PEN_H

@@ -3,25 +3,26 @@
 #ifndef MYO_TASK_STAND_H
 #define MYO_TASK_STAND_H
 
-// Row: qpos (nq), qvel * dt (nv), tip position (3), reach_err = target - tip (3), act (na).  T.tip_lpos = the tip site in the root link's
-// frame: world position = root position + R(root quat) tip_lpos
+// Row: ReachRow (myo_task_reach.h) with one tip.  T.tip_lpos = the tip site in the root link's frame: world position = root position +
+// Rm(root quat) tip_lpos
 __device__ __forceinline__ void stand_obs_body(const DevModel& M, const DevBatch& Bt, const TaskDev& T, int obs_only, const int e, const int lane) {
   const int nv = M.nv, nq = T.nq;
+  const ReachRow R{nq, nv, 1, M.na_obs};
   const auto [o, qq, v, a, dt] = task_row(M, Bt, T, e, nq);
   float vel2 = 0.f, err2 = 0.f;
-  for (int i = lane; i < nq; i += 64) o[i] = qq[i];
-  for (int i = lane; i < nv; i += 64) { const float vd = v[i] * dt; o[nq + i] = vd; vel2 += vd * vd; }
+  for (int i = lane; i < nq; i += 64) o[R.qpos.at + i] = qq[i];
+  for (int i = lane; i < nv; i += 64) { const float vd = v[i] * dt; o[R.qvel.at + i] = vd; vel2 += vd * vd; }
   if (lane < 3) {
-    float R[9];
+    float Rm[9];
     const float qn = 1.0f / sqrtf(qq[3] * qq[3] + qq[4] * qq[4] + qq[5] * qq[5] + qq[6] * qq[6]);
     const float uq[4] = {qq[3] * qn, qq[4] * qn, qq[5] * qn, qq[6] * qn};
-    quat2mat(R, uq);
-    const float p = qq[lane] + R[3 * lane] * T.tip_lpos[0] + R[3 * lane + 1] * T.tip_lpos[1] + R[3 * lane + 2] * T.tip_lpos[2] + M.origin[lane];
+    quat2mat(Rm, uq);
+    const float p = qq[lane] + Rm[3 * lane] * T.tip_lpos[0] + Rm[3 * lane + 1] * T.tip_lpos[1] + Rm[3 * lane + 2] * T.tip_lpos[2] + M.origin[lane];
     const float er = Bt.target[(size_t)e * T.ntarget + lane] - p;
-    o[nq + nv + lane] = p; o[nq + nv + 3 + lane] = er;
+    o[R.tip_pos.at + lane] = p; o[R.reach_err.at + lane] = er;
     err2 = er * er;
   }
-  const float act2 = act_sq(M, a, lane, o + nq + nv + 6);
+  const float act2 = act_sq(M, a, lane, o + R.act.at);
   if (obs_only) return;
   const float dist = sqrtf(wave_sum(err2)), veld = sqrtf(wave_sum(vel2));
   const float actn = act_norm(M, act2);
@@ -43,9 +44,9 @@ static int stand_configure(myo_batch* b, const myo_task_config* c) {
   const int nv = m->dm.nv, nq = m->nq;
   if (c->ntarget != 3) return fail(MYO_E_ARG, "stand task: ntarget must be 3 (target position)");
   if (!(m->wave_ok && m->dw.has_free && nq == nv + 1)) return fail(MYO_E_UNSUPPORTED, "stand task needs a model with a free root joint");
-  b->task.obs_dim = nq + nv + 6 + m->dm.na_obs;
+  b->task.obs_dim = ReachRow{nq, nv, 1, m->dm.na_obs}.dim;
   return MYO_OK;
 }
-static const TaskHooks stand_hooks = {stand_configure, launch_task_obs<StandTask>, launch_task_post<StandTask>};
+static const TaskHooks stand_hooks = {stand_configure, launch_task_obs<StandTask>, launch_task_post<StandTask>, RWD_COLS(rwd_reach), obs_terms_reach};
 
 #endif  // MYO_TASK_STAND_H

@@ -98,6 +98,14 @@ __device__ __forceinline__ float act_sq(const DevModel& M, const float* a, int l
 __device__ __forceinline__ float act_sq(const DevModel& M, const float* a, int lane, float* o_act) { return act_sq_lane<true>(M, a, lane, o_act); }
 __device__ __forceinline__ float act_norm(const DevModel& M, float act2) { return sqrtf(wave_sum(act2)) / (float)(M.na_obs > 0 ? M.na_obs : 1); }
 
+// host: how a task file states its two tables (RwdCols, ObsTable: myo_host.h).  Every reward row ends sparse, solved, done, dense.  A term of
+// the canonical row is ROW(R, block): the block's name is the key, its width and offset come from the row record R; a term from outside the
+// row is TERM(key, width, source, index).  Both fill `t`; a table function ends with t.dim = R.dim
+#define RWD_TAIL "sparse", "solved", "done", "dense"
+#define RWD_COLS(a) RwdCols{a, (int)(sizeof a / sizeof a[0])}
+#define TERM(name, width, src, idx) t.push_back(ObsTerm{name, width, src, idx});
+#define ROW(R, block) TERM(#block, R.block.n, OBS_SRC_ROW, R.block.at)
+
 // host: the checks of the *_configure functions (each caller refuses with its own text).  trk_model: a TrackEnv-class model whose qpos row is nq_extra wider than its qvel row (0: hinge / slide joints only, what link_chain walks)
 static bool trk_model(const myo_model* m, int nq_extra = 0) { return m->wave_ok && m->trk && m->nq == m->dm.nv + nq_extra; }
 static bool sites_in_range(const myo_model* m, const myo_task_config* c, int n) {

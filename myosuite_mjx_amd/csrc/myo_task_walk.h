@@ -18,7 +18,7 @@ static int walk_configure(myo_batch* b, const myo_walk_config* c) {
   for (int k = 0; k < 6; k++) if (qa[k] < 0 || qa[k] >= nq) return fail(MYO_E_ARG, "walk task: bad qpos address");
   if (c->frame_skip <= 0 || c->hip_period <= 0 || !c->init_qpos) return fail(MYO_E_ARG, "walk task: frame_skip, hip_period, init_qpos required");
   DevWalk w{};
-  w.obs_dim = (nq - 2) + nv + 16 + 4 * nu;
+  w.obs_dim = WalkRow{nq, nv, nu}.dim;
   if (w.obs_dim > b->obs_alloc) return fail(MYO_E_ARG, "obs_dim too large");
   w.hip_period = c->hip_period; w.dt = (float)c->frame_skip * dm.timestep;
   w.min_height = c->min_height; w.max_rot = c->max_rot; w.target_x_vel = c->target_x_vel; w.target_y_vel = c->target_y_vel;
@@ -58,6 +58,25 @@ static int walk_configure(myo_batch* b, const myo_walk_config* c) {
 static int walk_obs(myo_batch* b, hipStream_t s, int obs_only, int reset_only) {
   return launch_step(b, nullptr, MYO_ACTMAP_NONE, 0, s, KF_AUX | (obs_only ? KF_OBS_ONLY : 0) | (reset_only ? KF_RESET_ONLY : 0));
 }
-static const TaskHooks walk_hooks = {nullptr, walk_obs, nullptr};
+static const char* const rwd_walk[] = {"vel_reward", "cyclic_hip", "ref_rot", "joint_angle_rew", "act_mag", RWD_TAIL};   // walk_v0.py:298-311
+static void obs_terms_walk(const ObsDims& D, ObsTable& t) {      // walk_v0.py WalkEnvV0 get_obs_dict (TerrainEnvV0 inherits it); WalkRow: myo_common.h
+  const WalkRow R{D.nq, D.nv, D.nu};
+  TERM("t", 1, OBS_SRC_TIME, 0)
+  TERM("time", 1, OBS_SRC_TIME, 0)
+  ROW(R, qpos_without_xy)
+  ROW(R, qvel)
+  ROW(R, com_vel)
+  ROW(R, torso_angle)
+  ROW(R, feet_heights)
+  ROW(R, height)
+  ROW(R, feet_rel_positions)
+  ROW(R, phase_var)
+  ROW(R, muscle_length)
+  ROW(R, muscle_velocity)
+  ROW(R, muscle_force)
+  ROW(R, act)
+  t.dim = R.dim;
+}
+static const TaskHooks walk_hooks = {nullptr, walk_obs, nullptr, RWD_COLS(rwd_walk), obs_terms_walk};
 
 #endif  // MYO_TASK_WALK_H

@@ -259,6 +259,7 @@ template <class C, class LY> __device__ __forceinline__ float w_tendons(const Wa
     for (int i = lane; i < nu; i += 64) { Bt.tenlen[(size_t)env * nu + i] = E[Y.tlen + i]; Bt.actforce[(size_t)env * nu + i] = E[Y.tforce + i]; }
   }
   if (FULL && op) {   // walk observation, muscle block (walk_v0.py:283-285,354-361): length, clipped velocity, clipped force / 1000, then act
+    // (WalkRow's muscle_length .. act, myo_common.h; the offsets stay spelled out here: through the record the step kernels' code changes)
     float* o = Bt.obs + (size_t)env * wk->obs_dim + (nq - 2 + nv + 16);
 #pragma unroll
     for (int rr = 0; rr < NTR; rr++) {
@@ -387,7 +388,8 @@ template <class C, class LY> __device__ __forceinline__ bool w_dynamics(const Wa
   }
   SYNC();
   if (FULL && op) {
-    // ---- walk observation / reward (walk_v0.py:268-316, 363-470) from link frames and link velocities of this pass
+    // ---- walk observation / reward (walk_v0.py:268-316, 363-470) from link frames and link velocities of this pass; the row is WalkRow's
+    // qpos_without_xy .. phase_var (myo_common.h), its offsets spelled out here for the same reason (tests/test_gpu_task_rows.py holds the two together)
     float* o = Bt.obs + (size_t)env * wk->obs_dim;
     if (lane < nq - 2) o[lane] = E[Y.qpos + 2 + lane];                    // qpos_without_xy
     if (lane < nv) o[nq - 2 + lane] = E[Y.qvel + lane] * wk->dt;          // qvel * dt

@@ -319,14 +319,13 @@ class BatchedMyoEnv(capi.FieldViews):
             getattr(self.batch, name)(*args)
         if s.body_mass_range is not None:
             self.set_body_mass_range(*s.body_mass_range)
-        self.obs_dim = s.obs_dim
         if self.rwd_dict:      # nothing is allocated and no launch is added without it
             keys, w, mode = self._rwd
             assert self.batch.rwd_names() == keys, (self.batch.rwd_names(), keys)
             self.batch.enable_rewards(w, capi.RWD_SPARSE if mode == "sparse" else capi.RWD_DENSE)
             if self.episode_stats:
                 self.batch.enable_episode_stats()
-        self._setup_obs_terms(m, spec, s.obs_dim)
+        self._setup_obs_terms(m, spec)
         self._obs_in_step = s.call == "configure_walk"                 # the walk task's observation / reward pass is fused into the step kernel
         self._set_condition(m, spec)
         self.act_dim = m.nu
@@ -340,14 +339,14 @@ class BatchedMyoEnv(capi.FieldViews):
             self._torch = torch
             self._action_buf = torch.empty((self.num_envs, m.nu), dtype=torch.float32, device=f"cuda:{device}")
 
-    def _setup_obs_terms(self, m, spec, canonical_dim):
-        """obs_keys / proprio_keys / obs_dim of this env, and with any of the three parameters given the library's rows.  The default keys
-        must restate the canonical row (host arithmetic, checked for every env)."""
+    def _setup_obs_terms(self, m, spec):
+        """obs_keys / proprio_keys / obs_dim of this env, and with any of the three parameters given the library's rows.  The canonical row
+        (MYO_F_OBS) is the concatenation of the default keys, so its width is the sum of theirs (tests/test_obs_terms_host.py holds that sum
+        to the library's row record for every registered id)."""
         task, d = spec["task"], observations.dims(m, spec)
         self._obs_width = width = observations.widths(task, d)
         default = observations.default_keys(task, d["na"])
-        assert sum(width[k] for k in default) == canonical_dim, (self.id, default, width, canonical_dim)
-        self.canonical_obs_dim = canonical_dim
+        self.canonical_obs_dim = sum(width[k] for k in default)
         sel = self._obs_sel
         self.obs_keys = list(default if sel is None or sel.obs_keys is None else observations.with_act(task, sel.obs_keys, d["na"]))
         self.proprio_keys = None if sel is None or sel.proprio_keys is None else list(sel.proprio_keys)
@@ -682,11 +681,7 @@ def myodm_spec(env_id, flavour="mjx", reference=None):
         raise KeyError(f"{env_id} is not a MyoDM id")
     m = _model.load_asset(f"myohand_object_{spec['object']}")
     ref = track.ReferenceMotion(_myodm_reference(env_id, reference))
-    nr = ref.robot_dim
-    if flavour == "classic":     # qp, qv, hand_qpos_err, hand_qvel_err ([0] without robot_vel), obj_com_err, act (base_v0.py:34-38)
-        obs_dim = m.nq + m.nv + nr + (nr if ref.reference["robot_vel"] is not None else 1) + 3 + m.n_muscle
-    else:
-        obs_dim = m.nq + m.nv
+    obs_dim = track.classic_obs_dim(m, ref) if flavour == "classic" else m.nq + m.nv
     return dict(frame_skip=10 if flavour == "classic" else 5, obs_dim=obs_dim, act_dim=m.nu, init_qpos=track.myodm_init_qpos(m, ref),
                 max_episode_steps=spec["max_episode_steps"], ref_type=ref.type)
 

@@ -3,8 +3,9 @@ constructor parameters (`obs_keys`, `proprio_keys`, `obs_dict`) -- host arithmet
 
 The terms are the keys of the reference's `get_obs_dict` for the task's env class, in its order (pose_v0.py, reach_v0.py, obj_hold_v0.py,
 key_turn_v0.py, pen_v0.py, walk_v0.py ReachEnvV0 and WalkEnvV0, baoding_v1.py, reorient_v0.py); each carries its width as an expression of
-the model's dimensions (`dims`).  The library carries the same table (csrc/myo_obs_terms.h, the same names and the same width expressions)
-and tests/golden/obs_terms.json pins the names and the default keys to the reference's text."""
+the model's dimensions (`dims`).  The library builds its table from each task's row record (csrc/myo_task_<name>.h; capi.obs_term_table
+reads it without a GPU): tests/test_obs_terms_host.py holds the names and widths here, and the default keys as the row's blocks in order,
+to it by value for every registered id; tests/golden/obs_terms.json pins the names and the default keys to the reference's text."""
 from __future__ import annotations
 
 # (key, width): an expression of nq, nv, nu, na (muscles), ntip (reach tips) and pose_act (na, or nq for a model without muscles: PoseEnvV0

@@ -1,8 +1,9 @@
 """One record per task of the batched envs: the Python counterpart of the library's `TaskHooks` records (csrc/myo_host.h).
 
 A `Task` names the env kwargs its task accepts on top of COMMON_KWARGS, the kwargs it refuses (with the reason), and `setup(m, spec, env_id)`:
-host arithmetic only (init pose, noise / clip vectors, goal ranges, site ids, obs_dim), no `capi` handle.  `setup` returns a `Setup`: the binding
-call to make with its keyword arguments, and the calls that follow it.  `BatchedMyoEnv.__init__` (envs.py) looks the record up, filters the kwargs
+host arithmetic only (init pose, noise / clip vectors, goal ranges, site ids), no `capi` handle.  `setup` returns a `Setup`: the binding
+call to make with its keyword arguments, and the calls that follow it (the width of the observation row is not among them: it is the sum of
+the default keys' widths, observations.py).  `BatchedMyoEnv.__init__` (envs.py) looks the record up, filters the kwargs
 with `filter_kwargs` and applies the `Setup`; a new task is one `setup` function and one entry of TASKS, next to its registry entries in envs.py."""
 from __future__ import annotations
 
@@ -17,7 +18,6 @@ COMMON_KWARGS = ("reset_type", "fatigue_reset_random", "fatigue_reset_vec")     
 
 class Setup(NamedTuple):
     call: str                      # "configure" or "configure_walk" (capi.HipBatch)
-    obs_dim: int
     kwargs: dict                   # the call's keyword arguments
     then: tuple = ()               # HipBatch calls after it, in order: (method, args) of set_body_pos_range / set_body_quat_range / set_geom_override
     body_mass_range: tuple = None  # (body, lo, hi) for BatchedMyoEnv.set_body_mass_range (PoseEnvV0 weight_bodyname / weight_range)
@@ -62,7 +62,7 @@ def _pose(m, spec, env_id):
         if spec.get("weight_range") is None:
             raise ValueError(f"{env_id}: weight_bodyname needs weight_range")
         mass = (spec["weight_bodyname"], *spec["weight_range"])
-    return Setup("configure", 3 * m.nq + m.n_muscle, dict(
+    return Setup("configure", dict(
         task=capi.TASK_POSE, frame_skip=spec["frame_skip"],
         reset_random=spec["reset_type"] == "random", target_generate=spec["target_type"] == "generate",
         target_lo=spec["target_lo"], target_hi=spec["target_hi"], init_qpos=m.qpos0, pose_thd=spec["pose_thd"], far_th=4 * np.pi / 2,
@@ -73,7 +73,7 @@ def _reach(m, spec, env_id):
     w = spec["weights"]
     tips = [m.name2id("site", t) for t in spec["tips"]]
     n = len(tips)
-    return Setup("configure", 2 * m.nq + 6 * n + m.n_muscle, dict(
+    return Setup("configure", dict(
         task=capi.TASK_REACH, frame_skip=spec["frame_skip"], reset_random=0, target_generate=spec["target_type"] == "generate",
         target_lo=spec["target_lo"], target_hi=spec["target_hi"], init_qpos=m.qpos0, tip_sites=tips, far_th=spec["far_th"] * n, near_th=0.0125 * n,
         w_reach=w["reach"], w_bonus=w["bonus"], w_act_reg=w["act_reg"], w_penalty=w["penalty"]))
@@ -89,7 +89,7 @@ def _walk(m, spec, env_id):
         raise NotImplementedError("myoLegWalk: reset_type 'init' (keyframe 2) or 'random' (walk_v0.py:316-332)")
     rnd = spec["reset_type"] == "random"
     jadr = lambda n: int(m.jnt_qposadr[m.name2id("joint", n)])
-    return Setup("configure_walk", (m.nq - 2) + m.nv + 16 + 4 * m.nu, dict(
+    return Setup("configure_walk", dict(
         frame_skip=spec["frame_skip"], hip_period=spec["hip_period"], min_height=spec["min_height"], max_rot=spec["max_rot"],
         target_x_vel=spec["target_x_vel"], target_y_vel=spec["target_y_vel"],
         target_rot=spec["target_rot"] if spec["target_rot"] is not None else key_qpos[0][3:7],
@@ -121,7 +121,7 @@ def _stand(m, spec, env_id):
     q0 = np.clip(init[:7] + 0.0, np.r_[clo[:1], [-1e30] * 6], np.r_[chi[:1], [1e30] * 6])
     p0 = q0[:3] + quat2mat(q0[3:7] / np.linalg.norm(q0[3:7])) @ lpos     # generate_targets (:140-149): the site in the first random pose
     span = np.asarray(spec["target_span"], float)
-    return Setup("configure", m.nq + m.nv + 6 + m.n_muscle, dict(
+    return Setup("configure", dict(
         task=capi.TASK_STAND, frame_skip=spec["frame_skip"], reset_random=0, target_generate=1,
         target_lo=p0 + span[0], target_hi=p0 + span[1], init_qpos=init, init_qvel=key_qvel[0],
         reset_noise=(nlo, nhi), reset_clip=(clo, chi), tip_lpos=lpos, near_th=spec["near_th"], far_th=spec["far_th"],
@@ -135,7 +135,7 @@ def _hold(m, spec, env_id):
     else:
         glo = ghi = np.asarray(spec["goal"], float)
     then = (("set_geom_override", (m.name2id("geom", "object"), *spec["object_size"])),) if "object_size" in spec else ()
-    return Setup("configure", (m.nq - 7) + (m.nv - 6) + 6 + m.n_muscle, dict(
+    return Setup("configure", dict(
         task=capi.TASK_HOLD, frame_skip=spec["frame_skip"], reset_random=0, target_generate=int(spec["goal"] is None),
         target_lo=glo, target_hi=ghi, init_qpos=_open_hand(m, 7, -1.5), near_th=spec["goal_th"], far_th=spec["drop_th"],       # obj_hold_v0.py:63-64
         w_reach=w["goal_dist"], w_bonus=w["bonus"], w_act_reg=w["act_reg"], w_penalty=w["penalty"]), then)
@@ -153,7 +153,7 @@ def _keyturn(m, spec, env_id):
     big = np.full(m.nq, 1e30)
     # key_turn_v0.py:164-167: key_init_pos + U(-0.01, 0.01)^3
     then = (("set_body_pos_range", (np.full(3, -0.01), np.full(3, 0.01))),) if lo_k != hi_k else ()
-    return Setup("configure", 2 * m.nq + 6 + m.n_muscle, dict(
+    return Setup("configure", dict(
         task=capi.TASK_KEYTURN, frame_skip=spec["frame_skip"], reset_random=0, target_generate=0, init_qpos=np.zeros(m.nq),
         reset_noise=(nlo, nhi), reset_clip=(-big, big), tip_sites=[m.name2id("site", n) for n in ("keyhead", "IFtip", "THtip")],
         pose_thd=float(spec["goal_th"]), near_th=0.030, far_th=0.1,
@@ -166,7 +166,7 @@ def _pen(m, spec, env_id):
     w = spec["weights"]
     ob = m.name2id("body", "Object")
     then = (("set_body_quat_range", tuple(spec["target_euler_range"])),) if spec.get("target_euler_range") is not None else ()
-    return Setup("configure", (m.nq - 6) + 21 + m.n_muscle, dict(
+    return Setup("configure", dict(
         task=capi.TASK_PEN, frame_skip=spec["frame_skip"], reset_random=0, target_generate=0, init_qpos=_open_hand(m, 6, -1.5),
         tip_sites=[m.name2id("site", n) for n in ("object_top", "object_bottom", "target_top", "target_bottom", "eps_ball")],
         tip_lpos=tuple(np.asarray(m.hip_body_lpos).reshape(-1, 3)[ob]), pose_thd=0.95, far_th=0.075,
@@ -187,7 +187,7 @@ def _baoding(m, spec, env_id):
         raise ValueError(f"{env_id}: goal_time_period, goal_xrange and goal_yrange must be (lo, hi) with lo <= hi (periods > 0)")
     glo = [0.0 if rnd else np.pi / 4, -1.0 if rnd else 1.0, x0, y0, p0]
     ghi = [2 * np.pi if rnd else np.pi / 4, 2.0 if rnd else 1.0, x1, y1, p1]
-    return Setup("configure", (m.nq - 14) + 24, dict(
+    return Setup("configure", dict(
         task=capi.TASK_BAODING, frame_skip=spec["frame_skip"], reset_random=0, target_generate=1, target_lo=glo, target_hi=ghi,
         init_qpos=_open_hand(m, 14, -1.57), tip_sites=[m.name2id("site", n) for n in ("ball1_site", "ball2_site", "target1_site", "target2_site")],
         pose_thd=float(spec["proximity_th"]), far_th=float(spec["drop_th"]), w_pose=w["pos_dist_1"], w_reach=w["pos_dist_2"]))
@@ -201,7 +201,7 @@ def _die(m, spec, env_id):
     (p0, p1), (r0, r1) = ((float(a) for a in spec[k]) for k in ("goal_pos", "goal_rot"))
     if not (p0 <= p1 and r0 <= r1):
         raise ValueError(f"{env_id}: goal_pos and goal_rot must be (lo, hi) with lo <= hi")
-    return Setup("configure", (m.nq - 7) + (m.nv - 6) + 18, dict(
+    return Setup("configure", dict(
         task=capi.TASK_DIE, frame_skip=spec["frame_skip"], reset_random=0, target_generate=1, target_lo=[p0] * 3, target_hi=[p1] * 3,
         init_qpos=_open_hand(m, 7, -1.5),
         tip_sites=[m.name2id("site", n) for n in ("object_o", "object_x", "object_y", "object_z", "target_o", "target_x", "target_y", "target_z")],

@@ -53,7 +53,7 @@ def test_every_case_makes_the_same_calls_with_the_same_bytes(recorded):
 
 
 def test_setup_of_every_task_runs_without_any_capi_object(monkeypatch):
-    """`setup(m, spec, env_id)` is host arithmetic: with HipModel / HipBatch unusable it still returns the call, obs_dim and follow-ups."""
+    """`setup(m, spec, env_id)` is host arithmetic: with HipModel / HipBatch unusable it still returns the call and its follow-ups."""
     from myosuite_mjx_amd import capi, envs, model as M, tasks
 
     def unusable(*a, **k):
@@ -68,7 +68,7 @@ def test_setup_of_every_task_runs_without_any_capi_object(monkeypatch):
             continue
         m = M.load_asset(spec["model"])
         s = tasks.TASKS[spec["task"]].setup(m, dict(spec), env_id)
-        assert s.call == ("configure_walk" if spec["task"] == "walk" else "configure") and isinstance(s.obs_dim, int) and s.obs_dim > 0
+        assert s.call == ("configure_walk" if spec["task"] == "walk" else "configure")
         assert hasattr(real, s.call) and all(name in ("set_body_pos_range", "set_body_quat_range", "set_geom_override") for name, _ in s.then)
         assert s.kwargs["frame_skip"] == spec["frame_skip"]
         seen.setdefault(spec["task"], s)

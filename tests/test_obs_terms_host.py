@@ -1,8 +1,9 @@
 """CPU tests of the observation terms (obs_dict / obs_keys / proprio_keys of the batched envs): the term table and the default keys
-against the reference's text (tests/golden/obs_terms.json), the default keys' widths against every registered id's obs_dim, the library's
-copy of the table, the binding of include/myo_hip_obs.h, the constructor parameters' validation without a GPU, obsvec2obsdict on a numpy
+against the reference's text (tests/golden/obs_terms.json), the default keys' widths against every registered id's recorded obs_dim, the
+library's table by value (myo_obs_term_table), the binding of include/myo_hip_obs.h, the constructor parameters' validation without a GPU, obsvec2obsdict on a numpy
 array, and the register / scratch figures of the one kernel the feature adds."""
 import ctypes
+import gzip
 import json
 import os
 import re
@@ -47,10 +48,22 @@ def test_fixture_equals_a_fresh_parse(fixture):
     assert T.parse(REFERENCE) == fixture
 
 
-def test_default_keys_restate_every_registered_row():
-    """For every registered id outside MyoDM: the default keys (with `act` where base_v0.py appends it) are as wide as the obs_dim its
-    task's setup returns -- the canonical row is the concatenation of the default keys."""
-    from myosuite_mjx_amd import envs, model as M, observations as O, tasks
+@pytest.fixture(scope="module")
+def recorded_obs_dim():
+    """{env id: obs_dim} of the 129 non-MyoDM ids as tests/golden/env_setup_calls.json.gz recorded them, before tasks.py and before the row
+    records (tests/test_env_setup_host.py): not a product of the code under test."""
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "env_setup_calls.json.gz"), "rt") as f:
+        golden = json.load(f)
+    from myosuite_mjx_amd import envs
+    out = {i: golden[i]["attrs"]["obs_dim"] for i, reg in envs.REGISTRY.items() if reg["task"] != "track"}
+    assert len(out) == 129 and all(isinstance(v, int) and v > 0 for v in out.values())
+    return out
+
+
+def test_default_keys_restate_every_registered_row(recorded_obs_dim):
+    """For every registered id outside MyoDM: the default keys (with `act` where base_v0.py appends it) are as wide as the obs_dim recorded
+    for the id -- the canonical row is the concatenation of the default keys."""
+    from myosuite_mjx_amd import envs, model as M, observations as O
     n = 0
     for env_id, reg in envs.REGISTRY.items():
         if reg["task"] == "track":
@@ -60,7 +73,7 @@ def test_default_keys_restate_every_registered_row():
         d = O.dims(m, spec)
         w = O.widths(spec["task"], d)
         keys = O.default_keys(spec["task"], d["na"])
-        assert sum(w[k] for k in keys) == tasks.TASKS[spec["task"]].setup(m, spec, env_id).obs_dim, env_id
+        assert sum(w[k] for k in keys) == recorded_obs_dim[env_id], env_id
         assert ("act" in keys) == (d["na"] > 0 and spec["task"] not in O.NO_ACT_APPENDED), env_id
         assert all(v >= 0 for v in w.values()) and w["time"] == 1, env_id
         n += 1
@@ -70,18 +83,49 @@ def test_default_keys_restate_every_registered_row():
     assert d["na"] == 0 and O.widths("pose", d)["act"] == m.nq and O.widths("reach", dict(d, ntip=1))["act"] == 0
 
 
-def test_library_term_table_equals_the_python_one():
-    """csrc/myo_obs_terms.h carries the names and the width expressions for myo_batch_obs_term_name / _width; BatchedMyoEnv asserts they
-    agree when it enables the rows.  Here the two texts are compared: per task function, the TERM(name, width, ...) lines in order."""
-    from myosuite_mjx_amd import observations as O
-    src = open(os.path.join(ROOT, "myosuite_mjx_amd", "csrc", "myo_obs_terms.h")).read()
-    rows = {n: [(k, " ".join(w.replace("D.", "").split())) for k, w in re.findall(r'TERM\("(\w+)",\s*([^,]+),', body)]
-            for n, body in re.findall(r"static void obs_terms_(\w+)\(const ObsDims& D, ObsTable& t\) \{(.*?)\n\}", src, flags=re.S)}
-    assert sorted(rows) == sorted(set(O.OBS_TERMS) - {"stand"})              # reach and stand share one C function
-    for task, terms in O.OBS_TERMS.items():
-        assert rows["reach" if task == "stand" else task] == [tuple(t) for t in terms], task
-    fields = re.search(r"struct ObsDims \{ int ([^;]*); \}", src).group(1).replace(" ", "").split(",")
-    assert fields == ["nq", "nv", "nu", "na", "ntip", "pose_act"]             # what observations.dims provides
+def _check_library_table(task, d, obs_dim=None):
+    """The library's table of `task` for the dimensions `d` (myo_obs_term_table: no batch, no GPU) against observations.py, by value."""
+    from myosuite_mjx_amd import capi, observations as O
+    terms, dim = capi.obs_term_table(getattr(capi, "TASK_" + task.upper()), **d)      # (observations.dims names the export's six arguments)
+    assert [(k, w) for k, w, _ in terms] == list(O.widths(task, d).items()), (task, d)
+    # the canonical row: the terms that lie in it, by offset, are the default keys in order, end to end
+    blocks = sorted((at, k, w) for k, w, at in terms if at >= 0 and w > 0)
+    keys = O.with_act(task, O.DEFAULT_OBS_KEYS[task], d["na"])
+    assert tuple(k for _, k, _ in blocks) == keys, (task, d)
+    assert [at for at, _, _ in blocks] == [sum(w for _, _, w in blocks[:i]) for i in range(len(blocks))], (task, d)
+    assert dim == sum(w for _, _, w in blocks) and (obs_dim is None or dim == obs_dim), (task, d, dim, obs_dim)
+    return terms, dim
+
+
+def test_library_term_table_equals_the_python_one(recorded_obs_dim):
+    """The library states each task's row once, as a record of its blocks (csrc/myo_task_<name>.h), and builds its term table from it;
+    BatchedMyoEnv asserts names and widths agree when it enables the rows.  Here, for every registered id outside MyoDM, the library's
+    names and widths equal observations.widths, the default keys are the row's blocks in order at the running sum of their widths, and the
+    row's total is the obs_dim recorded for the id."""
+    from myosuite_mjx_amd import capi, envs, model as M, observations as O
+    if not os.path.exists(capi.LIB_PATH):
+        capi.build_library()
+    seen = set()
+    for env_id, reg in envs.REGISTRY.items():
+        if reg["task"] == "track":
+            continue
+        spec = dict(reg)
+        _check_library_table(spec["task"], O.dims(M.load_asset(spec["model"]), spec), recorded_obs_dim[env_id])
+        seen.add(spec["task"])
+    assert seen == set(O.OBS_TERMS)
+    d = O.dims(M.load_asset("motorfinger_v0"), envs.REGISTRY["motorFingerPoseFixed-v0"])       # no muscles
+    terms, dim = _check_library_table("pose", d)
+    assert ("act", d["nq"], -1) in terms and dim == 3 * d["nq"]              # zeros_like(qpos): as wide as qpos, from outside the row
+    terms, dim = _check_library_table("reach", dict(d, ntip=1))
+    assert ("act", 0) in [(k, w) for k, w, _ in terms] and dim == 2 * d["nq"] + 6
+    # what lies outside the rows (tests/test_gpu_obs_terms.py reads these from their sources)
+    outside = lambda task: {k for k, _, at in capi.obs_term_table(getattr(capi, "TASK_" + task.upper()), **O.dims(
+        M.load_asset(envs.REGISTRY[IDS[task]]["model"]), envs.REGISTRY[IDS[task]]))[0] if at < 0}
+    assert outside("pen") == {"time", "obj_des_pos"} and outside("die") == {"time", "hand_qpos", "act"} and outside("walk") == {"t", "time"}
+    assert outside("reach") == outside("stand") == {"time", "target_pos"} and outside("baoding") == {"time", "act"}
+    # no table: no task, the MyoDM track task, an id out of range
+    for task in (capi.TASK_NONE, capi.TASK_TRACK, 99, -1):
+        assert capi.obs_term_table(task, **d) == ((), 0)
 
 
 def test_binding_matches_the_header():
@@ -91,7 +135,7 @@ def test_binding_matches_the_header():
     protos = {}
     for ret, name, args in re.findall(r"^[ \t]*((?:const\s+)?\w+[\s*]+)(myo_[a-z0-9_]+)\s*\(([^;{}]*?)\)\s*;", TC._header_text("myo_hip_obs.h"), flags=re.M):
         protos[name] = (TC._c_kind(ret), [TC._c_kind(a) for a in args.split(",")])
-    assert sorted(protos) == sorted(capi.OBS_SIGNATURES) and len(protos) == 6
+    assert sorted(protos) == sorted(capi.OBS_SIGNATURES) and len(protos) == 7
     for name, (ret, args) in protos.items():
         restype, argtypes = capi.OBS_SIGNATURES[name]
         assert (TC._ctypes_kind(restype), [TC._ctypes_kind(t) for t in argtypes]) == (ret, args), name

@@ -48,9 +48,10 @@ def test_fixture_equals_a_fresh_parse(fixture):
 
 
 def test_library_column_table_equals_the_python_one():
-    """csrc/myo_rewards.h carries the names for myo_batch_rwd_name; BatchedMyoEnv asserts they agree when it enables the row."""
+    """Each csrc/myo_task_<name>.h carries its task's names for myo_batch_rwd_name; BatchedMyoEnv asserts they agree when it enables the row."""
+    import glob
     from myosuite_mjx_amd import rewards
-    src = open(os.path.join(ROOT, "myosuite_mjx_amd", "csrc", "myo_rewards.h")).read()
+    src = "".join(open(p).read() for p in sorted(glob.glob(os.path.join(ROOT, "myosuite_mjx_amd", "csrc", "myo_task_*.h"))))
     rows = {n: [x.strip().strip('"') for x in body.replace("RWD_TAIL", ", ".join(f'"{k}"' for k in rewards.TAIL)).split(",")]
             for n, body in re.findall(r"rwd_(\w+)\[\] = \{([^}]*)\}", src)}
     assert sorted(rows) == sorted(set(rewards.RWD_KEYS) - {"stand"})        # reach and stand share one C row

@@ -93,6 +93,62 @@ __device__ __host__ inline float u01(uint64_t seed, uint64_t a, uint64_t b) {
   z = z ^ (z >> 31);
   return (float)(z >> 40) * (1.0f / 16777216.0f);
 }
+// Every stream drawn anywhere in the library, one row each: X(name, salt, id, stride, offset, what is drawn).  Draw `index` of global env ge is
+//   u01(seed ^ salt, ge * stride + offset + index, id)
+// salt 0: the seed is used bare.  The streams of a reset (ids 1 to 12) take the episode's seed, rng_episode_seed(seed of the reset, episode).
+// RNG_ID_STEP / RNG_ID_ENV_STEP: the id is not fixed, it is the caller's step counter / 4 * the env's step + the sub-draw (robot, robot_vel,
+// object).  The static_assert below holds every (salt, id) pair of the table apart; a counter id can still meet a fixed one (the policy's step
+// 10 and the body offset share a salt), and there only the seeds of the two callers and the counter layouts differ.
+// Every draw goes through rng_u below (obj_draw_u included) but RS_TRACK_REF's: track_lookup (myo_task_track.h) still spells that key itself,
+// because the TRK step kernel's instruction text changed when it was respelled.
+// myosuite_mjx_amd/objects.py repeats RS_OBJECT's salt and RNG_EPISODE_MUL (tests/test_rng_streams_host.py compares them)
+#define RNG_ID_STEP (~0ull)
+#define RNG_ID_ENV_STEP (~1ull)
+#define RNG_EPISODE_MUL 0x632BE59BD9B4E019ull   /* the seed of episode k of an env = seed + RNG_EPISODE_MUL * k */
+#define MYO_RNG_STREAMS(X)                                                                                                                  \
+  X(RS_QPOS,              0,                     1,  4096,  0,    "qpos coordinate: uniform joint draw (pose), uniform noise (stand)")            \
+  X(RS_TARGET,            0,                     2,  4096,  2048, "component of the target row")                                                  \
+  X(RS_TERRAIN_ROUGH,     0x9E3779B97F4A7C15ull, 3,  16384, 0,    "cell of the rough terrain")                                                    \
+  X(RS_TERRAIN_SCALE,     0x9E3779B97F4A7C15ull, 4,  16384, 0,    "height of the hilly / stairs terrain")                                         \
+  X(RS_GEOM_SIZE,         0xD1B54A32D192ED03ull, 5,  8,     0,    "axis of the hold task's geom size")                                            \
+  X(RS_KEYFRAME_COIN,     0xA24BAED4963EE407ull, 6,  1,     0,    "walk reset_type random: the keyframe")                                         \
+  X(RS_KEYFRAME_NOISE_U1, 0x9FB21C651E98DF25ull, 7,  4096,  0,    "... normal noise on a qpos coordinate, Box-Muller radius")                     \
+  X(RS_KEYFRAME_NOISE_U2, 0x2545F4914F6CDD1Dull, 7,  4096,  0,    "... and angle")                                                                \
+  X(RS_FATIGUE_NF,        0x94D049BB133111EBull, 8,  4096,  0,    "fatigue_reset_random: non-fatigued share of an actuator")                      \
+  X(RS_FATIGUE_AP,        0xBF58476D1CE4E5B9ull, 8,  4096,  0,    "... and the active share of it")                                               \
+  X(RS_BODY_MASS,         0x3C6EF372FE94F82Bull, 9,  4096,  0,    "mass of a body (MYO_F_BODYMASS_RANGE)")                                        \
+  X(RS_BODY_OFFSET,       0x5851F42D4C957F2Dull, 10, 8,     0,    "component of the root-body offset (MYO_F_BODYPOS_RANGE)")                      \
+  X(RS_BODY_QUAT,         0x2545F4914F6CDD1Dull, 11, 8,     0,    "Euler angle of the body orientation (MYO_F_BODYQUAT_RANGE)")                   \
+  X(RS_OBJECT,            0x7A5662DCDF6B1F6Dull, 12, 1024,  0,    "object parameters: OBJ_MAX_DRAWS shared draws, then one per scalar parameter") \
+  X(RS_POLICY_U1,         0x5851F42D4C957F2Dull, RNG_ID_STEP, 1024, 0, "policy sampling, action component: Box-Muller radius")                    \
+  X(RS_POLICY_U2,         0x14057B7EF767814Full, RNG_ID_STEP, 1024, 0, "... and angle")                                                           \
+  X(RS_RANDOM_ACTION,     0,                     RNG_ID_STEP, 1024, 0, "myo_random_action, action component")                                     \
+  X(RS_TRACK_REF,         0,                     RNG_ID_ENV_STEP, 4096, 0, "MyoDM RANDOM reference: lane of the reference row")
+enum RngStream {
+#define X(name, ...) name,
+  MYO_RNG_STREAMS(X)
+#undef X
+  RS_COUNT
+};
+struct RngStreamRec { uint64_t salt, id, stride, offset; const char* what; };
+constexpr RngStreamRec RNG_STREAMS[RS_COUNT] = {
+#define X(name, salt, id, stride, offset, what) {salt, id, stride, offset, what},
+  MYO_RNG_STREAMS(X)
+#undef X
+};
+constexpr bool rng_streams_distinct() {
+  for (int a = 0; a < RS_COUNT; a++)
+    for (int b = a + 1; b < RS_COUNT; b++)
+      if (RNG_STREAMS[a].salt == RNG_STREAMS[b].salt && RNG_STREAMS[a].id == RNG_STREAMS[b].id) return false;
+  return true;
+}
+static_assert(rng_streams_distinct(), "two RNG streams share their (salt, id) pair");
+// draw `index` of stream S for global env ge; `step` is read by the streams whose id is a counter
+template <RngStream S> __device__ __host__ __forceinline__ float rng_u(uint64_t seed, uint64_t ge, uint64_t index, uint64_t step = 0) {
+  constexpr RngStreamRec r = RNG_STREAMS[S];
+  return u01(seed ^ r.salt, ge * r.stride + r.offset + index, r.id >= RNG_ID_ENV_STEP ? step : r.id);
+}
+__device__ __host__ __forceinline__ uint64_t rng_episode_seed(uint64_t seed, int episode) { return seed + RNG_EPISODE_MUL * (uint64_t)episode; }
 
 // MyoDM TrackEnv as a task of the TRK step kernel (mjx/myodm_v0.py:185-304; myo_batch_configure_track): action scaling onto the
 // actuator control ranges and the reference lookup in the kernel's prologue, observation / reward / done / metrics / masked reset in its
@@ -181,7 +237,7 @@ struct DevBatch {
 // key of a draw of the object parameters inside the reset's RNG stream: the shared draws first, then one per scalar parameter
 #define OBJ_MAX_DRAWS 8
 __device__ __host__ inline float obj_draw_u(uint64_t episode_seed, uint64_t global_env, int draw, int param) {
-  return u01(episode_seed ^ 0x7A5662DCDF6B1F6Dull, global_env * 1024 + (uint64_t)(draw >= 0 ? draw : OBJ_MAX_DRAWS + param), 12);
+  return rng_u<RS_OBJECT>(episode_seed, global_env, (uint64_t)(draw >= 0 ? draw : OBJ_MAX_DRAWS + param));
 }
 // bounding radius of a primitive geom from its size (mjModel.geom_rbound as the compiler sets it for these types)
 __device__ __host__ inline float obj_rbound(int type, float s0, float s1, float s2) {
@@ -209,6 +265,7 @@ struct TaskDev {
   int terrain, hf_n;        // terrain walk: myo_terrain kind and cells of the elevation grid re-drawn at reset (0: none)
   float terrain_lo, terrain_hi;
   float bd_frame[12];       // baoding task, link frame of the targets' body: its x axis (3), y axis (3), origin + z_site axis per target (3 + 3)
+  int target_floor = -1;    // component of the target row a reset rounds down and caps at its target_hi (baoding: 1, the direction sign); -1: none
 };
 
 // walk task (walk_v0.py:WalkEnvV0): its observation needs a forward pass at the post-step state, which the wave kernel

@@ -1,7 +1,7 @@
 // myo_hip.hip -- MI355X (gfx950) batched musculoskeletal stepper: kernels + C ABI (include/myo_hip.h).
 //
 // One translation unit, split over csrc/ for readability:
-//   myo_common.h        limits, device-side structs (model tables, per-env batch arrays, task records), vector math
+//   myo_common.h        limits, device-side structs (model tables, per-env batch arrays, task records), the counter RNG and the table of its streams, vector math
 //   myo_physics.h       tendon wrapping, muscle model, action map (+ muscle conditions), impedance, contact frames, MPR
 //   myo_task_track.h    MyoDM TrackEnv as a fused task of the TRK step kernel: reference lookup, reward / done, masked reset
 //   myo_kernel_lanes.h  step_kernel<G>: the first kernel, G = 16 / 32 / 64 lanes per env, all state in LDS (cross-check / fallback)
@@ -12,8 +12,11 @@
 //   myo_wave_collision.h   broad phase, narrow phase
 //   myo_wave_solver.h   constraint rows, packed mass matrix, sensor readout, task epilogues (the solver itself is inline in the kernel)
 //   myo_ldl_mfma.h      dense LDL^T of the Newton Hessian on the FP32 matrix cores (included by myo_wave_util.h)
-//   myo_kernels_aux.h   RNG, placement hint, random actions, policy inference, reset, task_obs_kernel / task_post_kernel
-//   myo_kernels_ppo.h   PPO training: policy sampling with log-probabilities, GAE (include/myo_hip_ppo.h)
+//   myo_reset.h         the reset of an env: its pieces (one per owner), reset_body, reset_kernel, ResetArgs; and, compiled by a second inclusion
+//                       after myo_host.h (launch_reset needs myo_batch, which holds a ResetArgs), launch_reset, myo_reset and myo_autoreset
+//   myo_kernels_aux.h   placement hint, random actions, link recomposition, task_obs_kernel / task_post_kernel
+//   myo_kernels_diag.h  the poison kernels of the diagnostic build, the VALU issue-rate probe
+//   myo_kernels_ppo.h   policy inference; PPO training: policy sampling with log-probabilities, GAE (include/myo_hip_ppo.h)
 //   myo_kernels_learner.h  the PPO SGD step: both MLPs forward and backward on the FP32 MFMA, loss, Adam (include/myo_hip_ppo.h)
 // Host side: a subsystem's host record, its launches and the entry points of its public header live in one file
 //   myo_host.h          shared by all of them: error reporting, device-memory pool (DevPool), use_device, blob view (Blob, blob_open), kernel
@@ -29,13 +32,13 @@
 //   myo_host_model.h    myo_model_load in pieces: table upload, packing of the per-lane records, kernel class
 //   myo_host_batch.h    batch creation, the per-env override records, the table of fields behind myo_batch_field / read / write
 //   myo_host_objects.h  per-env object parameters (include/myo_hip_objects.h): selection, tables, the per-launch compose kernel, draw table, entry points
-//   myo_host_step.h     the table of step-kernel instantiations, launch_reset, launch_step, myo_bench_rollout and the other timing entry points
+//   myo_host_step.h     the table of step-kernel instantiations, launch_step, myo_bench_rollout and the other timing entry points
 //   myo_kernel_forward.h   forward_kernel_w: frames and contact list without a step (include/myo_hip_forward.h), its export tables and buffers
 //   myo_host_forward.h  ... its instantiations, launch and entry points
 //   myo_host_policy.h   myo_policy: load, act, update, sample; myo_ppo_gae (include/myo_hip.h, include/myo_hip_ppo.h)
 //   myo_host_learner.h  myo_ppo_learner: create, tensor views, the SGD step's launches (include/myo_hip_ppo.h)
 //   myo_hip.hip         this map, the include list and the core entry points of include/myo_hip.h (and myo_hip_sensors.h): model, batch, configure,
-//                       reset, step, observation, status, set-state and the small setters
+//                       step, observation, status, set-state and the small setters
 //
 // Execution model: one environment = one wavefront = one workgroup; the whole working set of an env (link
 // frames, sparse tendon Jacobian rows, spatial inertias, mass matrix, contact rows, Newton vectors) lives in that wave's LDS slice
@@ -50,10 +53,13 @@
 #include "myo_task_track.h"
 #include "myo_kernel_lanes.h"
 #include "myo_kernel_wave.h"
+#include "myo_reset.h"
 #include "myo_kernels_aux.h"
+#include "myo_kernels_diag.h"
 #include "myo_kernels_ppo.h"
 #include "myo_kernels_learner.h"
 #include "myo_host.h"
+#include "myo_reset.h"   // its host half (see the map)
 #include "myo_rewards.h"
 #include "myo_host_tasks.h"
 #include "myo_obs_terms.h"
@@ -124,7 +130,7 @@ int myo_batch_configure(myo_batch* b, const myo_task_config* c) {
   if (c->task == MYO_TASK_WALK) return fail(MYO_E_ARG, "use myo_batch_configure_walk for the walk task");
   if (b->db.rwd && rwd_cols(c->task).n != b->db.rwd_n) return fail(MYO_E_ARG, "reward terms are enabled for a task with other columns");
   T.init_qvel = nullptr; T.rnd = nullptr;
-  T.terrain = 0; T.hf_n = 0;
+  T.terrain = 0; T.hf_n = 0; T.target_floor = -1;
   for (int k = 0; k < 3; k++) T.tip_lpos[k] = c->tip_lpos[k];
   if (c->reset_noise_lo || c->reset_noise_hi || c->reset_clip_lo || c->reset_clip_hi) {
     if (!(c->reset_noise_lo && c->reset_noise_hi && c->reset_clip_lo && c->reset_clip_hi)) return fail(MYO_E_ARG, "reset noise: all four arrays or none");
@@ -181,16 +187,6 @@ int myo_batch_configure_walk(myo_batch* b, const myo_walk_config* c) {
 int myo_batch_configure_track(myo_batch* b, const myo_track_config* c) {
   if (!b || !c) return fail(MYO_E_ARG, "myo_batch_configure_track: null");
   return b->obs_terms.terms ? fail(MYO_E_ARG, OBS_TERMS_CONFIGURED) : track_configure(b, c);
-}
-
-int myo_reset(myo_batch* b, const uint8_t* mask_dev, uint64_t seed, void* stream) {
-  if (!b) return fail(MYO_E_ARG, "myo_reset: null");
-  return launch_reset(b, mask_dev, seed, stream, 0);
-}
-
-int myo_autoreset(myo_batch* b, int max_episode_steps, uint64_t seed, void* stream) {
-  if (!b || max_episode_steps <= 0) return fail(MYO_E_ARG, "myo_autoreset: bad arguments");
-  return launch_reset(b, nullptr, seed, stream, max_episode_steps);
 }
 
 int myo_set_env_offset(myo_batch* b, int env_offset) {

@@ -3,7 +3,7 @@
 // kernel that composes the rows the step / forward kernels read (once per launch), and the entry points.  What the kernels do with the rows
 // is in the stages themselves: geom_world_pos and pair_decode / obj_pair_friction (myo_wave_util.h), the contact-row stage
 // (myo_wave_solver.h), the cinert stage (myo_wave_motion.h), the geom frames of forward_kernel_w; the draws are part of reset_body
-// (myo_kernels_aux.h).
+// (myo_reset.h).
 // Part of the single translation unit myo_hip.hip (included there, before myo_host_step.h, whose launch_step composes); not a stand-alone header.
 #ifndef MYO_HOST_OBJECTS_H
 #define MYO_HOST_OBJECTS_H

@@ -1,5 +1,5 @@
 // myo_host_policy.h -- the device policy on the host: myo_policy with its load / free / act (include/myo_hip.h) and, for PPO training, its
-// in-place update, sampling with log-probabilities and the GAE launch (include/myo_hip_ppo.h).  Kernels: myo_kernels_aux.h, myo_kernels_ppo.h.
+// in-place update, sampling with log-probabilities and the GAE launch (include/myo_hip_ppo.h).  Kernels: myo_kernels_ppo.h.
 #ifndef MYO_HOST_POLICY_H
 #define MYO_HOST_POLICY_H
 
@@ -35,7 +35,7 @@ int myo_policy_load(int device, int obs_dim, int act_dim, int nlayers, const int
 void myo_policy_free(myo_policy* p) { delete p; }
 
 // dynamic LDS of the policy kernels: two activation rows per env of a workgroup, as wide as the widest of observation, POL_MAXW and the
-// layers (policy_forward, myo_kernels_aux.h); 0: wider than the 64 KB a workgroup may ask for
+// layers (policy_forward, myo_kernels_ppo.h); 0: wider than the 64 KB a workgroup may ask for
 static size_t policy_lds_bytes(const PolicyDev& P) {
   int stride = P.obs_dim > POL_MAXW ? P.obs_dim : POL_MAXW;
   for (int l = 0; l < P.nlayers; l++) if (P.width[l] > stride) stride = P.width[l];

@@ -1,4 +1,4 @@
-// myo_host_step.h -- the step launch: the table of step_kernel_w instantiations and the choice among them, the reset launch, launch_step in
+// myo_host_step.h -- the step launch: the table of step_kernel_w instantiations and the choice among them, launch_step in
 // its pieces (lane choice and refusals, the substep scheduler's plan, the wave launch, the lanes launch), and the entry points that exist
 // to time it: myo_bench_rollout, myo_bench_last_kernel_ms / _name, myo_probe_valu (include/myo_hip.h).
 #ifndef MYO_HOST_STEP_H
@@ -47,16 +47,6 @@ static WaveKernelId select_wave_kernel(const myo_model* m, bool bm, bool sched, 
   if (m->wave_cfg == 0) return hand_sizes ? WK_HAND_SPEC : WK_HAND;
   if (m->dw.hf.on) return m->terrain_sizes ? WK_TERRAIN_SPEC : WK_TERRAIN;   // terrain models: the instantiations with the height-field narrow phase
   return leg_sizes ? WK_LEG_SPEC : WK_LEG;
-}
-
-static int launch_reset(myo_batch* b, const uint8_t* mask_dev, uint64_t seed, void* stream, int max_episode_steps) {
-  b->reset_seed = seed;
-  const DevModel& dm = b->model->dm;
-  HIPCHK(hipSetDevice(b->model->device));
-  hipLaunchKernelGGL(reset_kernel, dim3(b->db.B), dim3(64), 0, (hipStream_t)stream, b->db, b->task, b->model->nq, dm.nv, dm.nu, dm.qpos0, mask_dev, seed,
-                     b->env_offset, max_episode_steps);
-  HIPCHK(hipGetLastError());
-  return MYO_OK;
 }
 
 // Substep scheduler: MYO_SCHED=1 forces it, 0 disables it; default (auto) uses it where it was measured to pay: when the launch holds at

@@ -1,7 +1,70 @@
-// myo_kernels_ppo.h -- the device side of PPO training (include/myo_hip_ppo.h): sampling with log-probabilities, GAE.
+// myo_kernels_ppo.h -- the policy network on the device: inference (policy_kernel) and the device side of PPO training
+// (include/myo_hip_ppo.h): sampling with log-probabilities, GAE.
 // Part of the single translation unit myo_hip.hip (included there after myo_kernels_aux.h); not a stand-alone header.
 #ifndef MYO_KERNELS_PPO_H
 #define MYO_KERNELS_PPO_H
+
+// ------------------------------------------------------------------------------------------------
+// policy inference (brax PPO network family): 8 envs per 512-thread workgroup, thread = (env, hidden unit); activations ping-pong
+// through LDS, weights are read coalesced across units and shared by the 8 envs through the cache.  ~13 kMAC per env for
+// the hand observation: negligible next to the physics step, so plain FMAs (no MFMA)
+#define POL_ENVS 8
+#define POL_MAXW 64
+struct PolicyDev {
+  int obs_dim, act_dim, nlayers;
+  int width[8];               // output width of each layer
+  const float* W[8];
+  const float* b[8];
+  const float *mean, *std;
+};
+// The forward pass, shared by policy_kernel and policy_sample_kernel: one env = one wavefront (lane j of wave le);
+// returns the env's head row in LDS, [loc[act_dim], raw[act_dim]].  Every thread of the workgroup calls it (it holds the barriers)
+__device__ __forceinline__ const float* policy_forward(const PolicyDev& P, const float* __restrict__ obs, int B, float* sh, const int j, const int le, const int e) {
+  int stride = max(P.obs_dim, POL_MAXW);
+  for (int l = 0; l < P.nlayers; l++) stride = max(stride, P.width[l]);
+  float* xin = sh + le * stride;
+  float* xout = sh + (POL_ENVS + le) * stride;
+  if (e < B)
+    for (int i = j; i < P.obs_dim; i += POL_MAXW) xin[i] = (obs[(size_t)e * P.obs_dim + i] - P.mean[i]) / P.std[i];
+  __syncthreads();
+  int nin = P.obs_dim;
+  for (int l = 0; l < P.nlayers; l++) {
+    const int nout = P.width[l];
+    if (e < B) {
+      const float* Wl = P.W[l];
+      for (int jj = j; jj < nout; jj += POL_MAXW) {
+        float acc = P.b[l][jj];
+        for (int i = 0; i < nin; i++) acc += xin[i] * Wl[(size_t)i * nout + jj];
+        xout[jj] = (l + 1 < P.nlayers) ? acc / (1.0f + expf(-acc)) : acc;     // swish on hidden layers, linear head
+      }
+    }
+    __syncthreads();
+    float* t = xin; xin = xout; xout = t;
+    nin = nout;
+  }
+  return xin;
+}
+// the tanh-normal head's draw for action jj of global env ge: u = loc + scale * eps, scale = softplus(raw) + 0.001, eps by Box-Muller
+__device__ __forceinline__ float policy_draw(float loc, float raw, uint64_t seed, uint64_t step, uint64_t ge, int jj, float* scale_out) {
+  float scale = (raw > 20.f ? raw : log1pf(expf(raw))) + 0.001f;
+  float u1 = fmaxf(rng_u<RS_POLICY_U1>(seed, ge, jj, step), 1e-7f), u2 = rng_u<RS_POLICY_U2>(seed, ge, jj, step);
+  *scale_out = scale;
+  return loc + scale * sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);   // Box-Muller
+}
+__global__ void __launch_bounds__(POL_ENVS * POL_MAXW) policy_kernel(PolicyDev P, const float* __restrict__ obs, int B, float* __restrict__ action,
+                                                                     int deterministic, uint64_t seed, uint64_t step, int env_offset) {
+  extern __shared__ float sh[];                       // [POL_ENVS][max(obs_dim, POL_MAXW)] x 2
+  const int j = threadIdx.x % POL_MAXW, le = threadIdx.x / POL_MAXW;
+  const int e = blockIdx.x * POL_ENVS + le;
+  const float* head = policy_forward(P, obs, B, sh, j, le, e);
+  if (e < B) {
+    for (int jj = j; jj < P.act_dim; jj += POL_MAXW) {
+      float a = head[jj], scale;
+      if (!deterministic) a = policy_draw(a, head[P.act_dim + jj], seed, step, (uint64_t)(e + env_offset), jj, &scale);
+      action[(size_t)e * P.act_dim + jj] = tanhf(a);
+    }
+  }
+}
 
 // softplus(x) = log(1 + e^x) without overflow: max(x, 0) + log1p(e^-|x|)
 __device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }

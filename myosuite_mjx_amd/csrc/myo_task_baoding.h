@@ -103,6 +103,7 @@ static int baoding_configure(myo_batch* b, const myo_task_config* c) {
     for (int k = 0; k < 3; k++) T.bd_frame[6 + 3 * t + k] = (float)(m->body_lpos[3 * (size_t)tb + k] + R[3 * k + 2] * z);
   }
   T.obs_dim = BaodingRow{m->nq}.dim;
+  T.target_floor = 1;   // the direction sign: U(-1, 2) rounded down, one of -1, 0, +1
   return MYO_OK;
 }
 static const char* const rwd_baoding[] = {"pos_dist_1", "pos_dist_2", "act_reg", RWD_TAIL};   // baoding_v1.py:239-262

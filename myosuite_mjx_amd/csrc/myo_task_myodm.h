@@ -22,7 +22,7 @@ __device__ __forceinline__ void myodm_obs_body(const DevModel& M, const DevBatch
   const auto [o, q, v, a, dt] = task_row(M, Bt, T, e, nv);
   const int elapsed = Bt.elapsed[e];
   track_lookup<true>(K, e, e + Bt.env_offset, 0.f, elapsed, lane, (double)elapsed * (double)T.frame_skip * (double)M.timestep,
-                     seed + 0x632BE59BD9B4E019ull * (uint64_t)Bt.episode[e]);
+                     rng_episode_seed(seed, Bt.episode[e]));
   __syncthreads();                       // the reference row (written by lanes < nr + 7) is complete before every lane reads it
   const float* R = K.ref + (size_t)e * K.ref_pitch;
   const float* tc = R + 2 * nr;          // target object pose: com (3) | quaternion (4)

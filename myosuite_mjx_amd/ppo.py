@@ -32,7 +32,7 @@ from . import capi
 
 _LOG2 = math.log(2.0)
 _HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
-# limits of the policy kernel (csrc/myo_kernels_aux.h): layer widths, layer count, and the LDS tile that holds two activation rows of 8 envs
+# limits of the policy kernel (csrc/myo_kernels_ppo.h): layer widths, layer count, and the LDS tile that holds two activation rows of 8 envs
 MAX_WIDTH, MAX_LAYERS, MAX_OBS_DIM = 512, 8, 64 * 1024 // (2 * 8 * 4)
 
 

@@ -289,7 +289,7 @@ def test_host_twin_of_the_draws_is_the_counter_rng():
     t = objects.DrawTable(2, 1)
     sh, own = objects.draw_u(7, 0, 5, t)
     assert len(sh) == objects.MAX_DRAWS and len(own) == 19
-    key = 7 ^ 0x7A5662DCDF6B1F6D
+    key = 7 ^ objects._DRAW_KEY
     assert sh[3] == u01(key, 5 * 1024 + 3, 12) and own[4] == u01(key, 5 * 1024 + 8 + 4, 12)
     sh1, own1 = objects.draw_u(7, 1, 5, t)                         # another episode, another env: other draws
     sh2, own2 = objects.draw_u(7, 0, 6, t)
